@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline measurement of the downconvert + correlate hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 works two ways: under an external launcher (python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N ..., the driver's form: RANK / LOCAL_RANK / WORLD_SIZE come from the environment) or
@@ -34,6 +34,7 @@ Prints ONE JSON line on rank 0:
                device as one device group from one host thread -- peer replication of the signal (hipMemcpyPeerAsync
                between distinct devices), sharded launch, gather; bit_identical vs shard-by-shard on device 0, peer_copy_GBps
   ranks (N > 1 only) = per rank: ms per step, device name, PCI bus id; world size and backend
+  dump_outputs (--dump-outputs DIR) = the files written: the last timed step's outputs as DIR/<name>.npy (dump_outputs)
 Multi-GPU: satellite channels shard with no collective; every rank holds the full antenna signal
 and correlates its own PRNs ("weak" scaling: per-GPU work fixed).  RCCL carries only the timing
 barrier and the max-over-ranks reduction.
@@ -107,6 +108,9 @@ def parse_args(argv=None):
                     help="launch-geometry option of the library (include/gat.h gat_set_option), repeatable; recorded in the line")
     ap.add_argument("--matrix-core", type=int, choices=[0, 1, 2, 3], default=None,
                     help="kernel selection (include/gat.h GAT_MC_*): 0 vector kernel only, 1 auto (default), 2 f32 MFMA, 3 split-bf16 MFMA")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the operator's output arrays) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded sample beyond that)")
     ap.add_argument("--baseline-config", type=int, choices=[1, 2, 3, 4], default=None,
                     help="shape of BASELINE.json configs[i] (1 = the default headline workload; 2 = GPS L5, 4 ants, 12 PRNs, "
                          "5 taps @ 50 MHz; 3 = the per-GPU shard of 16 ants x 32 PRNs @ 50 MHz; 4 = 64 ants x 64 channels, "
@@ -510,6 +514,32 @@ def measure(args, g, torch, dist, world, rank, shape_kw, steps, warmup, settle, 
     return res
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, m, rank, world) -> dict:
+    """--dump-outputs: the arrays the timed path hands its caller, as its last timed step left them -- the operator's (re, im)
+    outputs [B, K, L, M], float32 -- written as out_dir/out_re.npy and out_im.npy (suffix _rank<r> when N > 1).  The
+    synthetic stream is the same from run to run, so two builds compare output for output.  Beyond 64 MB in all: a fixed
+    seeded sample of the flattened outputs, its flat indices in sample_index.npy (float64, exact)."""
+    got = m["op"].result()  # complex64 [B, K, L, M]; synchronises
+    re = np.ascontiguousarray(got.real, dtype=np.float32)
+    im = np.ascontiguousarray(got.imag, dtype=np.float32)
+    arrays = {"out_re": re, "out_im": im}
+    if re.nbytes + im.nbytes > DUMP_LIMIT_BYTES:
+        n = DUMP_LIMIT_BYTES // (4 + 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(re.size, n, replace=False))
+        arrays = {"out_re": re.reshape(-1)[idx], "out_im": im.reshape(-1)[idx], "sample_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    files = []
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + suffix + ".npy")
+        np.save(path, a)
+        files.append(os.path.basename(path))
+    return {"dir": out_dir, "files": files, "shape": list(got.shape), "sampled": "sample_index" in arrays}
+
+
 def leg_record(g, m, gnss, layout_name, args, backend, want_ceiling):
     """What every measured shape reports beside its headline figures (rank 0): launch geometry, per-step statistics, roofline
     (median-based, with the read ceiling and the issue-rate term), parity spot check."""
@@ -690,6 +720,7 @@ def main():
     m = measure(args, g, torch, dist, world, rank, shape_kw, args.steps, args.warmup, args.settle, True)
     B, N, M, L, K, layout = m["shape"]
     fs = m["fs"]
+    dumped = dump_outputs(args.dump_outputs, m, rank, world) if args.dump_outputs else None
 
     out = None
     want_ceiling = not args.no_read_ceiling
@@ -724,6 +755,8 @@ def main():
             out["config"]["options"] = list(args.option)
         if args.matrix_core is not None:
             out["config"]["options"] = out["config"].get("options", []) + [f"matrix_core={args.matrix_core}"]
+        if dumped:
+            out["dump_outputs"] = dumped
         if world > 1:
             out["ranks"] = {"world_size": world, "backend": backend, "ms_per_step_by_rank": rec["ms_per_step_by_rank"],
                             "kernel_ms_median_by_rank": rec["kernel_ms_median_by_rank"], "devices": m["devices"]}

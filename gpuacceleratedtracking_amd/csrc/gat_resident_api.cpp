@@ -236,7 +236,13 @@ GAT_API int32_t gat_resident_open(gat_ctx *c, const gat_signal_desc *sig, int32_
     res->r.max_calls = res->max_calls;
     res->r.idle_ticks = (long long)res->idle_us * res->ticks_per_us;
     res->r.life_ticks = (long long)res->life_ms * 1000ll * res->ticks_per_us;
-    if ((e = hipStreamCreateWithFlags(&res->stream, hipStreamNonBlocking)) != hipSuccess) return bail(hipfail(c, e, "hipStreamCreateWithFlags"));
+    // the kernel holds its stream's hardware queue until it leaves, and the runtime lets streams of one priority share a few
+    // queues: on a queue it shares with the caller's stream, the caller's copies and kernels would wait out its idle limit.
+    // Streams of the greatest priority take their queues from a pool of their own.
+    int prio_least = 0, prio_greatest = 0;
+    if ((e = hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest)) != hipSuccess) return bail(hipfail(c, e, "hipDeviceGetStreamPriorityRange"));
+    if ((e = hipStreamCreateWithPriority(&res->stream, hipStreamNonBlocking, prio_greatest)) != hipSuccess)
+        return bail(hipfail(c, e, "hipStreamCreateWithPriority"));
     res->seq = 1; // "the last call": nothing is pending when the kernel starts
     bell_set_seq(res, res->seq);
     rc = resident_start(res, res->seq);

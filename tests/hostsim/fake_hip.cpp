@@ -76,6 +76,13 @@ hipError_t hipMemset(void *d, int v, size_t n) { std::memset(d, v, n); return hi
 hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { std::memset(d, v, n); return hipSuccess; }
 
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = new ihipStream_t(); return hipSuccess; }
+hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { *s = new ihipStream_t(); return hipSuccess; }
+hipError_t hipDeviceGetStreamPriorityRange(int *least, int *greatest)
+{
+    *least = 0;
+    *greatest = -1;
+    return hipSuccess;
+}
 hipError_t hipStreamSynchronize(hipStream_t s)
 {
     if (s && s->worker.joinable()) s->worker.join();
