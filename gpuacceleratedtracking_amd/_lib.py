@@ -41,6 +41,8 @@ EXPORTS = [
     "gat_tracking_update_host", "gat_resident_tracking_run", "gat_resident_park_all",
     # measurement: per-call statistics, the in-run read ceiling; the texture-addressing study
     "gat_timer_lap", "gat_timer_laps", "gat_debug_read_stream", "gat_gen_code_replica_texaddr",
+    # acquisition: the PRN x Doppler x code-phase search that seeds the tracking loops
+    "gat_acquire", "gat_acq_stats_host",
 ]
 
 
@@ -107,6 +109,22 @@ class ResidentInfo(C.Structure):
 
     _fields_ = [("workgroups", C.c_int32), ("splits", C.c_int32), ("running", C.c_int32), ("last_exit", C.c_int32),
                 ("launches", C.c_uint64), ("calls", C.c_uint64)]
+
+
+class AcqConfig(C.Structure):
+    """gat_acq_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("num_doppler_bins", C.c_int32), ("if_hz", C.c_double),
+                ("code_freq_hz", C.c_double), ("doppler_first_hz", C.c_double), ("doppler_step_hz", C.c_double),
+                ("first_shift", C.c_int64), ("code_step_samples", C.c_int32), ("num_code_bins", C.c_int32),
+                ("min_peak_ratio", C.c_double), ("code_length", C.c_int32), ("reserved", C.c_int32)]
+
+
+ACQ_RESULT_DTYPE = np.dtype([("prn", "<i4"), ("detected", "<i4"), ("doppler_bin", "<i4"), ("code_bin", "<i4"),
+                             ("peak_power", "<f8"), ("noise_power", "<f8"), ("second_power", "<f8"),
+                             ("peak_to_second", "<f8"), ("cn0_dbhz", "<f8"), ("carrier_doppler_hz", "<f8"),
+                             ("code_phase_chips", "<f8"), ("num_noise_bins", "<i8")])
+assert C.sizeof(AcqConfig) == 72 and ACQ_RESULT_DTYPE.itemsize == 80
 
 
 _LIB = None
@@ -195,6 +213,8 @@ def load(build_if_missing: bool = True):
         "gat_timer_laps": (i32, [vp, C.POINTER(C.c_float), i32, i32p]),
         "gat_debug_read_stream": (i32, [vp, vp, C.c_size_t, i32, i32, C.POINTER(C.c_float)]),
         "gat_gen_code_replica_texaddr": (i32, [vp, vp, i64, i32, dbl, dbl, dbl, i64, i32, i32]),
+        "gat_acquire": (i32, [vp, sp, i32, i32p, i32, dbl, C.POINTER(AcqConfig), vp, vp]),
+        "gat_acq_stats_host": (i32, [vp, i32, i32, i32, C.POINTER(AcqConfig), dbl, i64, vp]),
     }
     assert sorted(sigs) == sorted(EXPORTS)
     for name, (res, args) in sigs.items():

@@ -1,0 +1,41 @@
+// gat_acq_kernels.h -- what the acquisition kernels (gat_acq.hip) and their host side (gat_acq_api.cpp) share: the grid
+// kernel's geometry, its arguments and the launchers.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "gat.h"
+
+namespace gat {
+
+constexpr int kAcqThreads = 256;    // four wave64
+constexpr int kAcqDopPerWave = 8;   // Doppler bins of one wave's register tile
+constexpr int kAcqCodePerLane = 4;  // code bins of one lane's register tile (lane + 64 r)
+constexpr int kAcqDopTile = kAcqDopPerWave * (kAcqThreads / 64); // 32 Doppler bins per workgroup
+constexpr int kAcqCodeTile = kAcqCodePerLane * 64;               // 256 code bins per workgroup
+constexpr int kAcqChunk = 128;      // samples staged per step (a power of two dividing kAcqThreads)
+constexpr int kAcqMaxCodeStep = 31; // s: the replica window (kAcqChunk + s * 255 chip pairs) stays within 64 KB of LDS
+
+struct AcqArgs {
+    const void *re, *im;
+    int M, B;
+    long long N, ant_stride, block_stride;
+    const int8_t *codes;
+    int code_row_stride, Lc;
+    const int *prns; // [P] code-table columns
+    int P, D, J, s, G;
+    double ratio, fs, if_hz, f_first, f_step; // ratio = fc / fs
+    long long first_shift;
+    float *out; // [G][P][D][J]: the power grid itself when G == 1, else the groups' slices
+};
+
+size_t acq_grid_lds_bytes(int s);
+hipError_t acq_grid_allow_lds(int s);
+hipError_t launch_acq_grid(const AcqArgs &a, int fmt, hipStream_t st);
+hipError_t launch_acq_sum_groups(const float *part, float *power, long long cells, int G, hipStream_t st);
+hipError_t launch_acq_stats(const float *power, int P, int D, int J, const gat_acq_config &cfg, double fs, long long N,
+                            const int *prns, gat_acq_result *res, hipStream_t st);
+
+} // namespace gat

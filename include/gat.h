@@ -526,6 +526,72 @@ GAT_API int32_t gat_group_gather(gat_group *group, float *const *out_re_dev, flo
                                  float *out_re_host, float *out_im_host);
 GAT_API int32_t gat_group_sync(gat_group *group);
 
+/* ---- signal acquisition: the search that seeds the tracking loops --------------------------------------------------
+ * Acquisition.jl's `acquire(system, signal, sampling_frequency, prns; interm_freq, max_doppler, dopplers, ...)` (the
+ * reference starts every track from an estimate its own code never produces: init_carrier_doppler_hz above,
+ * src/benchmarks.jl:54-61 builds its TrackingState from fixed values).  For every PRN p, Doppler bin i < D and code bin
+ * j < J the search computes
+ *   P[p,i,j] = sum_b sum_m | R[b, (p,i), j, m] |^2
+ * where R is exactly what gat_downconvert_and_correlate returns for the channel record
+ *   {prn p, code_freq fc, carrier_freq if_hz + f_i, code_phase tau_b, carrier_phase 0}
+ * with f_i = doppler_first_hz + i * doppler_step_hz, tau_b = fmod(fc/fs * (double)(b * block_stride), Lc) (the code phase
+ * continues from block to block) and the tap shift Delta_j = first_shift + s * j samples: coherent over one block's N
+ * samples, non-coherent over antennas and blocks.  Bin j's code phase at sample 0 of block 0 is fc/fs * Delta_j mod Lc, the
+ * convention of gat_channel_params.code_phase_chips.  Code Doppler is neglected (every bin uses fc, so one replica serves
+ * every Doppler bin): a signal at Doppler f_d drifts by fc * |f_d| / f_carrier * B * N / fs chips over the search (GPS L1,
+ * 5 kHz, 10 ms: 0.03 chip).
+ * power: dev float [P x D x J] (code bin fastest), deterministic (no float atomics; the same call gives the same bits). */
+typedef struct gat_acq_config {
+    uint32_t struct_size;       /* sizeof(gat_acq_config) of the caller's header                                    */
+    int32_t num_doppler_bins;   /* D >= 1                                                                          */
+    double if_hz;               /* intermediate frequency of the sampled signal                                     */
+    double code_freq_hz;        /* fc: nominal code frequency (chips/s)                                             */
+    double doppler_first_hz;    /* f_0                                                                             */
+    double doppler_step_hz;     /* f_{i+1} - f_i                                                                   */
+    int64_t first_shift;        /* Delta_0 in samples (any sign): a fine search starts its code window here         */
+    int32_t code_step_samples;  /* s: 1 .. 31 samples between code bins                                             */
+    int32_t num_code_bins;      /* J >= 1                                                                          */
+    double min_peak_ratio;      /* detection threshold on peak / second (0: default 2.0)                            */
+    int32_t code_length;        /* Lc in chips: gat_acquire 0 = the bound table's; gat_acq_stats_host: required     */
+    int32_t reserved;           /* must be 0                                                                       */
+} gat_acq_config;
+
+/* Per-PRN result.  Peak (i*, j*) = the largest bin (the first in [D x J] order on ties).  The Doppler and the code phase
+ * are refined by a three-point parabola on power through the peak's neighbours along that axis, clamped to +-0.5 bin; a
+ * peak on the grid's edge (or a neighbourhood that is not concave) keeps the bin centre.  The code phase is wrapped into
+ * [0, Lc).  The noise set = every bin, in every Doppler row, whose circular code distance from the peak's code phase is
+ * more than 1.5 chips; with fewer than 64 such bins (a narrow fine search) noise_power, second_power, peak_to_second and
+ * cn0_dbhz are NaN and detected = -1. */
+typedef struct gat_acq_result {
+    int32_t prn;                /* the code-table column searched (gat_acq_stats_host: the row index p)             */
+    int32_t detected;           /* 1: peak_to_second >= min_peak_ratio, 0: not, -1: no noise estimate                 */
+    int32_t doppler_bin;        /* i*                                                                              */
+    int32_t code_bin;           /* j*                                                                              */
+    double peak_power;          /* P[p, i*, j*]                                                                    */
+    double noise_power;         /* mean over the noise set                                                         */
+    double second_power;        /* maximum over the noise set                                                      */
+    double peak_to_second;      /* peak_power / second_power                                                       */
+    double cn0_dbhz;            /* 10 log10((peak - noise) / (noise * N / fs))                                     */
+    double carrier_doppler_hz;  /* f_0 + (i* + di) * doppler_step_hz                                              */
+    double code_phase_chips;    /* fc/fs * (first_shift + s * (j* + dj)) mod Lc                                    */
+    int64_t num_noise_bins;     /* size of the noise set                                                           */
+} gat_acq_result;
+
+/* The search on the device for num_prns PRNs (prns_host: code-table columns) over num_blocks blocks of `signal` (any
+ * layout, any alignment, any N; chan_stride must be 0).  power_dev: dev float [num_prns x D x J] that receives the grid,
+ * or NULL (the grid stays in the context's scratch).  results_host: num_prns results.  Synchronises: the results are on the
+ * host when the call returns.  Bounds: num_prns * D * J <= 2^26 bins, N + |first_shift| + s * J < 2^30 samples, else
+ * GAT_ERR_RANGE; GAT_ERR_STATE before gat_set_codes. */
+GAT_API int32_t gat_acquire(gat_ctx *ctx, const gat_signal_desc *signal, int32_t num_blocks, const int32_t *prns_host,
+                            int32_t num_prns, double sampling_freq_hz, const gat_acq_config *config, float *power_dev,
+                            gat_acq_result *results_host);
+
+/* The same statistics on the HOST over a grid power_host [num_prns x D x J] (the arithmetic is csrc/gat_acq.h, shared with
+ * the device): N and sampling_freq_hz enter the C/N0 only.  Needs no context and no device. */
+GAT_API int32_t gat_acq_stats_host(const float *power_host, int32_t num_prns, int32_t num_doppler_bins, int32_t num_code_bins,
+                                   const gat_acq_config *config, double sampling_freq_hz, int64_t num_samples,
+                                   gat_acq_result *results_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,36 @@ struct ResidentInfo
     calls::UInt64
 end
 
+# struct gat_acq_config (72 bytes) / gat_acq_result (80 bytes): the acquisition search (include/gat.h gat_acquire)
+struct AcqConfig
+    struct_size::UInt32
+    num_doppler_bins::Int32
+    if_hz::Float64
+    code_freq_hz::Float64
+    doppler_first_hz::Float64
+    doppler_step_hz::Float64
+    first_shift::Int64
+    code_step_samples::Int32
+    num_code_bins::Int32
+    min_peak_ratio::Float64
+    code_length::Int32
+    reserved::Int32
+end
+struct AcqResult
+    prn::Int32
+    detected::Int32
+    doppler_bin::Int32
+    code_bin::Int32
+    peak_power::Float64
+    noise_power::Float64
+    second_power::Float64
+    peak_to_second::Float64
+    cn0_dbhz::Float64
+    carrier_doppler_hz::Float64
+    code_phase_chips::Float64
+    num_noise_bins::Int64
+end
+
 struct GatError <: Exception
     status::Int32
     msg::String
@@ -658,6 +688,29 @@ function gen_code_replica_texaddr!(ctx::Context, code_replica_dev::Ptr{Cfloat}, 
                      (Ptr{Cvoid}, Ptr{Cfloat}, Int64, Int32, Float64, Float64, Float64, Int64, Int32, Int32),
                      ctx.handle, code_replica_dev, Int64(count), Int32(prn - 1), code_frequency_hz, sampling_frequency_hz,
                      start_code_phase, Int64(first_shift), Int32(coord_frac_bits), Int32(texel_frac_bits)))
+end
+
+# ---- acquisition (Acquisition.jl's acquire): power over PRN x Doppler x code phase on the device, per-PRN statistics
+#      (peak, noise, C/N0, detection) on the host.  `prns` are 1-based as in the reference; power_dev: a device buffer of
+#      length(prns) * D * J Float32 (code bin fastest) or C_NULL.  Synchronises.
+function acquire!(ctx::Context, desc::SignalDesc, num_blocks::Integer, prns::AbstractVector{<:Integer}, sampling_frequency_hz::Float64,
+                  cfg::AcqConfig, power_dev::Ptr{Cvoid} = C_NULL)
+    cols = Int32[p - 1 for p in prns]
+    res = Vector{AcqResult}(undef, length(cols))
+    check(ctx, ccall((:gat_acquire, libgat), Int32,
+                     (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Ptr{Int32}, Int32, Float64, Ref{AcqConfig}, Ptr{Cvoid}, Ptr{AcqResult}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), cols, Int32(length(cols)), sampling_frequency_hz, Ref(cfg),
+                     power_dev, res))
+    res
+end
+# the same statistics over a host grid power[J, D, P] (Julia's column-major view of the library's [P x D x J])
+function acq_stats_host(power::Array{Float32,3}, cfg::AcqConfig, sampling_frequency_hz::Float64, num_samples::Integer)
+    J, D, P = size(power)
+    res = Vector{AcqResult}(undef, P)
+    rc = ccall((:gat_acq_stats_host, libgat), Int32, (Ptr{Cfloat}, Int32, Int32, Int32, Ref{AcqConfig}, Float64, Int64, Ptr{AcqResult}),
+               power, Int32(P), Int32(D), Int32(J), Ref(cfg), sampling_frequency_hz, Int64(num_samples), res)
+    rc == GAT_OK || throw(GatError(rc, "gat_acq_stats_host"))
+    res
 end
 
 end # module
