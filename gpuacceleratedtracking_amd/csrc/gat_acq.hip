@@ -14,9 +14,10 @@
 //     evaluation, gat_phase.h sincos_cycles on the double-precision phase);
 //   * wave w owns Doppler bins 8w .. 8w+7, lane l the code bins l + 64 r (r < 4): an 8 x 4 register tile of complex sums,
 //     two FMAs per (Doppler, code, sample), one 16-byte broadcast read per (Doppler bin, two samples) and one 8-byte read per
-//     (code bin, two samples).  The tile sums one chunk at a time and is then added to a second tile holding the block's
-//     sums: a two-level sum whose rounding stays ~1e-7 relative at N = 20 000 (a single running sum per lane over a whole
-//     1 ms block at 20 MHz drifts to ~1e-5).
+//     (code bin, two samples).  The tile sums kAcqChunksPerSum chunks (1024 samples) and is then added to a second tile
+//     holding the block's sums: a two-level sum.  A single running sum per lane over a whole 1 ms block at 20 MHz drifts to
+//     ~1e-5; adding every 128-sample chunk into the block's sum kept 20 000 samples at ~1e-6 but not 2^21 (a bin of a
+//     Doppler row off the peak missed 1e-5).  1024-sample sums balance the two levels' rounding over that range.
 // An antenna's coherent sums are finished before they are squared.  Antennas and blocks (the non-coherent units) are split
 // over G workgroup groups when the grid alone does not fill the device; every group owns its own slice of a scratch grid
 // (plain stores / read-modify-writes of bins only it touches), and a second kernel adds the G slices in a fixed order: no
@@ -31,6 +32,8 @@
 namespace gat {
 
 namespace {
+
+constexpr int kAcqChunksPerSum = 8; // chunks the register tile sums before it is added to the block's sum
 
 template <int FMT>
 __device__ __forceinline__ void acq_load(const void *re, const void *im, size_t e, float &xr, float &xi)
@@ -82,7 +85,9 @@ __global__ void __launch_bounds__(kAcqThreads, 2) acq_grid_kernel(const AcqArgs 
 #pragma unroll
             for (int r = 0; r < kAcqCodePerLane; ++r) tot_re[d][r] = tot_im[d][r] = 0.f;
 
+        float acc_re[kAcqDopPerWave][kAcqCodePerLane], acc_im[kAcqDopPerWave][kAcqCodePerLane];
         for (long long n0 = 0; n0 < a.N; n0 += kAcqChunk) {
+            const int chunk = (int)(n0 / kAcqChunk); // N < 2^30
             __syncthreads(); // the previous chunk's reads are done (and s_step is written before the first)
             // replica window: entry e <-> x = n0 + first_shift + s j0 + e; pair e = (chip e, chip e + 1)
             const long long x0 = n0 + a.first_shift + (long long)s * j0;
@@ -110,11 +115,12 @@ __global__ void __launch_bounds__(kAcqThreads, 2) acq_grid_kernel(const AcqArgs 
             __syncthreads();
             const float4 *wv = s_w + (size_t)wave * kAcqDopPerWave * (kAcqChunk / 2);
             const float2 *rp = reinterpret_cast<const float2 *>(s_rep) + (size_t)s * lane;
-            float acc_re[kAcqDopPerWave][kAcqCodePerLane], acc_im[kAcqDopPerWave][kAcqCodePerLane];
+            if (chunk % kAcqChunksPerSum == 0) {
 #pragma unroll
-            for (int d = 0; d < kAcqDopPerWave; ++d)
+                for (int d = 0; d < kAcqDopPerWave; ++d)
 #pragma unroll
-                for (int r = 0; r < kAcqCodePerLane; ++r) acc_re[d][r] = acc_im[d][r] = 0.f;
+                    for (int r = 0; r < kAcqCodePerLane; ++r) acc_re[d][r] = acc_im[d][r] = 0.f;
+            }
 #pragma unroll 2
             for (int n = 0; n < kAcqChunk; n += 2) {
                 float2 cp[kAcqCodePerLane];
@@ -132,13 +138,15 @@ __global__ void __launch_bounds__(kAcqThreads, 2) acq_grid_kernel(const AcqArgs 
                     }
                 }
             }
+            if (chunk % kAcqChunksPerSum == kAcqChunksPerSum - 1 || n0 + kAcqChunk >= a.N) {
 #pragma unroll
-            for (int d = 0; d < kAcqDopPerWave; ++d)
+                for (int d = 0; d < kAcqDopPerWave; ++d)
 #pragma unroll
-                for (int r = 0; r < kAcqCodePerLane; ++r) {
-                    tot_re[d][r] += acc_re[d][r];
-                    tot_im[d][r] += acc_im[d][r];
-                }
+                    for (int r = 0; r < kAcqCodePerLane; ++r) {
+                        tot_re[d][r] += acc_re[d][r];
+                        tot_im[d][r] += acc_im[d][r];
+                    }
+            }
         }
         // |R|^2 of this antenna and block into the group's slice: the first unit stores, the later ones add
         float *out = a.out + (size_t)(g * a.P + p) * a.D * a.J;
@@ -237,12 +245,6 @@ __global__ void __launch_bounds__(256) acq_stats_kernel(const float *__restrict_
 }
 
 } // namespace
-
-size_t acq_grid_lds_bytes(int s)
-{
-    return kAcqDopTile * sizeof(double) + (size_t)kAcqDopTile * kAcqChunk * 2 * sizeof(float) +
-           (size_t)(kAcqChunk + s * (kAcqCodeTile - 1)) * 2 * sizeof(float);
-}
 
 hipError_t launch_acq_grid(const AcqArgs &a, int fmt, hipStream_t st)
 {

@@ -31,7 +31,13 @@ struct AcqArgs {
     float *out; // [G][P][D][J]: the power grid itself when G == 1, else the groups' slices
 };
 
-size_t acq_grid_lds_bytes(int s);
+// LDS of one grid workgroup for code step s: the Doppler steps, the wiped samples and the chunk's replica window as chip pairs
+inline size_t acq_grid_lds_bytes(int s)
+{
+    return kAcqDopTile * sizeof(double) + (size_t)kAcqDopTile * kAcqChunk * 2 * sizeof(float) +
+           (size_t)(kAcqChunk + s * (kAcqCodeTile - 1)) * 2 * sizeof(float);
+}
+
 hipError_t acq_grid_allow_lds(int s);
 hipError_t launch_acq_grid(const AcqArgs &a, int fmt, hipStream_t st);
 hipError_t launch_acq_sum_groups(const float *part, float *power, long long cells, int G, hipStream_t st);

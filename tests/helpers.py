@@ -77,3 +77,51 @@ def check_close(got, ref, rtol=RTOL, what="", floor_frac=None, abs_floor=0.0):
             strong = np.abs(r) >= 0.1 * scale
             rel = (np.abs(g - r)[strong] / np.abs(r)[strong]).max()
             assert rel <= rtol, f"{what} block {b} chan {k}: element-wise error {rel:.3e} > {rtol}"
+
+
+# ---- the acquisition search (include/gat.h gat_acquire) ----------------------------------------------------------------
+def acq_power_oracle(re, im, codes, prn, fc, lc, fs, if_hz, f_first, f_step, rows, first_shift, s, cols, N, B,
+                     block_stride):
+    """The search's power P[i, j] for PRN ``prn`` (code-table row), Doppler rows ``rows`` and code bins ``cols``, built from
+    the FP64 correlator exactly as gat_acquire's contract states it: the channel record {prn, fc, if + f_i, tau_b, 0} with
+    f_i = f_first + i f_step and tau_b = fmod(fc / fs * b * block_stride, Lc), the tap first_shift + s j, |R|^2 summed over
+    antennas and blocks.  re / im: float32 [M, ld] planar (the antenna stride is ld).  Returns float64 [len(rows), len(cols)]."""
+    rows = np.asarray(rows, dtype=np.int64)
+    cols = np.asarray(cols, dtype=np.int64)
+    f = if_hz + (f_first + rows.astype(np.float64) * f_step)
+    tau = np.fmod(fc / fs * (np.arange(B, dtype=np.int64) * block_stride).astype(np.float64), float(lc))
+    shifts = (first_shift + s * cols).astype(np.int32)
+    K = rows.size
+    prm = oracle.make_params(np.full((B, K), prn), fc, np.broadcast_to(f, (B, K)), np.broadcast_to(tau[:, None], (B, K)), 0.0)
+    R = oracle.correlate_f64(re, im, codes, prm, fs, shifts, N=N, blk_stride=block_stride)  # [B, K, L, M]
+    return (R.real ** 2 + R.imag ** 2).sum(axis=(0, 3))
+
+
+def acq_sample_bins(rng, D, J, n_rows=4, n_cols=12, rows=(), cols=()):
+    """Sorted Doppler rows and code bins to compare: the grid's edges and tile seams (rows 0, D - 1, 31, 32; bins 0, J - 1,
+    255, 256, where they exist), ``rows`` / ``cols`` (the peak), and a few random ones."""
+    r = [0, D - 1, 31, 32, *rows, *rng.integers(0, D, n_rows)]
+    c = [0, J - 1, 255, 256, *cols, *rng.integers(0, J, n_cols)]
+    return (np.unique([i for i in r if 0 <= i < D]).astype(np.int64), np.unique([j for j in c if 0 <= j < J]).astype(np.int64))
+
+
+def check_power_close(got, ref, rtol=RTOL, what=""):
+    """got / ref [rows, cols] powers over the sampled bins, judged per Doppler row as check_close judges a channel: norm-wise
+    max|dP| / max P_ref, and element-wise on the bins with P_ref >= 0.1 of the row's sampled maximum.  Returns the worst
+    (norm-wise, element-wise) errors."""
+    got = np.asarray(got, dtype=np.float64)
+    ref = np.asarray(ref, dtype=np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    assert np.isfinite(got).all(), f"{what}: non-finite power"
+    worst_n = worst_e = 0.0
+    for r in range(ref.shape[0]):
+        scale = ref[r].max()
+        assert scale > 0, f"{what} row {r}: zero reference"
+        d = np.abs(got[r] - ref[r])
+        e_inf = d.max() / scale
+        strong = ref[r] >= 0.1 * scale
+        rel = (d[strong] / ref[r][strong]).max()
+        assert e_inf <= rtol, f"{what} row {r}: norm-wise error {e_inf:.3e} > {rtol}"
+        assert rel <= rtol, f"{what} row {r}: element-wise error {rel:.3e} > {rtol}"
+        worst_n, worst_e = max(worst_n, e_inf), max(worst_e, rel)
+    return worst_n, worst_e

@@ -4,11 +4,17 @@
 // contract, over thousands of random shapes, under ASan / UBSan on the CPU.  A launch of the resident kernel starts a host
 // thread that plays the device's side of the doorbell protocol (gat_resident.h), so that gat_resident_*'s host side --
 // ring, wait, second stage, restart after the kernel has left -- runs for real.  Test infrastructure only.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <thread>
 
+#include "gat_acq_kernels.h"
+#include "gat_ctx.h"
 #include "gat_internal.h"
 #include "hostsim.h"
 
@@ -200,6 +206,104 @@ hipError_t launch_tracking_update(const float *, const float *, int, int, const 
 {
     ++counters.other_launches;
     REQUIRE(cur != nullptr && next != nullptr && cur != next, "tracking update: parameter ping-pong");
+    return hipSuccess;
+}
+
+// ---- the acquisition search (gat_acq.hip) ---------------------------------------------------------------------------------
+// Each launch is checked against what acq_grid_kernel / acq_sum_groups_kernel / acq_stats_kernel assume, and every byte a
+// kernel would read or write is touched, so that ASan reports a wrong offset in gat_acquire's scratch carve-up.
+static size_t acq_allowed_lds = 0;            // what acq_grid_allow_lds granted last
+static const float *acq_last_grid_out = nullptr; // the grid launch's `out`, for the group sum and statistics that follow
+static long long acq_last_cells = 0;
+static int acq_last_G = 0;
+
+hipError_t acq_grid_allow_lds(int s)
+{
+    const size_t lds = acq_grid_lds_bytes(s);
+    REQUIRE(s >= 1 && s <= kAcqMaxCodeStep && lds <= 160 * 1024, "acq: LDS %zu bytes for code step %d", lds, s);
+    acq_allowed_lds = lds;
+    return hipSuccess;
+}
+
+hipError_t launch_acq_grid(const AcqArgs &a, int fmt, hipStream_t)
+{
+    ++counters.acq_grid_launches;
+    if (a.G > 1) ++counters.acq_split_launches;
+    const long long jt = (a.J + kAcqCodeTile - 1) / kAcqCodeTile, dt = (a.D + kAcqDopTile - 1) / kAcqDopTile;
+    const long long z = (long long)a.P * a.G, cells = (long long)a.P * a.D * a.J, units = (long long)a.M * a.B;
+    REQUIRE(fmt >= GAT_LAYOUT_PLANAR && fmt <= GAT_LAYOUT_INTERLEAVED_I8 && (fmt == GAT_LAYOUT_PLANAR) == (a.im != nullptr) && a.re,
+            "acq: layout %d", fmt);
+    REQUIRE(a.P >= 1 && a.D >= 1 && a.J >= 1 && z <= 65535 && jt <= 0x7fffffff && dt <= 65535, "acq: grid %lld x %lld x %lld", jt, dt, z);
+    REQUIRE(a.G >= 1 && a.G <= units, "acq: %d groups for %lld units", a.G, units);
+    REQUIRE(a.s >= 1 && a.s <= kAcqMaxCodeStep && acq_grid_lds_bytes(a.s) <= acq_allowed_lds && acq_allowed_lds <= 160 * 1024,
+            "acq: code step %d, LDS %zu of %zu allowed", a.s, acq_grid_lds_bytes(a.s), acq_allowed_lds);
+    REQUIRE(a.N >= 1 && a.M >= 1 && a.B >= 1 && (a.M == 1 || a.ant_stride >= 1) && (a.B == 1 || a.block_stride >= 1), "acq: signal %lld x %d x %d", a.N, a.M, a.B);
+    // the replica window: sample index x = n0 + first_shift + s j0 + e, e < kAcqChunk + s (kAcqCodeTile - 1), as the kernel
+    // evaluates it (an int), within what chip_index evaluates exactly for any tau in [0, Lc) (code_span_bad)
+    const long long last_n0 = (a.N - 1) / kAcqChunk * kAcqChunk, rep_len = kAcqChunk + (long long)a.s * (kAcqCodeTile - 1);
+    const long long x_lo = a.first_shift, x_hi = last_n0 + a.first_shift + (long long)a.s * (jt - 1) * kAcqCodeTile + rep_len - 1;
+    const double reach = (double)std::max(std::llabs(x_lo), std::llabs(x_hi));
+    REQUIRE(x_lo > INT32_MIN && x_hi < INT32_MAX, "acq: window index %lld .. %lld", x_lo, x_hi);
+    REQUIRE(code_span_ok(a.ratio, (double)a.Lc, reach, a.Lc), "acq: code span for ratio %g over %g samples", a.ratio, reach);
+    REQUIRE(a.ratio > 0.0 && std::isfinite(a.fs) && a.fs > 0.0, "acq: ratio %g fs %g", a.ratio, a.fs);
+    // the PRNs' code rows, the signal's first and last sample of every (antenna, block) unit, the output slices
+    volatile long sink = 0;
+    for (int p = 0; p < a.P; ++p) {
+        REQUIRE(a.prns[p] >= 0, "acq: prn %d", a.prns[p]);
+        sink += a.codes[(size_t)a.prns[p] * a.code_row_stride] + a.codes[(size_t)a.prns[p] * a.code_row_stride + a.Lc - 1];
+    }
+    const size_t bytes = fmt == GAT_LAYOUT_PLANAR ? 4 : fmt == GAT_LAYOUT_INTERLEAVED ? 8 : fmt == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 2;
+    for (long long u = 0; u < units; ++u) {
+        const long long m = u % a.M, b = u / a.M;
+        for (const long long n : {0ll, a.N - 1}) {
+            const size_t e = (size_t)(b * a.block_stride + m * a.ant_stride + n);
+            if (fmt == GAT_LAYOUT_PLANAR) {
+                sink += static_cast<const unsigned char *>(a.re)[e * bytes + bytes - 1] + static_cast<const unsigned char *>(a.im)[e * bytes];
+            } else {
+                sink += static_cast<const unsigned char *>(a.re)[e * bytes] + static_cast<const unsigned char *>(a.re)[e * bytes + bytes - 1];
+            }
+        }
+    }
+    (void)sink;
+    const auto *o0 = reinterpret_cast<const unsigned char *>(a.out), *o1 = o0 + (size_t)a.G * cells * sizeof(float);
+    const auto *q0 = reinterpret_cast<const unsigned char *>(a.prns), *q1 = q0 + (size_t)a.P * sizeof(int);
+    REQUIRE(o1 <= q0 || q1 <= o0, "acq: the grid's output overlaps the PRN list");
+    std::memset(a.out, 0, (size_t)a.G * cells * sizeof(float));
+    acq_last_grid_out = a.out;
+    acq_last_cells = cells;
+    acq_last_G = a.G;
+    return hipSuccess;
+}
+
+hipError_t launch_acq_sum_groups(const float *part, float *power, long long cells, int G, hipStream_t)
+{
+    ++counters.other_launches;
+    REQUIRE(G > 1 && G == acq_last_G && part == acq_last_grid_out && cells == acq_last_cells, "acq: group sum of %d slices", G);
+    REQUIRE(power + cells <= part || part + (size_t)G * cells <= power, "acq: the group sum's output overlaps its slices");
+    volatile float sink = part[0] + part[(size_t)G * cells - 1];
+    (void)sink;
+    std::memset(power, 0, (size_t)cells * sizeof(float));
+    acq_last_grid_out = power;
+    return hipSuccess;
+}
+
+hipError_t launch_acq_stats(const float *power, int P, int D, int J, const gat_acq_config &cfg, double fs, long long N,
+                            const int *prns, gat_acq_result *res, hipStream_t)
+{
+    ++counters.other_launches;
+    REQUIRE(power == acq_last_grid_out && (long long)P * D * J == acq_last_cells, "acq: statistics of a grid the search did not write");
+    REQUIRE(cfg.code_length >= 1 && cfg.num_doppler_bins == D && cfg.num_code_bins == J && N >= 1 && fs > 0.0, "acq: statistics config");
+    const auto *r0 = reinterpret_cast<const unsigned char *>(res), *r1 = r0 + (size_t)P * sizeof(gat_acq_result);
+    const auto *g0 = reinterpret_cast<const unsigned char *>(power), *g1 = g0 + (size_t)P * D * J * sizeof(float);
+    const auto *q0 = reinterpret_cast<const unsigned char *>(prns), *q1 = q0 + (size_t)P * sizeof(int);
+    REQUIRE((r1 <= g0 || g1 <= r0) && (r1 <= q0 || q1 <= r0), "acq: the results overlap the grid or the PRN list");
+    volatile float sink = power[0] + power[(size_t)P * D * J - 1];
+    for (int p = 0; p < P; ++p) {
+        sink = sink + (float)prns[p];
+        std::memset(&res[p], 0, sizeof(gat_acq_result));
+        res[p].prn = prns[p];
+    }
+    (void)sink;
     return hipSuccess;
 }
 

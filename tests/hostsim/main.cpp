@@ -5,6 +5,8 @@
 //      GAT_ERR_* codes, never crash;
 //   2. the closed loop (eager and graph replay with its LRU), device groups (shard, replicate, correlate, gather), the
 //      stand-alone operators, timers, scratch reallocation;
+//   1b. random acquisition searches (gat_acq_api.cpp): valid and invalid configs, L1 / L5 tables, caller's grid or none --
+//      every launch is checked by fake_kernels.cpp, which touches every byte the kernels would; the host statistics on grids with ties;
 //   3. the resident correlator's host side against a host thread that plays the device: rings at random distances around
 //      the kernel's idle limit and call budget, park, code-table change, free, close, destroy with correlators still open --
 //      every call must return exactly what the emulated workgroups posted, summed by the host's second stage.
@@ -150,6 +152,154 @@ int main(int argc, char **argv)
     EXPECT(gat_set_matrix_core(ctx, 1) == GAT_OK, "kernel selection back to auto");
     for (int o = 0; o < 18; ++o) gat_set_option(ctx, opts[o], o == 17 ? 2 : o == 0 ? 1024 : o == 1 ? 4 : o == 2 ? 4 : o == 3 ? 4 : o == 4 ? 16 : o == 5 ? 0 : o == 6 ? 0 : o == 7 ? 1 : o == 8 ? -1 : o == 9 ? 4 : o == 10 ? 2 : o == 11 ? -1 : o == 12 ? 1 : o == 15 ? 1 : o == 16 ? -1 : 0);
     EXPECT(gat_set_codes(ctx, codes.data(), lc, 32) == GAT_OK, "rebind L1");
+
+    // ---- 1b. random acquisition searches (gat_acquire, gat_acq_stats_host) ---------------------------------------------------
+    {
+        gat_ctx *fresh = nullptr;
+        EXPECT(gat_create(0, GAT_OWN_STREAM, &fresh) == GAT_OK, "context for the state check");
+        gat_signal_desc sig = {(void *)0x100000, (void *)0x200000, GAT_LAYOUT_PLANAR, 1, 1000, 1000, 1000, 0};
+        gat_acq_config cfg{};
+        cfg.struct_size = sizeof cfg;
+        cfg.num_doppler_bins = cfg.num_code_bins = cfg.code_step_samples = 1;
+        cfg.code_freq_hz = fc;
+        int32_t prn = 0;
+        gat_acq_result r{};
+        EXPECT(gat_acquire(fresh, &sig, 1, &prn, 1, 4e6, &cfg, nullptr, &r) == GAT_ERR_STATE, "acquire without codes");
+        EXPECT(gat_destroy(fresh) == GAT_OK, "destroy");
+    }
+    long acq_launched = 0, acq_rejected = 0, acq_stats_ok = 0;
+    const long acq_split0 = hostsim::counters.acq_split_launches.load();
+    gat_ctx *actx = ctx;
+    for (int it = 0; it < calls / 4; ++it) {
+        const bool l5a = it % 2 == 1;
+        const int tbl = l5a ? 8 : 32, Lc = l5a ? lc5 : lc;
+        const double fcode = l5a ? fc5 : fc;
+        // every other search on a new context: its scratch is then exactly what the call asked for, and ASan sees a carve-up
+        // that reaches past it (a reused, larger scratch would hide it)
+        if (actx != ctx) EXPECT(gat_destroy(actx) == GAT_OK, "destroy");
+        actx = it % 4 < 2 ? ctx : nullptr;
+        if (!actx) EXPECT(gat_create(0, GAT_OWN_STREAM, &actx) == GAT_OK, "context for one search");
+        EXPECT((l5a ? gat_set_codes(actx, codes5.data(), lc5, 8) : gat_set_codes(actx, codes.data(), lc, 32)) == GAT_OK, "rebind codes");
+        const int fmt = (int)uni(0, 3);
+        const int M = (int)pick<long long>({1, 1, 2, 3, 4, 7});
+        const int B = (int)pick<long long>({1, 1, 2, 3, 5, 9, 40});
+        const long long N = pick<int>({0, 1, 2}) == 0 ? uni(1, 300) : uni(1, 12000);
+        long long bs = pick<int>({0, 1, 2}) == 0 ? N : pick<int>({0, 1}) ? N + uni(1, 64) : std::max(1ll, N - uni(1, N));
+        if (B == 1 && uni(0, 1)) bs = 0;
+        const long long as = (B - 1) * bs + N + uni(0, 33);
+        const long long extent = (M - 1) * as + (B - 1) * bs + N; // samples the signal spans
+        const size_t sbytes = fmt == GAT_LAYOUT_PLANAR ? 4 : fmt == GAT_LAYOUT_INTERLEAVED ? 8 : fmt == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 2;
+        std::vector<unsigned char> sre((size_t)extent * sbytes), sim(fmt == GAT_LAYOUT_PLANAR ? (size_t)extent * sbytes : 0);
+        gat_signal_desc sig = {sre.data(), fmt == GAT_LAYOUT_PLANAR ? (void *)sim.data() : nullptr, fmt, M, N, M > 1 ? as : uni(0, 1) * as, bs, 0};
+        const double fs = pick<double>({1.5e6, 2.046e6, 4e6, 5e6, 20e6, 20.46e6});
+        gat_acq_config cfg{};
+        cfg.struct_size = sizeof cfg;
+        cfg.num_doppler_bins = (int)pick<long long>({1, 2, 31, 32, 33, uni(1, 80)});
+        cfg.num_code_bins = (int)pick<long long>({1, 255, 256, 257, uni(1, 1200)});
+        cfg.code_step_samples = (int)uni(1, 31);
+        cfg.if_hz = pick<int>({0, 1}) ? 0.0 : unif(-0.25, 0.25) * fs;
+        cfg.code_freq_hz = fcode;
+        cfg.doppler_first_hz = unif(-1e4, 0.0);
+        cfg.doppler_step_hz = pick<double>({0.0, 250.0, -500.0, 33.3});
+        cfg.first_shift = pick<int>({0, 1, 2}) == 0 ? -uni(0, 3 * N) : uni(0, 100000);
+        cfg.min_peak_ratio = pick<double>({0.0, 2.0, 2.5});
+        cfg.code_length = pick<int>({0, 1}) ? 0 : Lc;
+        int P = (int)uni(1, 12);
+        std::vector<int32_t> prns((size_t)P);
+        for (auto &p : prns) p = (int32_t)uni(0, tbl - 1);
+        if (P > 1 && uni(0, 2) == 0) prns[P - 1] = prns[0];
+        int blocks = B;
+        const gat_signal_desc *sigp = &sig;
+        bool bad = true;
+        switch (uni(0, 34)) { // one way to be wrong, or none
+        case 0: cfg.struct_size = (uint32_t)uni(0, sizeof cfg - 1); break;
+        case 1: cfg.reserved = (int32_t)pick<long long>({-1, 1, 7}); break;
+        case 2: cfg.code_step_samples = (int)pick<long long>({0, -3, 32, 33, 40}); break;
+        case 3: (uni(0, 1) ? cfg.num_doppler_bins : cfg.num_code_bins) = (int)uni(-2, 0); break;
+        case 4: P = 0; break;
+        case 5: cfg.num_doppler_bins = 4096, cfg.num_code_bins = (int)uni(16385, 40000); break; // above 2^26 bins
+        case 6: *pick<double *>({&cfg.if_hz, &cfg.doppler_first_hz, &cfg.doppler_step_hz, &cfg.code_freq_hz, &cfg.min_peak_ratio}) = pick<double>({NAN, INFINITY, -INFINITY}); break;
+        case 7: prns[(size_t)uni(0, P - 1)] = (int32_t)pick<long long>({-1, tbl, tbl + 5, 1 << 20}); break;
+        case 8: if (M > 1) sig.ant_stride = uni(-5, 0); else sig.num_ants = (int)uni(-1, 0); break;
+        case 9: if (B > 1) sig.block_stride = uni(-5, 0); else blocks = (int)uni(-1, 0); break;
+        case 10: sig.chan_stride = pick<long long>({1, -1, as}); break;
+        case 11: cfg.first_shift = pick<long long>({1ll << 30, -(1ll << 30), 1ll << 40}); break;
+        case 12: cfg.code_length = pick<int>({Lc + 1, Lc == lc ? lc5 : lc, -1}); break;
+        case 13: sigp = nullptr; break;
+        case 14: sig.layout = (int)pick<long long>({-1, 4, 9}); break;
+        case 15: sig.im = fmt == GAT_LAYOUT_PLANAR ? nullptr : (void *)sre.data(); break;
+        case 16: sig.num_samples = uni(-3, 0); break;
+        case 17: cfg.doppler_step_hz = 1e15; break; // carrier beyond every bound
+        default: bad = false; break;
+        }
+        const double fs_call = bad && uni(0, 9) == 0 ? pick<double>({0.0, -1.0, NAN}) : fs;
+        if (fs_call != fs) bad = true;
+        std::vector<float> power;
+        const long long cells = (long long)std::max(P, 0) * std::max(cfg.num_doppler_bins, 0) * std::max(cfg.num_code_bins, 0);
+        const bool own = uni(0, 1) == 1 && cells > 0 && cells < (1ll << 24);
+        if (own) power.assign((size_t)cells, NAN);
+        std::vector<gat_acq_result> res((size_t)std::max(P, 1));
+        const int32_t rc = gat_acquire(actx, sigp, blocks, prns.data(), P, fs_call, &cfg, own ? power.data() : nullptr, res.data());
+        if (bad) {
+            EXPECT(rc == GAT_ERR_ARG || rc == GAT_ERR_RANGE || rc == GAT_ERR_STATE, "acquire: bad config (it %d) returned %d", it, rc);
+            ++acq_rejected;
+        } else {
+            EXPECT(rc == GAT_OK, "acquire: valid config (it %d: layout %d M %d B %d N %lld D %d J %d s %d P %d) returned %d: %s", it, fmt, M, B, N,
+                   cfg.num_doppler_bins, cfg.num_code_bins, cfg.code_step_samples, P, rc, gat_last_error(actx));
+            if (rc == GAT_OK) {
+                ++acq_launched;
+                for (int p = 0; p < P; ++p) EXPECT(res[(size_t)p].prn == prns[(size_t)p], "acquire: result %d for prn %d", p, prns[(size_t)p]);
+                if (own) EXPECT(std::all_of(power.begin(), power.end(), [](float v) { return v == 0.0f; }), "acquire: the caller's grid not (all) written");
+            }
+        }
+        // the host statistics on a grid with ties (a few integer levels): the peak is the first maximum
+        if (cells > 0 && cells < (1ll << 22)) {
+            std::vector<float> grid((size_t)cells);
+            const int levels = (int)uni(1, 6);
+            for (auto &v : grid) v = (float)uni(0, levels);
+            std::vector<gat_acq_result> hres((size_t)P);
+            const int32_t rs = gat_acq_stats_host(grid.data(), P, cfg.num_doppler_bins, cfg.num_code_bins, &cfg, fs_call, N, hres.data());
+            if (bad && rs != GAT_OK) {
+                EXPECT(rs == GAT_ERR_ARG || rs == GAT_ERR_RANGE, "stats: returned %d", rs);
+            } else if (rs == GAT_OK) {
+                ++acq_stats_ok;
+                const long long c1 = (long long)cfg.num_doppler_bins * cfg.num_code_bins;
+                for (int p = 0; p < P; ++p) {
+                    const float *g = grid.data() + (size_t)p * c1;
+                    const long long pk = std::max_element(g, g + c1) - g;
+                    const gat_acq_result &h = hres[(size_t)p];
+                    EXPECT(h.doppler_bin == pk / cfg.num_code_bins && h.code_bin == pk % cfg.num_code_bins && h.peak_power == (double)g[pk],
+                           "stats: peak (%d, %d) instead of the first maximum %lld", h.doppler_bin, h.code_bin, pk);
+                    EXPECT(h.num_noise_bins >= 0 && h.num_noise_bins < c1 && (h.detected == -1) == (h.num_noise_bins < 64) && h.detected >= -1 && h.detected <= 1,
+                           "stats: %lld noise bins, detected %d", (long long)h.num_noise_bins, h.detected);
+                }
+            } else {
+                EXPECT(cfg.code_length == 0 && rs == GAT_ERR_ARG, "stats: a valid config (code_length %d) returned %d", cfg.code_length, rs);
+            }
+        }
+    }
+    if (actx != ctx) EXPECT(gat_destroy(actx) == GAT_OK, "destroy");
+    {
+        int32_t many[1] = {0};
+        gat_acq_config cfg{};
+        cfg.struct_size = sizeof cfg;
+        cfg.num_doppler_bins = cfg.num_code_bins = cfg.code_step_samples = 1;
+        cfg.code_freq_hz = fc;
+        float g[1] = {1.0f};
+        gat_acq_result r{};
+        EXPECT(gat_acq_stats_host(nullptr, 1, 1, 1, &cfg, 4e6, 100, &r) == GAT_ERR_ARG && gat_acq_stats_host(g, 1, 1, 1, &cfg, 4e6, 0, &r) == GAT_ERR_ARG &&
+                   gat_acq_stats_host(g, 1, 1, 1, &cfg, 4e6, 100, nullptr) == GAT_ERR_ARG && gat_acq_stats_host(g, 1, 1, 1, nullptr, 4e6, 100, &r) == GAT_ERR_ARG,
+               "stats: null arguments");
+        std::vector<int32_t> lots(70000, 0); // more PRNs than grid z can carry
+        std::vector<gat_acq_result> rr(lots.size());
+        EXPECT(gat_set_codes(ctx, codes.data(), lc, 32) == GAT_OK, "rebind L1");
+        gat_signal_desc sig = {many, nullptr, GAT_LAYOUT_INTERLEAVED_I8, 1, 1, 0, 0, 0};
+        EXPECT(gat_acquire(ctx, &sig, 1, lots.data(), (int32_t)lots.size(), 4e6, &cfg, nullptr, rr.data()) == GAT_ERR_RANGE, "acquire: 70000 PRNs");
+        ++acq_rejected;
+    }
+    const long acq_split = hostsim::counters.acq_split_launches.load() - acq_split0;
+    std::printf("acquisition sweep: %ld calls launched, %ld rejected, %ld with G > 1 (%ld host statistics)\n", acq_launched, acq_rejected, acq_split, acq_stats_ok);
+    EXPECT(acq_launched > calls / 16 && acq_rejected > calls / 64 && acq_split > calls / 64, "the acquisition sweep launched, rejected and split");
 
     // ---- 2. closed loop, stand-alone operators, groups ---------------------------------------------------------------------
     {

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle
+from tests.helpers import acq_power_oracle, acq_sample_bins, check_power_close
 
 pytestmark = pytest.mark.gpu
 
@@ -88,17 +89,13 @@ def test_power_grid_matches_oracle(g, case):
     cfg = _cfg(g, D, J, s, first_shift, f_first, f_step, if_hz)
     rc, power, _ = _acquire_raw(g, sig, N, B, bstride, prns, fs, cfg)
     assert rc == 0
-    jsel = np.unique(np.concatenate([rng.choice(J, 40, replace=False), [0, J - 1]])).astype(np.int64)
-    shifts = (first_shift + s * jsel).astype(np.int32)
-    tau = np.fmod(FC / fs * (np.arange(B, dtype=np.int64) * bstride).astype(np.float64), float(LC))
+    rand = rng.choice(J, 40, replace=False)
+    rows = np.arange(D)
     for pi, p in enumerate(prns):
-        f = if_hz + (f_first + np.arange(D) * f_step)
-        prm = oracle.make_params(np.full((B, D), p), FC, np.broadcast_to(f, (B, D)), np.broadcast_to(tau[:, None], (B, D)), 0.0)
-        R = oracle.correlate_f64(re, im, codes, prm, fs, shifts, N=N, blk_stride=bstride)  # [B, D, L, M]
-        ref = (np.abs(R) ** 2).sum(axis=(0, 3))  # [D, L]
-        got = power[pi][:, jsel].astype(np.float64)
-        err = np.abs(got - ref).max(axis=1) / ref.max(axis=1)
-        assert err.max() <= 1e-5, (p, err.max())
+        peak = np.unravel_index(np.argmax(power[pi]), power[pi].shape)
+        _, jsel = acq_sample_bins(rng, D, J, n_cols=0, cols=[*rand, peak[1]])
+        ref = acq_power_oracle(re, im, codes, p, FC, LC, fs, if_hz, f_first, f_step, rows, first_shift, s, jsel, N, B, bstride)
+        check_power_close(power[pi][:, jsel], ref, what=f"prn {p}")
 
 
 def test_all_ones_signal_is_exact(g):

@@ -5,7 +5,8 @@ oracle/sanitize/sanitize_main.c (ragged sizes, negative taps at n = 0, ratio = 1
 chip edges, carrier phases that round to a whole cycle, GPS L5 lengths).  Any report aborts the run.
 
 `make -C tests/hostsim run` does the same for the REST of the library's host code -- csrc/gat_api.cpp (validation, launch
-planning, scratch management, graph cache, device groups) and csrc/gat_resident_api.cpp (the resident correlator's host side) -- by linking it against a
+planning, scratch management, graph cache, device groups) and csrc/gat_resident_api.cpp (the resident correlator's host side) and csrc/gat_acq_api.cpp (the acquisition search's validation,
+work split and scratch carve-up) -- by linking it against a
 host-only stand-in of the HIP runtime ("device" memory = host memory: every copy size is checked) and of the kernel
 launchers, which check each planned launch against what the kernel assumes about its arguments (LDS carve-up, replica
 room, grid decode, tap tables) and play the device's side of the resident correlator's doorbell protocol in a thread."""
@@ -39,3 +40,6 @@ def test_library_host_code_on_a_simulated_device_under_asan_ubsan():
     assert m and int(m.group(1)) > 2000 and int(m.group(2)) > 20 and int(m.group(3)) > 10 and int(m.group(4)) > 100 and int(m.group(5)) > 5, out[-2000:]
     m = re.search(r"resident correlator: (\d+) opened, (\d+) refused as unsupported \(\+ \d+ for want of room\), (\d+) calls answered; the emulated kernel was started (\d+) times", out)
     assert m and int(m.group(1)) > 10 and int(m.group(3)) > 500 and int(m.group(4)) > int(m.group(1)), out[-2000:]
+    # ... and through the acquisition search's host side (csrc/gat_acq_api.cpp): launches, rejections and split grids
+    m = re.search(r"acquisition sweep: (\d+) calls launched, (\d+) rejected, (\d+) with G > 1", out)
+    assert m and int(m.group(1)) > 150 and int(m.group(2)) > 150 and int(m.group(3)) > 50, out[-2000:]
