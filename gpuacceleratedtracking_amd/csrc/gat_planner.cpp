@@ -123,8 +123,15 @@ int32_t gat::correlate_impl(gat_ctx *c, const gat_signal_desc *sig, const gat_ch
         std::stable_sort(order, order + L, [&](int x, int y) { return shifts[x] < shifts[y]; });
         const long long span = (long long)shifts[order[L - 1]] - shifts[order[0]];
         const int CT = L <= kMfmaMaxTaps ? 16 / L : 0;
+        // Both matrix-core kernels fill a lane's replica entries from one floored modulo and at most one wrap of the table
+        // per 32 samples, and poison (NaN) a channel whose code rate breaks that: ratio * 32 >= Lc.  Tables of fewer than 64
+        // chips (where a rate below two chips per sample can break it), and host-side records that break it, take the vector
+        // kernel instead (a one-chip table under GAT_MC_F32 returned NaN for a valid call).
+        bool wraps_ok = c->Lc >= 64;
+        if (params_inline)
+            for (long long i = 0; i < (long long)B * K && wraps_ok; ++i) wraps_ok = params_inline[i].code_freq_hz / fs * 32.0 < (double)c->Lc;
         const bool shape_any = !plan_out && c->mc_mode != 0 && vec == 4 && N % spv == 0 /* whole load groups */ && M % 16 == 0 && sig->chan_stride == 0 && CT >= 1 &&
-                              span <= kMfmaMaxSpan && 2 * std::min(K, CT) * L >= 12 /* >= 3/8 of the columns */;
+                              span <= kMfmaMaxSpan && 2 * std::min(K, CT) * L >= 12 /* >= 3/8 of the columns */ && wraps_ok;
         const bool shape_ok = shape_any && planar; // the f32-MFMA kernel reads planar f32 only
         const int nct_total = shape_ok ? (K + CT - 1) / CT : 1;
         int nct = nct_total >= 4 ? 4 : (nct_total >= 2 ? 2 : 1);
@@ -349,8 +356,16 @@ int32_t gat::correlate_impl(gat_ctx *c, const gat_signal_desc *sig, const gat_ch
     const bool aw2_rule = fmt != GAT_LAYOUT_INTERLEAVED_I8 && !(fmt == GAT_LAYOUT_INTERLEAVED && max_taps > 5) && K >= 2 && sig->chan_stride == 0 &&
                           pairs_wgs >= 2ll * c->num_cus;
     const bool aw4_tile = (M / MT) % 4 == 0 && c->max_aw >= 4; // sixteen antennas on four waves (with up to four channels per workgroup)
+    // LDS: two workgroups per CU at least (80 KB each); a chip table that does not even fit alone is an error
+    // chip tables in LDS: int8 rows, or -- long codes (GPS L5: 10 KB per PRN) whose chips are all +-1 -- sign-bit rows (1.3 KB):
+    // room for long replica segments and for a second channel's table (option dc_bits: 0 never, 1 long codes, 2 always)
+    bool bit_tables = c->d_code_bits && c->code_bits_stride > 0 && (c->bit_tables == 2 || (c->bit_tables == 1 && c->code_row_stride > 2048));
+    int tab_bytes = bit_tables ? c->code_bits_stride * 4 : c->code_row_stride;
+    // (the 2 x 2 tile only where its two channels' tables fit: a long int8 table -- chips not all +-1, 20 000 and more --
+    // would leave it one channel, and there is no instance of that)
     const bool aw2 = (c->aw2 == 1 || (c->aw2 < 0 && aw2_rule)) && !plan_out && vec == 4 && MT == 4 && !aw4_tile && c->max_kt >= 2 &&
-                     c->max_aw >= 2 && K >= 2 && sig->chan_stride == 0 && dc_has_instance(2, max_taps, 4, 2, 2);
+                     c->max_aw >= 2 && K >= 2 && sig->chan_stride == 0 && dc_has_instance(2, max_taps, 4, 2, 2) &&
+                     dc_lds_bytes(2, 2, tab_bytes, dc_chunk(vec, fmt, 2)) <= 80 * 1024;
     if (aw2) MT = 2;
     const int AT = M / MT;
     int aw = 1, kt = 1;
@@ -363,11 +378,6 @@ int32_t gat::correlate_impl(gat_ctx *c, const gat_signal_desc *sig, const gat_ch
     if (plan_out) aw = 1, kt = 1;
     while (kt > 1 && !dc_has_instance(MT, max_taps, vec, aw, kt)) kt >>= 1;
     while (aw > 1 && !dc_has_instance(MT, max_taps, vec, aw, kt)) aw >>= 1;
-    // LDS: two workgroups per CU at least (80 KB each); a chip table that does not even fit alone is an error
-    // chip tables in LDS: int8 rows, or -- long codes (GPS L5: 10 KB per PRN) whose chips are all +-1 -- sign-bit rows (1.3 KB):
-    // room for long replica segments and for a second channel's table (option dc_bits: 0 never, 1 long codes, 2 always)
-    bool bit_tables = c->d_code_bits && c->code_bits_stride > 0 && (c->bit_tables == 2 || (c->bit_tables == 1 && c->code_row_stride > 2048));
-    int tab_bytes = bit_tables ? c->code_bits_stride * 4 : c->code_row_stride;
     auto lds_of = [&](int kt_, int aw_) { return dc_lds_bytes(kt_, MT, tab_bytes, dc_chunk(vec, fmt, aw_)); };
     while (kt > 1 && lds_of(kt, aw) > 80 * 1024) kt >>= 1;
     if (lds_of(kt, aw) > 160 * 1024)

@@ -122,7 +122,12 @@ GAT_API int32_t gat_device_info(gat_ctx *ctx, char *name_buf, size_t name_len,
 
 /* ---- code tables --------------------------------------------------------------------------
  * Replaces `system.codes` (GNSSSignals.jl; src/benchmarks.jl:93, src/algorithms.jl:185):
- * int8 +-1 chips, column-major [code_length x num_prns], copied to the device once. */
+ * int8 chips, column-major [code_length x num_prns], copied to the device once.  Any int8 value is
+ * accepted (a chip multiplies the sample as it is), 1 to 120000 chips per row (more: GAT_ERR_RANGE),
+ * any number of rows.  Tables whose chips are all +-1 also get sign-bit rows: the vector kernel
+ * stages those for rows of 2048 chips and more, and the split-bf16 matrix kernel needs them.  Any
+ * other table is staged as int8 rows and runs on the vector kernel or, on request (GAT_MC_F32),
+ * the f32 matrix kernel -- never on the split-bf16 kernel. */
 GAT_API int32_t gat_set_codes(gat_ctx *ctx, const int8_t *codes_host, int32_t code_length,
                               int32_t num_prns);
 

@@ -1,6 +1,7 @@
 """Shared helpers for the parity tests: build seeded inputs, run the HIP path through the C ABI
 (via the Python host layer) and the FP64 oracle on the same inputs, compare."""
 import numpy as np
+import pytest
 
 import oracle
 
@@ -15,17 +16,67 @@ def system_tables(name):
     return oracle.codes(name, 32), fc, lc
 
 
-def make_case(seed, system="GPSL1", N=2500, M=1, L=3, K=1, B=1, fs=None, if_hz=0.0, noise=0.0):
-    """Seeded scenario: K channels (distinct PRNs) summed into one antenna signal with
-    per-antenna steering phases; per-(block, channel) Doppler / code phase / carrier phase."""
+# ---- caller's code tables (gat_set_codes: any int8 chips, 1 .. 120 000 per row) -----------------------------------------
+CHIP_KINDS = ("pm1", "pm1_zeros", "ternary", "int8")
+
+
+def code_table(length, num_prns, seed, kind="pm1"):
+    """A caller's chip table, int8 [num_prns, length] (the layout GNSSSystem(codes=...) takes).  kind: "pm1" random +-1;
+    "pm1_zeros" +-1 with about 5 % of the chips 0 (the last row's last chip always, where the table has two chips or
+    more); "ternary" {-1, 0, +1}; "int8" the whole range, -128 (first chip) and 127 (last chip) included.  A row of zeros only gets
+    a +1 as its first chip."""
     rng = np.random.default_rng(seed)
-    codes, fc, lc = system_tables(system)
+    shape = (num_prns, length)
+    if kind in ("pm1", "pm1_zeros"):
+        t = np.where(rng.integers(0, 2, shape) == 1, 1, -1)
+        if kind == "pm1_zeros":
+            t[rng.random(shape) < 0.05] = 0
+            if t.size > 1:
+                t[-1, -1] = 0
+    elif kind == "ternary":
+        t = rng.integers(-1, 2, shape)
+    elif kind == "int8":
+        t = rng.integers(-128, 128, shape)
+        t.flat[0], t.flat[-1] = -128, 127
+    else:
+        raise ValueError(kind)
+    t[~t.any(axis=1), 0] = 1  # no row of zeros only (a channel without any signal has no relative error to judge)
+    return np.ascontiguousarray(t, dtype=np.int8)
+
+
+@pytest.fixture()
+def standard_codes_after():
+    """Tests share the default context, and the C-level users (resident correlator, acquisition) bind whatever table they
+    are handed: bind the standard GPS L1 table again after the test, so that no caller's table leaks into later tests."""
+    yield
+    import gpuacceleratedtracking_amd as g
+    g.get_context().set_codes(g.GPSL1().codes)
+
+
+def make_case(seed, system="GPSL1", N=2500, M=1, L=3, K=1, B=1, fs=None, if_hz=0.0, noise=0.0, codes=None, fc=None,
+              prns=None, tau=None):
+    """Seeded scenario: K channels (distinct PRNs) summed into one antenna signal with
+    per-antenna steering phases; per-(block, channel) Doppler / code phase / carrier phase.
+    ``codes`` (int8 [P, Lc]) / ``fc``: a caller's table and code rate instead of the system's (default 1.023 MHz); ``prns``
+    (K rows of it) and ``tau`` ([B, K] code phases) replace the drawn ones."""
+    rng = np.random.default_rng(seed)
+    if codes is None:
+        codes, fc, lc = system_tables(system)
+        num_prns = 32
+    else:
+        codes = np.ascontiguousarray(codes, dtype=np.int8)
+        num_prns, lc = codes.shape
+        fc = 1.023e6 if fc is None else fc
     if fs is None:
         fs = N / 1e-3
-    prns = rng.permutation(32)[:K]  # every row of both tables is pinned to its ICD (tests/test_oracle_golden.py)
+    # (every row of both ICD tables is pinned to its ICD, tests/test_oracle_golden.py; a caller's table of fewer rows than
+    # channels repeats them)
+    drawn = rng.permutation(num_prns)[:K] if K <= num_prns else rng.integers(0, num_prns, K)
+    prns = drawn if prns is None else np.asarray(prns)
     f = if_hz + rng.uniform(-5e3, 5e3, size=(B, K))
     fcode = fc * (1.0 + (f - if_hz) / 1575.42e6)
-    tau = rng.uniform(0, lc, size=(B, K))
+    drawn_tau = rng.uniform(0, lc, size=(B, K))
+    tau = drawn_tau if tau is None else np.broadcast_to(np.asarray(tau, dtype=np.float64), (B, K))
     phi = rng.uniform(0, 1, size=(B, K))
     prm = oracle.make_params(np.broadcast_to(prns, (B, K)), fcode, f, tau, phi)
     # signal: sum over channels, built with the oracle's gen_signal (phi in radians there)

@@ -1,10 +1,11 @@
 // main.cpp -- drives libgat's C ABI (the real gat_api.cpp + gat_codes.cpp + gat_version.cpp) on the host-only stand-ins of
 // this directory, under AddressSanitizer + UndefinedBehaviorSanitizer:
-//   1. thousands of random correlate calls (formats, alignments, ragged lengths, strides, tap lists, flags, options) -- every
+//   1. thousands of random correlate calls on L1 / L5 and random caller's tables (formats, alignments, ragged lengths, strides, tap lists, flags, options) -- every
 //      launch the planner emits is checked against the kernel's contract by fake_kernels.cpp; error paths must return
 //      GAT_ERR_* codes, never crash;
 //   2. the closed loop (eager and graph replay with its LRU), device groups (shard, replicate, correlate, gather), the
 //      stand-alone operators, timers, scratch reallocation;
+//   1a. a fixed grid of caller's code tables (1 .. 120 000 chips, +-1 or not) under the default options: every valid call launches;
 //   1b. random acquisition searches (gat_acq_api.cpp): valid and invalid configs, L1 / L5 tables, caller's grid or none --
 //      every launch is checked by fake_kernels.cpp, which touches every byte the kernels would; the host statistics on grids with ties;
 //   3. the resident correlator's host side against a host thread that plays the device: rings at random distances around
@@ -21,6 +22,7 @@
 #include <vector>
 
 #include "gat.h"
+#include "gat_ctx.h"
 #include "gat_internal.h"
 #include "hostsim.h"
 
@@ -42,6 +44,27 @@ template <class T> static T pick(std::initializer_list<T> l) { return *(l.begin(
 
 static const int kBytes[4] = {4, 8, 4, 2};   // bytes of one sample in one plane, by layout
 static const int kSpv[4] = {4, 2, 4, 8};     // samples of one 16-byte load
+
+// A caller's chip table (gat_set_codes takes any int8 chips, 1 .. 120 000 per row), [Lc x P] column-major.  kind 0: random
+// +-1; 1: +-1 with some chips 0; 2: {-1, 0, +1}; 3: the whole int8 range, -128 and 127 included.
+static std::vector<int8_t> chip_table(int Lc, int P, int kind)
+{
+    std::vector<int8_t> t((size_t)Lc * P);
+    for (auto &v : t) v = kind == 3 ? (int8_t)uni(-128, 127) : kind == 2 ? (int8_t)uni(-1, 1) : (int8_t)(uni(0, 1) ? 1 : -1);
+    if (kind == 1)
+        for (int i = 0; i < std::max(1, Lc / 50); ++i) t[(size_t)uni(0, (long long)t.size() - 1)] = 0;
+    return t;
+}
+static bool all_pm1(const std::vector<int8_t> &t) { return std::all_of(t.begin(), t.end(), [](int8_t v) { return v == 1 || v == -1; }); }
+// the one refusal a correlate call with valid records may meet: the code-span bound (gat_ctx.h), evaluated here
+static bool span_refused(const std::vector<gat_channel_params> &prm, double fs, long long N, const std::vector<int32_t> &sh, int Lc)
+{
+    long long ms = 0;
+    for (int32_t s : sh) ms = std::max<long long>(ms, std::llabs((long long)s));
+    for (const auto &p : prm)
+        if (!gat::code_span_ok(p.code_freq_hz / fs, p.code_phase_chips, (double)(N + ms), Lc)) return true;
+    return false;
+}
 
 int main(int argc, char **argv)
 {
@@ -74,15 +97,30 @@ int main(int argc, char **argv)
     // ---- 1. random correlate calls ---------------------------------------------------------------------------------------
     const char *opts[] = {"sync_flag_wgs", "max_ant_tile", "dc_aw", "dc_kt", "dc_bpw", "dc_bpw_force", "dc_wgs_per_cu", "dc_one_wave",
                           "dc_one_wave_min", "dc_ow_seg", "dc_depth", "dc_keep_l2", "dc_align", "dc_aw2", "dc_seg", "dc_bits", "dc_quads", "mc_i16_terms"};
-    const long long opt_lo[] = {0, 1, 1, 1, 1, 0, 0, 0, -1, 1, 1, -1, 0, 0, 0, 0, -1, 2}, opt_hi[] = {2048, 4, 4, 4, 64, 8, 16, 1, 64, 8, 2, 1, 1, 1, 8, 2, 1, 3};
+    const long long opt_lo[] = {0, 1, 1, 1, 1, 0, 0, 0, -1, 1, 1, -1, 0, -1, 0, 0, -1, 2}, opt_hi[] = {2048, 4, 4, 4, 64, 8, 16, 1, 64, 8, 2, 1, 1, 1, 8, 2, 1, 3};
     EXPECT(gat_set_option(ctx, "no_such_option", 1) == GAT_ERR_ARG && gat_set_option(ctx, "dc_depth", 7) == GAT_ERR_RANGE, "option errors");
     EXPECT(gat_set_matrix_core(ctx, 7) != GAT_OK, "kernel selection: bad mode");
     long ok_calls = 0, rejected = 0;
-    bool l5 = false;
+    long tables_bound = 0, long_int8_calls = 0, valid_refused = 0; // (caller's tables: bound, calls on long ones not +-1, valid calls refused)
+    int tbl_which = 0, tbl_P = 32, tbl_Lc = lc; // 0 L1, 1 L5, 2 a caller's table
+    double tbl_fc = fc;
+    bool tbl_int8 = false;
+    std::vector<int8_t> caller;
     for (int it = 0; it < calls; ++it) {
-        if (it % 97 == 0) { // a dual-frequency receiver alternates tables on one context
-            l5 = !l5;
-            EXPECT((l5 ? gat_set_codes(ctx, codes5.data(), lc5, 8) : gat_set_codes(ctx, codes.data(), lc, 32)) == GAT_OK, "rebind codes");
+        if (it % 47 == 0) { // a dual-frequency receiver alternates tables on one context -- and now and then a caller's own
+            tbl_which = (tbl_which + 1) % 3;
+            if (tbl_which == 2) {
+                const int len = (int)pick<long long>({uni(1, 40), uni(1, 2100), uni(2000, 20000), uni(20000, 120000), 120000, 1023, 10230});
+                const int kind = (int)uni(0, 3);
+                tbl_P = (int)uni(1, 64);
+                caller = chip_table(len, tbl_P, kind);
+                tbl_Lc = len, tbl_fc = pick<double>({1.023e6, 10.23e6, 0.5e6}), tbl_int8 = !all_pm1(caller);
+                EXPECT(gat_set_codes(ctx, caller.data(), len, tbl_P) == GAT_OK, "bind a caller's table (%d chips, kind %d, %d PRNs)", len, kind, tbl_P);
+                ++tables_bound;
+            } else {
+                tbl_P = tbl_which ? 8 : 32, tbl_Lc = tbl_which ? lc5 : lc, tbl_fc = tbl_which ? fc5 : fc, tbl_int8 = false;
+                EXPECT((tbl_which ? gat_set_codes(ctx, codes5.data(), lc5, 8) : gat_set_codes(ctx, codes.data(), lc, 32)) == GAT_OK, "rebind codes");
+            }
         }
         if (it % 13 == 0) EXPECT(gat_set_matrix_core(ctx, (int32_t)uni(0, 3)) == GAT_OK, "kernel selection");
         if (it % 11 == 0) {
@@ -106,9 +144,9 @@ int main(int argc, char **argv)
         for (int l = 0; l < L; ++l) sh[l] = (int32_t)uni(-spread, spread);
         if (uni(0, 1)) std::sort(sh.begin(), sh.end());
         const double fs = N / 1e-3;
-        const int P = l5 ? 8 : 32, Lc = l5 ? lc5 : lc;
+        const int P = tbl_P, Lc = tbl_Lc;
         std::vector<gat_channel_params> prm((size_t)B * K);
-        for (auto &p : prm) p = {(int32_t)uni(0, P - 1), 0, (l5 ? fc5 : fc) * (1 + unif(-1e-5, 1e-5)), unif(-5e3, 5e3), unif(0, Lc), unif(0, 1)};
+        for (auto &p : prm) p = {(int32_t)uni(0, P - 1), 0, tbl_fc * (1 + unif(-1e-5, 1e-5)), unif(-5e3, 5e3), unif(0, Lc), unif(0, 1)};
         const int bad = (int)uni(0, 40); // now and then something the validation must catch
         if (bad == 0) prm[0].prn = P + 3;
         if (bad == 1) prm.back().code_phase_chips = NAN;
@@ -121,14 +159,22 @@ int main(int argc, char **argv)
         int32_t rc;
         if (uni(0, 1)) {
             rc = gat_downconvert_and_correlate(ctx, &sig, prm.data(), B, K, L, sh.data(), fs, (float *)o_re, (float *)o_im, flags);
-            EXPECT(rc == GAT_OK || rc == GAT_ERR_RANGE || rc == GAT_ERR_ARG || rc == GAT_ERR_UNSUPPORTED, "host-parameter call: %d (%s)", rc, gat_last_error(ctx));
+            EXPECT(rc == GAT_OK || rc == GAT_ERR_RANGE || rc == GAT_ERR_ARG, "host-parameter call: %d (%s)", rc, gat_last_error(ctx));
             EXPECT(bad > 2 || rc != GAT_OK, "a bad record passed the validation (case %d)", bad);
         } else {
             gat_malloc(ctx, prm.size() * sizeof(gat_channel_params), &prm_dev);
             gat_memcpy_h2d(ctx, prm_dev, prm.data(), prm.size() * sizeof(gat_channel_params));
             rc = gat_downconvert_and_correlate_dev(ctx, &sig, (gat_channel_params *)prm_dev, B, K, L, sh.data(), fs, (float *)o_re, (float *)o_im,
                                                    flags | (uni(0, 3) == 0 && !flags ? GAT_FLAG_GRAPH : 0u));
-            EXPECT(rc == GAT_OK || rc == GAT_ERR_RANGE || rc == GAT_ERR_ARG || rc == GAT_ERR_UNSUPPORTED, "device-parameter call: %d (%s)", rc, gat_last_error(ctx));
+            EXPECT(rc == GAT_OK || rc == GAT_ERR_RANGE || rc == GAT_ERR_ARG, "device-parameter call: %d (%s)", rc, gat_last_error(ctx));
+        }
+        // a valid call launches -- or meets the code-span bound; the planner refuses nothing (whatever the table and options)
+        if (bad > 2) {
+            const bool ok = rc == GAT_OK || (rc == GAT_ERR_RANGE && span_refused(prm, fs, N, sh, Lc));
+            EXPECT(ok, "valid call refused: %d (%s): table %d (%d chips, %d PRNs%s), layout %d M %d K %d L %d B %lld N %lld", rc, gat_last_error(ctx), tbl_which, Lc, P,
+                   tbl_int8 ? ", int8" : "", fmt, M, K, L, (long long)B, N);
+            valid_refused += !ok;
+            long_int8_calls += tbl_int8 && Lc >= 20000;
         }
         if (rc == GAT_OK) {
             ++ok_calls;
@@ -150,8 +196,59 @@ int main(int argc, char **argv)
     EXPECT(ok_calls > calls / 2 && hostsim::counters.tail_launches > 0 && hostsim::counters.finalize_launches > 0 && (calls < 500 || hostsim::counters.mfma_launches > 0),
            "the sweep covers second stages, tails and the matrix-core kernels");
     EXPECT(gat_set_matrix_core(ctx, 1) == GAT_OK, "kernel selection back to auto");
-    for (int o = 0; o < 18; ++o) gat_set_option(ctx, opts[o], o == 17 ? 2 : o == 0 ? 1024 : o == 1 ? 4 : o == 2 ? 4 : o == 3 ? 4 : o == 4 ? 16 : o == 5 ? 0 : o == 6 ? 0 : o == 7 ? 1 : o == 8 ? -1 : o == 9 ? 4 : o == 10 ? 2 : o == 11 ? -1 : o == 12 ? 1 : o == 15 ? 1 : o == 16 ? -1 : 0);
+    for (int o = 0; o < 18; ++o) gat_set_option(ctx, opts[o], o == 17 ? 2 : o == 0 ? 1024 : o == 1 ? 4 : o == 2 ? 4 : o == 3 ? 4 : o == 4 ? 16 : o == 5 ? 0 : o == 6 ? 0 : o == 7 ? 1 : o == 8 ? -1 : o == 9 ? 4 : o == 10 ? 2 : o == 11 ? -1 : o == 12 ? 1 : o == 13 ? -1 : o == 15 ? 1 : o == 16 ? -1 : 0);
     EXPECT(gat_set_codes(ctx, codes.data(), lc, 32) == GAT_OK, "rebind L1");
+
+    // ---- 1a. a fixed grid of caller's tables under the default options ----------------------------------------------------
+    // Table lengths from one chip to the 120 000-chip limit, +-1 (sign-bit rows where long) and +-1 with one chip 0 (int8 rows
+    // whatever the length: LDS budget, the 2 x 2 tile's fit), by taps, channels, antennas, blocks and layouts.  Every call is
+    // valid: it must launch, or meet the code-span bound.
+    {
+        gat_ctx *tctx = nullptr; // a new context: the library's default options
+        EXPECT(gat_create(0, GAT_OWN_STREAM, &tctx) == GAT_OK, "context for the table grid");
+        const int lens[] = {1, 7, 16, 33, 511, 2046, 2048, 4092, 5115, 10230, 20000, 30000, 65536, 100000, 120000};
+        const int Ls[] = {1, 3, 7}, Ks[] = {1, 2, 3, 4, 8}, Ms[] = {1, 2, 4, 8, 16, 32}, Bs[] = {1, 16, 256};
+        const int P = 4;
+        const long long N = 20000;
+        const double fs = 20e6;
+        void *o_re = nullptr, *o_im = nullptr;
+        const size_t outs = (size_t)256 * 8 * 7 * 32;
+        gat_malloc(tctx, outs * sizeof(float), &o_re);
+        gat_malloc(tctx, outs * sizeof(float), &o_im);
+        long grid_calls = 0, grid_refused = 0;
+        for (int len : lens)
+            for (int zero = 0; zero < 2; ++zero) {
+                std::vector<int8_t> t = chip_table(len, P, 0);
+                if (zero) t[(size_t)uni(0, (long long)t.size() - 1)] = 0;
+                EXPECT(gat_set_codes(tctx, t.data(), len, P) == GAT_OK, "bind %d chips", len);
+                ++tables_bound;
+                for (int L : Ls)
+                    for (int K : Ks)
+                        for (int M : Ms)
+                            for (int B : Bs)
+                                for (int fmt = 0; fmt < 4; ++fmt) {
+                                    std::vector<int32_t> sh(L);
+                                    for (int l = 0; l < L; ++l) sh[l] = l - L / 2;
+                                    gat_signal_desc sig = {(void *)(uintptr_t)0x10000000, fmt == 0 ? (void *)(uintptr_t)0x50000000 : nullptr, fmt, M, N, N * B, N, 0};
+                                    std::vector<gat_channel_params> prm((size_t)B * K);
+                                    for (size_t i = 0; i < prm.size(); ++i)
+                                        prm[i] = {(int32_t)(i % P), 0, 1.023e6 * (1 + unif(-1e-5, 1e-5)), unif(-5e3, 5e3), unif(0, len), unif(0, 1)};
+                                    const int32_t rc = gat_downconvert_and_correlate(tctx, &sig, prm.data(), B, K, L, sh.data(), fs, (float *)o_re, (float *)o_im, 0);
+                                    const bool ok = rc == GAT_OK || (rc == GAT_ERR_RANGE && span_refused(prm, fs, N, sh, len));
+                                    EXPECT(ok, "table grid: %d (%s): %d chips%s, layout %d M %d K %d L %d B %d", rc, gat_last_error(tctx), len, zero ? " (one chip 0)" : "", fmt, M, K, L, B);
+                                    ++grid_calls;
+                                    grid_refused += !ok;
+                                    long_int8_calls += zero && len >= 20000;
+                                    EXPECT(gat_sync(tctx) == GAT_OK, "sync");
+                                }
+            }
+        gat_free(tctx, o_re);
+        gat_free(tctx, o_im);
+        EXPECT(gat_destroy(tctx) == GAT_OK, "destroy");
+        valid_refused += grid_refused;
+        std::printf("code tables: %ld tables bound, %ld grid calls, %ld calls on int8 tables of >= 20000 chips, %ld valid calls refused\n", tables_bound, grid_calls,
+                    long_int8_calls, valid_refused);
+    }
 
     // ---- 1b. random acquisition searches (gat_acquire, gat_acq_stats_host) ---------------------------------------------------
     {

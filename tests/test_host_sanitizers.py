@@ -40,6 +40,10 @@ def test_library_host_code_on_a_simulated_device_under_asan_ubsan():
     assert m and int(m.group(1)) > 2000 and int(m.group(2)) > 20 and int(m.group(3)) > 10 and int(m.group(4)) > 100 and int(m.group(5)) > 5, out[-2000:]
     m = re.search(r"resident correlator: (\d+) opened, (\d+) refused as unsupported \(\+ \d+ for want of room\), (\d+) calls answered; the emulated kernel was started (\d+) times", out)
     assert m and int(m.group(1)) > 10 and int(m.group(3)) > 500 and int(m.group(4)) > int(m.group(1)), out[-2000:]
+    # ... on caller's code tables of every length and chip kind: the fixed grid and the random sweep's tables, long int8 tables
+    # among them, and no valid call refused (the planner once chose a tile that no longer fitted: 280 refusals in this grid)
+    m = re.search(r"code tables: (\d+) tables bound, (\d+) grid calls, (\d+) calls on int8 tables of >= 20000 chips, (\d+) valid calls refused", out)
+    assert m and int(m.group(1)) >= 35 and int(m.group(2)) >= 32400 and int(m.group(3)) >= 5400 and int(m.group(4)) == 0, out[-2000:]
     # ... and through the acquisition search's host side (csrc/gat_acq_api.cpp): launches, rejections and split grids
     m = re.search(r"acquisition sweep: (\d+) calls launched, (\d+) rejected, (\d+) with G > 1", out)
     assert m and int(m.group(1)) > 150 and int(m.group(2)) > 150 and int(m.group(3)) > 50, out[-2000:]
