@@ -253,9 +253,9 @@
             // prn outside the table, or a code-phase span beyond the int32 / float-reciprocal modulo range
             // (the host entry point rejects these up front; device-resident parameters are checked here).
             const bool bad = P.prn < 0 || P.prn >= a.num_prns || code_span_bad(ratio, tau, (double)(N + a.max_abs_shift), Lc) ||
-                             !(step == step) || !(phi == phi) ||
-                             !(__builtin_fabs(step) < 1.0e15) || !(__builtin_fabs(phi) < 1.0e15);
+                             carrier_bad(step, phi);
             if (bad) ratio = 0.0, tau = 0.0, step = 0.0, phi = 0.0; // tame values; the output is poisoned below
+            carrier_reduce(step, phi);
             if (valid) valid_mask |= 1u << kk;
             if (valid && bad) bad_mask |= 1u << kk;
             prn_k[kk] = (P.prn < 0 || P.prn >= a.num_prns) ? 0 : P.prn;

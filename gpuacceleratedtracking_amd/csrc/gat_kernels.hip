@@ -106,12 +106,13 @@ __global__ void __launch_bounds__(kThreads) dc_tail_kernel(const DcTailArgs a)
         const long long b = bk / a.K;
         const gat_channel_params P = a.params ? a.params[bk] : a.inl[bk];
         const double ratio = P.code_freq_hz / a.fs, tau = P.code_phase_chips; // src/algorithms.jl:179
-        const double step = P.carrier_freq_hz / a.fs, phi = P.carrier_phase_cycles;
+        double step = P.carrier_freq_hz / a.fs, phi = P.carrier_phase_cycles;
         const int N = (int)a.N;
         // the same predicate as dc_kernel: such a channel's outputs are NaN already, nothing to add (and nothing indexed)
         const bool bad = P.prn < 0 || P.prn >= a.num_prns || code_span_bad(ratio, tau, (double)(N + a.max_abs_shift), a.Lc) ||
-                         !(step == step) || !(phi == phi) || !(__builtin_fabs(step) < 1.0e15) || !(__builtin_fabs(phi) < 1.0e15);
+                         carrier_bad(step, phi);
         if (!bad) {
+            carrier_reduce(step, phi);
             const int r = N - a.n_vec; // 1 .. 7
             const size_t base = (size_t)b * a.block_stride + (size_t)k * a.chan_stride + (size_t)m * a.ant_stride + a.n_vec;
             float dr[8], di[8];

@@ -500,9 +500,10 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
             ci.phi = P.carrier_phase_cycles;
             const double sp = __builtin_fabs(ci.tau) + __builtin_fabs(ci.ratio) * (double)(N + a.max_abs_shift) + 1.0;
             ci.bad = P.prn < 0 || P.prn >= a.num_prns || !(sp < 1073741824.0) || !(sp < 2097152.0 * (double)Lc) ||
-                     !(ci.ratio >= 0.0) || !(ci.ratio * 32.0 < (double)Lc) || !(ci.step == ci.step) || !(ci.phi == ci.phi);
+                     !(ci.ratio >= 0.0) || !(ci.ratio * 32.0 < (double)Lc) || carrier_bad(ci.step, ci.phi);
             ci.prn = (P.prn < 0 || P.prn >= a.num_prns) ? 0 : P.prn;
             if (ci.bad) { ci.ratio = 0.0; ci.tau = 0.0; ci.step = 0.0; ci.phi = 0.0; }
+            carrier_reduce(ci.step, ci.phi);
             const double st_O = ci.step * (double)OS;
             sincos_cycles(st_O - __builtin_rint(st_O), ci.wr, ci.wi);
             const double st_T = ci.step * (double)T;

@@ -56,6 +56,24 @@ __device__ __forceinline__ bool code_span_bad(double ratio, double tau, double r
     return !(span < 1073741824.0) || !(span < 2097152.0 * (double)Lc) || !(ratio >= 0.0);
 }
 
+// The carrier part of the same predicate: a carrier step f / fs or a carrier phase of 10^15 cycles or more, NaN or inf.
+// Every correlator kernel poisons such a device-resident record with it; the host entry points reject the same records
+// (validate_params).  (Below the bound carrier_reduce makes every record exact.)
+__device__ __forceinline__ bool carrier_bad(double step, double phi)
+{
+    return !(__builtin_fabs(step) < 1.0e15) || !(__builtin_fabs(phi) < 1.0e15);
+}
+
+// Exact reduction of a channel's carrier, once where its record is read: the phase to [0, 1] (phi - floor(phi)), the
+// step to [-1/2, 1/2] (step - rint(step)); both subtractions are exact.  n * rint(step) is a whole number of cycles, so
+// exp(j 2 pi (n step + phi)) is unchanged for every sample n, and the kernels' fma(n, step, phi) rounds values below N
+// instead of |phi| + N |step|: unreduced, phases of 10^11 - 10^12 cycles and more missed the 1e-5 contract.
+__device__ __forceinline__ void carrier_reduce(double &step, double &phi)
+{
+    phi -= __builtin_floor(phi);
+    step -= __builtin_rint(step);
+}
+
 // The reference's code phase of sample x = n + shift, src/algorithms.jl:179: one double multiply and one double
 // add, NOT fused (bit-identical to the CPU oracle).
 __device__ __forceinline__ double code_phase(double ratio, double tau, int x)

@@ -76,6 +76,13 @@ typedef struct gat_channel_params {
     double code_phase_chips;     /* start_code_phase at sample 0                             */
     double carrier_phase_cycles; /* carrier_phase at sample 0, in CYCLES (algorithms.jl:172) */
 } gat_channel_params;
+/* Accepted records (the correlate entry points and the resident correlator; host records outside this set return
+ * GAT_ERR_RANGE / GAT_ERR_ARG, device records outside it get NaN outputs): 0 <= prn < num_prns; code_freq_hz >= 0;
+ * |code_phase_chips| + code_freq_hz / fs * (num_samples + max|shift|) + 1 below both 2^30 and 2^21 * code_length;
+ * |carrier_freq_hz / fs| < 1e15 and |carrier_phase_cycles| < 1e15, any carrier within that, above Nyquist included.  Every
+ * value is finite.  The kernels reduce the carrier phase modulo 1 and the carrier step f / fs modulo 1 exactly, so results
+ * meet the 1e-5 contract over the whole carrier range.  The matrix-core kernels also need code_freq_hz / fs * 32 < code_length
+ * (see gat_set_matrix_core). */
 
 /* Device-resident antenna signal; replaces signal.re / signal.im (CuArray{Float32,2} or ,3)
  * handed to kernel_algorithm (src/algorithms.jl:887-888) -- element (n, m, b, k) lives at

@@ -176,3 +176,84 @@ def check_power_close(got, ref, rtol=RTOL, what=""):
         assert rel <= rtol, f"{what} row {r}: element-wise error {rel:.3e} > {rtol}"
         worst_n, worst_e = max(worst_n, e_inf), max(worst_e, rel)
     return worst_n, worst_e
+
+
+# ---- the channel record across its whole accepted domain (include/gat.h gat_channel_params) -------------------------------
+SPAN_LIMIT = 1073741824.0  # 2^30: |code phase| bound of the kernels' int32 / float-reciprocal chip index
+
+
+def span_bound_tau(ratio, reach, lc):
+    """(inside, outside): the largest code phase tau >= 0 that the span rule |tau| + ratio * reach + 1 < min(2^30, 2^21 Lc)
+    accepts, evaluated in the kernels' own double expression, and the next double above it (rejected)."""
+    limit = min(SPAN_LIMIT, 2097152.0 * lc)
+    ok = lambda t: abs(t) + abs(ratio) * reach + 1.0 < limit  # noqa: E731
+    t = np.float64(limit - abs(ratio) * reach - 1.0)
+    while not ok(t):
+        t = np.nextafter(t, 0.0)
+    while ok(np.nextafter(t, np.inf)):
+        t = np.nextafter(t, np.inf)
+    return float(t), float(np.nextafter(t, np.inf))
+
+
+def floormod_hard_taus(lc, lo, hi, seed, count=3):
+    """Integer code phases in [lo, hi) whose chip index floor(ip * (1/Lc)) the kernels' float-reciprocal modulo gets one
+    quotient wrong (gat_phase.h floormod_fast, float32 arithmetic): up to `count` whose first remainder is negative and up to
+    `count` whose first remainder is Lc + 1 or more (Lc itself reads the wrap chip, which hides a missing second correction).
+    Which of the two occur depends on the rounding of 1 / Lc and on the sign of the range."""
+    rng = np.random.default_rng(seed)
+    ip = rng.integers(lo, hi, 400000, dtype=np.int64)
+    inv = np.float32(1.0) / np.float32(lc)
+    q = np.floor(ip.astype(np.float32) * inv).astype(np.int64)
+    r = ip - q * lc
+    low, high = ip[r < 0][:count], ip[r >= lc + 1][:count]
+    return [float(x) for x in np.concatenate([low, high])]
+
+
+def reduced_carrier(step, phi):
+    """The carrier of a record reduced exactly: phase phi - floor(phi) in [0, 1], step s - rint(s) in [-1/2, 1/2].  Both
+    subtractions are exact in binary64 (for |phi| >= 1, |s| >= 1/2), and n * rint(s) is a whole number of cycles."""
+    step = np.asarray(step, dtype=np.float64)
+    phi = np.asarray(phi, dtype=np.float64)
+    return step - np.rint(step), phi - np.floor(phi)
+
+
+def correlate_reduced(re, im, codes, prm, fs, shifts, N, blk_stride=None):
+    """numpy reference of the correlator (as oracle.np_correlate) with the carrier phase n * s0 + phi0 built from the
+    exactly reduced step s0 and phase phi0 of every record (reduced_carrier): exact wherever |phi| or |f / fs| is large,
+    and the same as oracle.correlate_f64 where nothing needs reducing.  re / im float32 [M, ld] planar; prm: oracle records
+    [B, K] (field prn0).  Returns complex128 [B, K, L, M]."""
+    B, K = prm.shape
+    M = re.shape[0]
+    S = N if blk_stride is None else blk_stride
+    lc = codes.shape[1]
+    n = np.arange(N, dtype=np.float64)
+    out = np.empty((B, K, len(shifts), M), dtype=np.complex128)
+    for b in range(B):
+        x = re[:, b * S:b * S + N].astype(np.float64) + 1j * im[:, b * S:b * S + N].astype(np.float64)
+        for k in range(K):
+            p = prm[b, k]
+            s0, phi0 = reduced_carrier(p["carrier_freq_hz"] / fs, p["carrier_phase_cycles"])
+            dw = x * np.exp(-2j * np.pi * (n * s0 + phi0))[None, :]
+            ratio = np.float64(p["code_freq_hz"]) / np.float64(fs)
+            row = codes[p["prn0"]].astype(np.float64)
+            for li, s in enumerate(shifts):
+                idx = np.mod(np.floor(ratio * (n + float(s)) + p["code_phase_chips"]).astype(np.int64), lc)
+                out[b, k, li] = dw @ row[idx]
+    return out
+
+
+def channel_errors(got, ref):
+    """Per (block, channel) errors as check_close judges them: norm-wise max|dR| / max|R_ref| and element-wise on the taps
+    with |R_ref| >= 0.1 max|R_ref|.  Returns two float64 [B, K] arrays."""
+    got = np.asarray(got, dtype=np.complex128)
+    ref = np.asarray(ref, dtype=np.complex128)
+    B, K = ref.shape[:2]
+    e_n, e_e = np.zeros((B, K)), np.zeros((B, K))
+    for b in range(B):
+        for k in range(K):
+            r, d = ref[b, k], np.abs(got[b, k] - ref[b, k])
+            scale = np.abs(r).max()
+            e_n[b, k] = d.max() / scale
+            strong = np.abs(r) >= 0.1 * scale
+            e_e[b, k] = (d[strong] / np.abs(r)[strong]).max()
+    return e_n, e_e

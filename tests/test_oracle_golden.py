@@ -204,3 +204,26 @@ def test_sample_shifts():
     assert oracle.sample_shifts(3, 50e6, 1.023e6).tolist() == [-24, 0, 24]      # BASELINE C4
     assert oracle.sample_shifts(3, 1.0e6, 1.023e6).tolist() == [-1, 0, 1]       # max(1, .)
     assert oracle.sample_shifts(7, 20e6, 1.023e6).tolist() == [-30, -20, -10, 0, 10, 20, 30]
+
+
+def test_reduced_carrier_reference_matches_the_oracle_where_nothing_reduces():
+    """tests/helpers.py correlate_reduced (the channel-domain tests' reference) equals oracle.correlate_f64 on records whose
+    carrier needs no reduction, and is unchanged by phase + 2^10 and carrier + k fs."""
+    from tests.helpers import correlate_reduced, reduced_carrier
+    rng = np.random.default_rng(3)
+    codes = oracle.codes("GPSL1", 4)
+    N, fs = 3000, 3e6
+    re = rng.standard_normal((2, 2 * N)).astype(np.float32)
+    im = rng.standard_normal((2, 2 * N)).astype(np.float32)
+    prm = oracle.make_params(np.array([[0, 3], [1, 2]]), 1.023e6, rng.uniform(-0.49, 0.49, (2, 2)) * fs,
+                             rng.uniform(-2000, 2000, (2, 2)), rng.uniform(0, 1, (2, 2)))
+    shifts = np.array([-2, 0, 2], dtype=np.int32)
+    ref = oracle.correlate_f64(re, im, codes, prm, fs, shifts, N=N)
+    red = correlate_reduced(re, im, codes, prm, fs, shifts, N)
+    assert np.abs(red - ref).max() <= 1e-12 * np.abs(ref).max()
+    moved = prm.copy()
+    moved["carrier_phase_cycles"] += 1024.0
+    moved["carrier_freq_hz"] += np.array([[3.0, -2.0], [37.0, 1.0]]) * fs
+    assert np.abs(correlate_reduced(re, im, codes, moved, fs, shifts, N) - red).max() <= 1e-9 * np.abs(ref).max()
+    s0, phi0 = reduced_carrier(np.array([37.25, -2.75, 0.5]), np.array([1e14 + 0.375, -3e5 - 0.25, 0.0]))
+    assert list(s0) == [0.25, 0.25, 0.5] and list(phi0) == [0.375, 0.75, 0.0]
