@@ -257,3 +257,96 @@ def channel_errors(got, ref):
             strong = np.abs(r) >= 0.1 * scale
             e_e[b, k] = (d[strong] / np.abs(r)[strong]).max()
     return e_n, e_e
+
+
+# ---- the correlator's paths (shared by the domain tests: test_channel_domain_gpu.py, test_tap_domain_gpu.py) ------------------
+SENTINEL = 7.0  # what correlate() pre-fills the outputs with by default
+
+
+def reset(g, c):
+    c.set_matrix_core(g.GAT_MC_AUTO)
+    c.set_vector_tiling(4, 4, 16)
+    for name, val in (("dc_bits", 1), ("dc_quads", -1), ("dc_aw2", -1), ("dc_one_wave_min", -1), ("dc_depth", 2)):
+        c.set_option(name, val)
+
+
+# ---- the paths ---------------------------------------------------------------------------------------------------------------
+# mc: kernel selection; tiling / opts: forced vector-kernel settings; M, N: the call's antennas and block length (None: the
+# test's own); offset: samples the signal's base is moved by (1: unaligned -> the scalar-load path); ragged: N - 1 samples
+# (N mod 4 = 3 -> the tail kernel); want: what gat_last_launch_info must show.
+PATHS = {
+    "default-planar": dict(layout=0),
+    "default-cf32": dict(layout=1),
+    "default-i16": dict(layout=2),
+    "default-i8": dict(layout=3),
+    # (sixteen antennas: four antenna tiles, whose workgroups loop over channels -- 256 / KT replica entries per producer)
+    "tiling-1-1-1": dict(mc=0, tiling=(1, 1, 1), M=16, want=lambda i: i["channels_per_wg"] == 1 and i["blocks_per_wg"] == 1),
+    "tiling-2-2-4": dict(mc=0, tiling=(2, 2, 4), M=16, want=lambda i: i["channels_per_wg"] == 1),
+    "tiling-4-2-4": dict(mc=0, tiling=(4, 2, 4), M=16, want=lambda i: i["channels_per_wg"] == 2),
+    "tiling-4-4-16": dict(mc=0, tiling=(4, 4, 16), M=16, want=lambda i: i["channels_per_wg"] == 4),
+    "one-wave": dict(mc=0, opts=dict(dc_one_wave_min=1), M=2, N=1000, want=lambda i: i["threads"] == 64),
+    "2x2-quads": dict(mc=0, opts=dict(dc_aw2=1, dc_quads=1), want=lambda i: i["channels_per_wg"] == 2 and i["ant_tile"] == 4),
+    "2x2-no-quads": dict(mc=0, opts=dict(dc_aw2=1, dc_quads=0), want=lambda i: i["channels_per_wg"] == 2 and i["ant_tile"] == 4),
+    "scalar-load": dict(mc=0, offset=1, want=lambda i: i["vec"] != 4),
+    "ragged-tail": dict(mc=0, ragged=True, want=lambda i: i["vec"] == 4),
+    "split-finalize": dict(mc=0, B=1, N=16384, want=lambda i: i["splits"] > 1 and i["finalize_launched"] == 1),
+    "mc-f32": dict(mc=2, M=16, want=lambda i: i["matrix_core"] == 1),
+    "mc-bf16-f32": dict(mc=3, M=16, want=lambda i: i["matrix_core"] == 2),
+    "mc-bf16-i16": dict(mc=3, M=16, layout=2, want=lambda i: i["matrix_core"] == 2),
+    "mc-bf16-i8": dict(mc=3, M=16, layout=3, want=lambda i: i["matrix_core"] == 2),
+}
+
+
+def configure(g, ctx, path):
+    reset(g, ctx)
+    spec = PATHS[path]
+    ctx.set_matrix_core(spec.get("mc", g.GAT_MC_AUTO))
+    if "tiling" in spec:
+        ctx.set_vector_tiling(*spec["tiling"])
+    for name, val in spec.get("opts", {}).items():
+        ctx.set_option(name, val)
+
+
+def geometry(path, N, M, B):
+    spec = PATHS[path]
+    N = spec.get("N") or N
+    if spec.get("ragged"):
+        N -= 1
+    return N, spec.get("M", M), spec.get("B", B)
+
+
+def correlate(g, ctx, path, re, im, prm, N, fs, shifts, host=False, check_want=True, sentinel=SENTINEL, flags=0):
+    """One call of the correlator on `path`: re / im float32 [M, B * S] planar (S = block stride, a multiple of 8), prm library
+    records [B, K]; host: the records as host records (gat_downconvert_and_correlate) instead of device records; check_want:
+    assert the path's launch info; sentinel: what the outputs are pre-filled with; flags: GAT_FLAG_*.  Returns the outputs
+    complex128 [B, K, L, M] and the launch info."""
+    import torch
+    spec = PATHS[path]
+    layout, off = spec.get("layout", 0), spec.get("offset", 0)
+    B, K = prm.shape
+    M, ld = re.shape
+    S = ld // B
+    dev = ctx.device
+    if layout == 0:
+        bufs = [torch.zeros((M, ld + 8), dtype=torch.float32, device=dev) for _ in range(2)]
+        bufs[0][:, off:off + ld] = torch.from_numpy(re).to(dev)
+        bufs[1][:, off:off + ld] = torch.from_numpy(im).to(dev)
+        ptrs = (bufs[0].data_ptr() + 4 * off, bufs[1].data_ptr() + 4 * off)
+    else:
+        assert off == 0
+        dt = {1: torch.float32, 2: torch.int16, 3: torch.int8}[layout]
+        x = torch.stack([torch.from_numpy(re), torch.from_numpy(im)], dim=-1).to(dt).contiguous().to(dev)
+        bufs = [x]
+        ptrs = (x.data_ptr(), None)
+    desc = g._lib.SignalDesc(ptrs[0], ptrs[1], layout, M, N, bufs[0].shape[1], S, 0)
+    L = len(shifts)
+    o_re = torch.full((B, K, L, M), sentinel, dtype=torch.float32, device=dev)
+    o_im = torch.full((B, K, L, M), sentinel, dtype=torch.float32, device=dev)
+    params = prm if host else ctx.params_to_device(prm)
+    ctx.downconvert_and_correlate(desc, params, B, K, shifts, fs, o_re, o_im, flags)
+    ctx.sync()
+    got = o_re.cpu().numpy().astype(np.float64) + 1j * o_im.cpu().numpy().astype(np.float64)
+    info = ctx.last_launch_info()
+    if check_want and "want" in spec:
+        assert spec["want"](info), (path, info)
+    return got, info

@@ -108,6 +108,7 @@ hipError_t launch_dc(const DcArgs &a, const DcLaunch &cfg, hipStream_t)
 {
     ++counters.dc_launches;
     check_dc(a, cfg, false);
+    for (int l = 0; l < cfg.taps && l < kMaxTapsPerLaunch; ++l) hostsim::tap_cover.main.emplace_back(a.tap_index[l], a.shifts[l]);
     return hipSuccess;
 }
 hipError_t launch_finalize(const float *partial, float *out_re, float *out_im, int splits, int elems, long long groups, hipStream_t, unsigned *done, unsigned *flag, unsigned seq)
@@ -120,6 +121,7 @@ hipError_t launch_finalize(const float *partial, float *out_re, float *out_im, i
 hipError_t launch_dc_tail(const DcTailArgs &a, hipStream_t)
 {
     ++counters.tail_launches;
+    hostsim::tap_cover.tail.emplace_back(a.shifts, a.shifts + std::min(std::max(a.L, 0), (int)GAT_MAX_TAPS));
     REQUIRE(a.n_vec < a.N && a.N - a.n_vec < 8 && a.out_re && a.out_im, "tail: n_vec %d of %lld", a.n_vec, a.N);
     return hipSuccess;
 }
@@ -158,6 +160,7 @@ hipError_t launch_mfma(const MfArgs &a, int nct, unsigned grid, unsigned lds_byt
     REQUIRE(a.chan_groups == ((a.K + a.CT - 1) / a.CT + nct - 1) / nct, "f32 mfma: channel groups %d", a.chan_groups);
     REQUIRE(lds_bytes == mf_lds_bytes(nct, a.CT, a.rep_stride, a.code_row_stride, a.codes_in_lds) && lds_bytes <= 160 * 1024, "f32 mfma: LDS %u", lds_bytes);
     check_mf_common(a, grid, kMfTile, "f32 mfma");
+    for (int l = 0; l < a.L && l < kMfmaMaxTaps; ++l) hostsim::tap_cover.main.emplace_back(a.tap_index[l], a.shifts[l]);
     return hipSuccess;
 }
 hipError_t launch_mfma_bf16(const MfArgs &a, int rt, int nct, int fmt, unsigned grid, unsigned lds_bytes, hipStream_t)
@@ -182,6 +185,7 @@ hipError_t launch_mfma_bf16(const MfArgs &a, int rt, int nct, int fmt, unsigned 
     REQUIRE(a.mb_mode != kMbTwo || a.nslots * T / 4 <= mb_threads(rt, nct) - 64 * mb_consumer_waves(rt, nct), "bf16 mfma: two-term items");
     REQUIRE(lds_bytes == mb_lds_bytes(rt, nct, fmt, a.nslots, a.rep_stride, a.code_bits_stride, a.mb_mode) && lds_bytes <= 160 * 1024, "bf16 mfma: LDS %u", lds_bytes);
     check_mf_common(a, grid, T, "bf16 mfma");
+    for (int l = 0; l < a.L && l < kMfmaMaxTaps; ++l) hostsim::tap_cover.main.emplace_back(a.tap_index[l], a.shifts[l]);
     return hipSuccess;
 }
 

@@ -6,6 +6,8 @@
 //   2. the closed loop (eager and graph replay with its LRU), device groups (shard, replicate, correlate, gather), the
 //      stand-alone operators, timers, scratch reallocation;
 //   1a. a fixed grid of caller's code tables (1 .. 120 000 chips, +-1 or not) under the default options: every valid call launches;
+//   1c. a fixed grid of tap lists (the GPU tests' lists and permutations of them) by layout, antennas, channels and kernel
+//      selection: every valid call launches, with the launches the sorted taps' grouping asks for, covering every tap once;
 //   1b. random acquisition searches (gat_acq_api.cpp): valid and invalid configs, L1 / L5 tables, caller's grid or none --
 //      every launch is checked by fake_kernels.cpp, which touches every byte the kernels would; the host statistics on grids with ties;
 //   3. the resident correlator's host side against a host thread that plays the device: rings at random distances around
@@ -64,6 +66,93 @@ static bool span_refused(const std::vector<gat_channel_params> &prm, double fs, 
     for (const auto &p : prm)
         if (!gat::code_span_ok(p.code_freq_hz / fs, p.code_phase_chips, (double)(N + ms), Lc)) return true;
     return false;
+}
+
+// After a call: the launches of the correlator wrote every position of the caller's tap list exactly once, each with the
+// caller's shift at that position (tap_index), and a tail launch took the list in the caller's order.
+static bool taps_covered(const std::vector<int32_t> &sh, const char *what)
+{
+    const auto &cv = hostsim::tap_cover;
+    std::vector<int> seen(sh.size(), 0);
+    bool ok = !cv.main.empty();
+    for (const auto &is : cv.main) {
+        const bool in = is.first >= 0 && is.first < (int)sh.size() && sh[is.first] == is.second;
+        ok &= in;
+        if (in) ++seen[is.first];
+    }
+    for (int n : seen) ok &= n == 1;
+    for (const auto &t : cv.tail) ok &= t == std::vector<int>(sh.begin(), sh.end());
+    EXPECT(ok, "%s: %zu tap launches entries, %zu tails for %zu taps", what, cv.main.size(), cv.tail.size(), sh.size());
+    return ok;
+}
+
+// Sorted taps cut greedily into groups of <= kMaxTapsPerLaunch within kMaxLaunchSpan of the group's first tap: the vector
+// kernel's launches of one call.
+static long greedy_groups(std::vector<int32_t> sh)
+{
+    std::sort(sh.begin(), sh.end());
+    long n = 0;
+    for (size_t t0 = 0; t0 < sh.size(); ++n) {
+        size_t t1 = t0 + 1;
+        while (t1 < sh.size() && t1 - t0 < (size_t)gat::kMaxTapsPerLaunch && (long long)sh[t1] - sh[t0] <= gat::kMaxLaunchSpan) ++t1;
+        t0 = t1;
+    }
+    return n;
+}
+
+// The tap lists of tests/test_tap_domain_gpu.py for a block of N samples (one tap at 0, before and after the block; order and
+// duplicates; the count and span boundaries of a launch; the matrix kernels' limits; N + max|shift| = 2^30 - 1).
+static std::vector<std::vector<int32_t>> tap_lists(int N)
+{
+    std::vector<std::vector<int32_t>> T;
+    const int32_t far = (1 << 30) - 1 - N;
+    auto shuffled = [](std::vector<int32_t> v) { std::shuffle(v.begin(), v.end(), rng); return v; };
+    auto range = [](int lo, int hi, int step) { std::vector<int32_t> v; for (int x = lo; x < hi; ++x) v.push_back(x * step); return v; };
+    T.push_back({0});
+    T.push_back({-N - 5});
+    T.push_back({3 * N});
+    T.push_back({1, 0, -1});
+    {
+        std::vector<int32_t> v = range(-100, 101, 1);
+        v = shuffled(v);
+        v.resize(32);
+        T.push_back(v);
+        T.push_back(std::vector<int32_t>(32, 7));
+        std::vector<int32_t> p = shuffled(range(-60, 61, 1));
+        p.resize(16);
+        std::vector<int32_t> d = p;
+        for (int32_t x : shuffled(p)) d.push_back(x);
+        T.push_back(d);
+    }
+    T.push_back(range(-4, 4, 3));
+    T.push_back(shuffled(range(-4, 5, 3)));
+    T.push_back(shuffled(range(-8, 9, 1)));
+    {
+        std::vector<int32_t> v = range(-4, 5, 11);
+        v.push_back(5000);
+        T.push_back(shuffled(v));
+    }
+    auto spread = [&](int L, int s) {
+        std::vector<int32_t> d(L);
+        for (int l = 0; l < L; ++l) d[l] = (int32_t)std::lround(L > 1 ? (double)s * l / (L - 1) : 0.0);
+        const int32_t mid = d[L / 2];
+        for (auto &x : d) x -= mid;
+        return shuffled(d);
+    };
+    T.push_back(spread(8, 769));
+    T.push_back(shuffled({far, far - 1, far - 2, far - 7}));
+    T.push_back(shuffled({-far, -far + 3, -far + 1}));
+    T.push_back({-far, 0, far});
+    for (int s : {511, 512, 513, 2047, 2048, 2049}) {
+        const int b = -((s / 2) & ~1);
+        T.push_back(shuffled({b, b + 2, 0, b + ((s - 2) & ~1), b + s}));
+        T.push_back(shuffled({b, b + 1, b + 3, 0, b + s - 1, b + s}));
+    }
+    for (int L : {6, 7, 8, 11, 16})
+        for (int s : {0, 1, 767, 768}) T.push_back(spread(L, s));
+    const size_t n = T.size();
+    for (size_t i = 0; i < n; ++i) T.push_back(shuffled(T[i])); // and a random permutation of each
+    return T;
 }
 
 int main(int argc, char **argv)
@@ -158,14 +247,19 @@ int main(int argc, char **argv)
         gat_malloc(ctx, outs * sizeof(float), &o_im);
         int32_t rc;
         if (uni(0, 1)) {
+            hostsim::tap_cover.clear();
             rc = gat_downconvert_and_correlate(ctx, &sig, prm.data(), B, K, L, sh.data(), fs, (float *)o_re, (float *)o_im, flags);
+            if (rc == GAT_OK) taps_covered(sh, "random sweep, host records");
             EXPECT(rc == GAT_OK || rc == GAT_ERR_RANGE || rc == GAT_ERR_ARG, "host-parameter call: %d (%s)", rc, gat_last_error(ctx));
             EXPECT(bad > 2 || rc != GAT_OK, "a bad record passed the validation (case %d)", bad);
         } else {
             gat_malloc(ctx, prm.size() * sizeof(gat_channel_params), &prm_dev);
             gat_memcpy_h2d(ctx, prm_dev, prm.data(), prm.size() * sizeof(gat_channel_params));
+            const uint32_t graph = uni(0, 3) == 0 && !flags ? GAT_FLAG_GRAPH : 0u;
+            hostsim::tap_cover.clear();
             rc = gat_downconvert_and_correlate_dev(ctx, &sig, (gat_channel_params *)prm_dev, B, K, L, sh.data(), fs, (float *)o_re, (float *)o_im,
-                                                   flags | (uni(0, 3) == 0 && !flags ? GAT_FLAG_GRAPH : 0u));
+                                                   flags | graph);
+            if (rc == GAT_OK && !graph) taps_covered(sh, "random sweep, device records"); // (a replayed graph launches nothing here)
             EXPECT(rc == GAT_OK || rc == GAT_ERR_RANGE || rc == GAT_ERR_ARG, "device-parameter call: %d (%s)", rc, gat_last_error(ctx));
         }
         // a valid call launches -- or meets the code-span bound; the planner refuses nothing (whatever the table and options)
@@ -248,6 +342,58 @@ int main(int argc, char **argv)
         valid_refused += grid_refused;
         std::printf("code tables: %ld tables bound, %ld grid calls, %ld calls on int8 tables of >= 20000 chips, %ld valid calls refused\n", tables_bound, grid_calls,
                     long_int8_calls, valid_refused);
+    }
+
+    // ---- 1c. a fixed grid of tap lists under the default options ------------------------------------------------------------
+    // The tap lists of the GPU tests (and a random permutation of each) by layout, antennas, channels and kernel selection: every
+    // valid call launches (or meets the code-span bound); the vector kernel runs as many launches as the greedy grouping of the
+    // sorted taps; the matrix kernels only within L <= 16 and a span of 768; the launches cover the caller's taps exactly once.
+    {
+        gat_ctx *tctx = nullptr;
+        EXPECT(gat_create(0, GAT_OWN_STREAM, &tctx) == GAT_OK, "context for the tap grid");
+        EXPECT(gat_set_codes(tctx, codes.data(), lc, 32) == GAT_OK, "bind L1 for the tap grid");
+        const int N = 4096;
+        const double fs = 16.368e6;
+        const auto lists = tap_lists(N);
+        const int Ms[] = {1, 4, 16, 64}, Ks[] = {1, 2, 5};
+        void *o_re = nullptr, *o_im = nullptr;
+        const size_t outs = (size_t)5 * 32 * 64;
+        gat_malloc(tctx, outs * sizeof(float), &o_re);
+        gat_malloc(tctx, outs * sizeof(float), &o_im);
+        long tap_calls = 0, tap_launches = 0, tap_refused = 0;
+        for (int mode = 0; mode < 4; ++mode) {
+            EXPECT(gat_set_matrix_core(tctx, mode) == GAT_OK, "kernel selection %d", mode);
+            for (const auto &sh : lists)
+                for (int fmt = 0; fmt < 4; ++fmt)
+                    for (int M : Ms)
+                        for (int K : Ks) {
+                            const int L = (int)sh.size();
+                            gat_signal_desc sig = {(void *)(uintptr_t)0x10000000, fmt == 0 ? (void *)(uintptr_t)0x50000000 : nullptr, fmt, M, N, N, N, 0};
+                            std::vector<gat_channel_params> prm((size_t)K);
+                            for (int k = 0; k < K; ++k) prm[k] = {k % 32, 0, 1.023e6 * (1 + unif(-1e-5, 1e-5)), unif(-5e3, 5e3), unif(0, lc), unif(0, 1)};
+                            const long dc0 = hostsim::counters.dc_launches, mc0 = hostsim::counters.mfma_launches;
+                            hostsim::tap_cover.clear();
+                            const int32_t rc = gat_downconvert_and_correlate(tctx, &sig, prm.data(), 1, K, L, sh.data(), fs, (float *)o_re, (float *)o_im, 0);
+                            const bool ok = rc == GAT_OK || (rc == GAT_ERR_RANGE && span_refused(prm, fs, N, sh, lc));
+                            EXPECT(ok, "tap grid: %d (%s): mode %d layout %d M %d K %d L %d", rc, gat_last_error(tctx), mode, fmt, M, K, L);
+                            ++tap_calls;
+                            tap_refused += !ok;
+                            if (rc == GAT_OK) {
+                                const long dc = hostsim::counters.dc_launches - dc0, mc = hostsim::counters.mfma_launches - mc0;
+                                const long span = (long)*std::max_element(sh.begin(), sh.end()) - *std::min_element(sh.begin(), sh.end());
+                                EXPECT((mc == 0 && dc == greedy_groups(sh)) || (mc == 1 && dc == 0 && L <= gat::kMfmaMaxTaps && span <= gat::kMfmaMaxSpan),
+                                       "tap grid: %ld vector / %ld matrix-core launches for L %d span %ld (greedy %ld): mode %d layout %d M %d K %d", dc, mc, L, span,
+                                       greedy_groups(sh), mode, fmt, M, K);
+                                taps_covered(sh, "tap grid");
+                                tap_launches += dc + mc;
+                            }
+                            EXPECT(gat_sync(tctx) == GAT_OK, "sync");
+                        }
+        }
+        gat_free(tctx, o_re);
+        gat_free(tctx, o_im);
+        EXPECT(gat_destroy(tctx) == GAT_OK, "destroy");
+        std::printf("tap grid: %ld calls, %ld tap launches, %ld valid calls refused\n", tap_calls, tap_launches, tap_refused);
     }
 
     // ---- 1b. random acquisition searches (gat_acquire, gat_acq_stats_host) ---------------------------------------------------

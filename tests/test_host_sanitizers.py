@@ -44,6 +44,10 @@ def test_library_host_code_on_a_simulated_device_under_asan_ubsan():
     # among them, and no valid call refused (the planner once chose a tile that no longer fitted: 280 refusals in this grid)
     m = re.search(r"code tables: (\d+) tables bound, (\d+) grid calls, (\d+) calls on int8 tables of >= 20000 chips, (\d+) valid calls refused", out)
     assert m and int(m.group(1)) >= 35 and int(m.group(2)) >= 32400 and int(m.group(3)) >= 5400 and int(m.group(4)) == 0, out[-2000:]
+    # ... on the tap lists of the GPU tests by layout, antennas, channels and kernel selection: every valid call launched, with
+    # the launches covering each of the caller's taps exactly once (checked per call: a broken coverage is a failure above)
+    m = re.search(r"tap grid: (\d+) calls, (\d+) tap launches, (\d+) valid calls refused", out)
+    assert m and int(m.group(1)) >= 18048 and int(m.group(2)) >= 18048 and int(m.group(3)) == 0, out[-2000:]
     # ... and through the acquisition search's host side (csrc/gat_acq_api.cpp): launches, rejections and split grids
     m = re.search(r"acquisition sweep: (\d+) calls launched, (\d+) rejected, (\d+) with G > 1", out)
     assert m and int(m.group(1)) > 150 and int(m.group(2)) > 150 and int(m.group(3)) > 50, out[-2000:]
