@@ -30,7 +30,7 @@ struct gat_resident {
     bool running = false;             // a kernel was started and has not been seen to end
     bool stale = false;               // the code table changed: the correlator has to be opened again
     int K = 0, L = 0, M = 0, spv = 1;
-    long long N = 0, max_shift = 0;
+    long long N = 0;
     double fs = 0.0;
     uint32_t idle_us = 0, life_ms = 0, max_calls = 0;
     long long ticks_per_us = 100;
@@ -144,20 +144,23 @@ void drop_loop_graphs(gat_ctx *c);
 int32_t ensure_partial(gat_ctx *c, size_t bytes);
 int32_t upload_params(gat_ctx *c, const gat_channel_params *params_host, size_t n);
 
-// What the planner hands to gat_resident_open instead of launching: the arguments and geometry of the ONE vector launch
-// that would serve the call (four-wave workgroups, one antenna tile and one channel each: the resident instances).
-struct DcPlan {
-    long long max_wgs = 64; // in: workgroups the block's samples may be split over (times antenna tiles and channels)
-    gat::DcArgs a{};
-    gat::DcLaunch cfg{};
+// What planning returns: GAT_OK, or a refusal's code and message (the caller reports it with fail()).
+struct Refusal {
+    int32_t code;
+    const char *msg;
 };
 
 // params_dev: [B*K] records on the device -- or null with params_inline: B*K <= kInlineParams validated HOST records that
 // travel inside the vector kernel's arguments (uploaded after all if a matrix-core kernel takes the call)
-// plan_out != null: nothing is launched; GAT_ERR_UNSUPPORTED unless the call is exactly one launch of the vector kernel
 int32_t correlate_impl(gat_ctx *c, const gat_signal_desc *sig, const gat_channel_params *params_dev, int32_t B, int32_t K, int32_t L,
                        const int32_t *shifts, double fs, float *out_re, float *out_im, uint32_t flags,
-                       const gat_channel_params *params_inline = nullptr, DcPlan *plan_out = nullptr);
+                       const gat_channel_params *params_inline = nullptr);
+// The resident correlator's launch plan (gat_resident_open): the call's validation and every restriction of a resident
+// launch.  a, cfg: the arguments and geometry of the ONE vector launch that would serve the call -- one block, 16-byte
+// aligned, no tail; four-wave workgroups, one antenna tile and one channel each (the resident instances), about max_wgs
+// of them.  GAT_ERR_UNSUPPORTED where the call is no such launch.
+Refusal plan_resident(const gat_ctx &c, const gat_signal_desc *sig, int32_t K, int32_t L, const int32_t *shifts, double fs,
+                      long long max_wgs, DcArgs *a, DcLaunch *cfg);
 // host mirror of the kernels' `bad` predicate for host-resident records: what passes here is not poisoned there
 int32_t validate_params(gat_ctx *c, const gat_channel_params *params_host, size_t n, double reach, double fs);
 // the context's resident correlators (gat_resident_api.cpp): asked to leave before anything that waits for the whole device

@@ -152,23 +152,16 @@ GAT_API int32_t gat_resident_open(gat_ctx *c, const gat_signal_desc *sig, int32_
     // geometry: the planner's, restricted to the resident instances.  More workgroups shorten every workgroup's walk and
     // lengthen the host's (two or three result lines each): best around 128 (profiles/r04/resident/v10_*); behind a
     // forwarded host doorbell 64
-    DcPlan plan;
-    plan.max_wgs = cf.max_workgroups ? cf.max_workgroups : std::min(c->num_cus, bell_on_device ? 128 : 64);
-    const gat_channel_params dummy[kResMaxChannels] = {};
-    float *const nonnull = reinterpret_cast<float *>(uintptr_t(64));
-    int32_t rc = correlate_impl(c, sig, nullptr, 1, K, L, shifts, fs, nonnull, nonnull, 0, dummy, &plan);
-    if (rc != GAT_OK) return bail(rc);
-    if (!dc_has_resident_instance(plan.cfg.ant_tile, plan.cfg.taps, plan.cfg.format))
-        return bail(fail(c, GAT_ERR_UNSUPPORTED, "resident correlator: no kernel instance for this shape"));
-    res->a = plan.a;
-    res->cfg = plan.cfg;
+    // (the body posts its sums through LDS: the plan leaves the outputs, the scratch and the completion flag null)
+    const Refusal why = plan_resident(*c, sig, K, L, shifts, fs, cf.max_workgroups ? cf.max_workgroups : std::min(c->num_cus, bell_on_device ? 128 : 64),
+                                      &res->a, &res->cfg);
+    if (why.code != GAT_OK) return bail(fail(c, why.code, why.msg));
     res->K = K;
     res->L = L;
     res->M = sig->num_ants;
     res->N = sig->num_samples;
     res->fs = fs;
     res->spv = dc_group_samples(4, sig->layout);
-    for (int l = 0; l < L; ++l) res->max_shift = std::max<long long>(res->max_shift, std::llabs((long long)shifts[l]));
     res->idle_us = cf.idle_us ? cf.idle_us : 5000u;
     res->life_ms = cf.life_ms ? cf.life_ms : 2000u;
     res->max_calls = cf.max_calls ? cf.max_calls : 0xfffffff0u;
@@ -181,10 +174,10 @@ GAT_API int32_t gat_resident_open(gat_ctx *c, const gat_signal_desc *sig, int32_
     // ones, each counted in compute units at what one unit holds of its instance (occupancy API with the launch's LDS; the
     // API may answer one block too many near scalar-register limits -- MI355X_MICROARCH.md, Residency --, so one is taken off
     // every answer above one), may not exceed the device's.
-    res->wgs = (int)plan.a.total_wgs;
+    res->wgs = (int)res->a.total_wgs;
     {
         int occ = 0;
-        hipError_t oe = dc_resident_blocks_per_cu(plan.cfg, &occ);
+        hipError_t oe = dc_resident_blocks_per_cu(res->cfg, &occ);
         if (oe != hipSuccess) return bail(hipfail(c, oe, "hipOccupancyMaxActiveBlocksPerMultiprocessor"));
         if (occ < 1) return bail(fail(c, GAT_ERR_UNSUPPORTED, "resident correlator: the kernel instance does not fit a compute unit with this LDS size"));
         res->blocks_per_cu = occ > 1 ? occ - 1 : 1;
@@ -194,12 +187,12 @@ GAT_API int32_t gat_resident_open(gat_ctx *c, const gat_signal_desc *sig, int32_
             return bail(fail(c, GAT_ERR_UNSUPPORTED, "resident correlator: more workgroups than the device holds at once (with the context's other open resident correlators): lower max_workgroups, the channel count or close one"));
     }
     // pinned host block: doorbell | state | result lines of every workgroup
-    res->nval = 2 * plan.cfg.ant_tile * plan.cfg.taps;
+    res->nval = 2 * res->cfg.ant_tile * res->cfg.taps;
     res->lines_per_wg = (res->nval + kResLinePayload - 1) / kResLinePayload;
     for (int o = 0; o < res->nval; ++o) { // where the host's second stage finds a workgroup's values and where they go
         res->val_src.push_back((o / kResLinePayload) * 16 + o % kResLinePayload);
         const int ml = o >> 1;
-        if (!(o & 1)) res->val_dst.push_back(plan.a.tap_index[ml / plan.cfg.ant_tile] * sig->num_ants + ml % plan.cfg.ant_tile);
+        if (!(o & 1)) res->val_dst.push_back(res->a.tap_index[ml / res->cfg.ant_tile] * sig->num_ants + ml % res->cfg.ant_tile);
     }
     const size_t host_bytes = kResBellBytes + 64 + kResDevBytes + (size_t)res->wgs * res->lines_per_wg * 64;
     hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&res->h_block), host_bytes, hipHostMallocCoherent | hipHostMallocMapped);
@@ -227,12 +220,6 @@ GAT_API int32_t gat_resident_open(gat_ctx *c, const gat_signal_desc *sig, int32_
     }
     res->r.bell_copies = res->bell_copies;
     res->r.forward = !res->d_bell && res->wgs > (cf.host_pollers ? (int)cf.host_pollers : kResHostPollers) ? 1 : 0;
-    // the body posts its sums through LDS: it stores nothing to device or host memory itself
-    res->a.partial = nullptr;
-    res->a.out_re = nullptr;
-    res->a.out_im = nullptr;
-    res->a.done_counter = nullptr;
-    res->a.host_flag = nullptr;
     res->r.max_calls = res->max_calls;
     res->r.idle_ticks = (long long)res->idle_us * res->ticks_per_us;
     res->r.life_ticks = (long long)res->life_ms * 1000ll * res->ticks_per_us;
@@ -245,7 +232,7 @@ GAT_API int32_t gat_resident_open(gat_ctx *c, const gat_signal_desc *sig, int32_
         return bail(hipfail(c, e, "hipStreamCreateWithPriority"));
     res->seq = 1; // "the last call": nothing is pending when the kernel starts
     bell_set_seq(res, res->seq);
-    rc = resident_start(res, res->seq);
+    const int32_t rc = resident_start(res, res->seq);
     if (rc != GAT_OK) return bail(rc);
     c->residents.push_back(res);
     *out = res;
@@ -261,7 +248,7 @@ GAT_API int32_t gat_resident_correlate(gat_resident *res, const gat_channel_para
     if (res->stale) return fail(c, GAT_ERR_STATE, "the code table changed: open the resident correlator again");
     if (block_offset < 0 || block_offset % res->spv != 0 || block_offset >= (1ll << 40))
         return fail(c, GAT_ERR_ARG, "block offset must be a non-negative multiple of the samples one 16-byte load holds");
-    int32_t rc = validate_params(c, params_host, (size_t)res->K, (double)(res->N + res->max_shift), res->fs);
+    int32_t rc = validate_params(c, params_host, (size_t)res->K, (double)(res->N + res->a.max_abs_shift), res->fs);
     if (rc != GAT_OK) return rc;
 
     // ring: one line per channel, line 0 last; inside a line the two sequence words last
