@@ -93,7 +93,7 @@ def is_stale(lib: str = LIB) -> bool:
 def build_libgat(force: bool = False, verbose: bool = False, extra_flags: tuple[str, ...] = (), out: str = LIB) -> str:
     """Compile libgat.so for gfx950 if missing or older than its sources: one object per source under
     build/obj/ (compiled concurrently, reused while newer than source + headers), then one link.
-    ``extra_flags`` / ``out``: diagnostic variants (e.g. -DGAT_MFMA_STAMPS -> build/libgat_stamps.so)."""
+    ``extra_flags`` / ``out``: development variants (e.g. -DGAT_DC_DEV -> build/libgat_dev.so), always with -DGAT_DEV."""
     if not (force or is_stale(out)):
         return out
     from concurrent.futures import ThreadPoolExecutor
@@ -108,8 +108,6 @@ def build_libgat(force: bool = False, verbose: bool = False, extra_flags: tuple[
     hdr_t = max(os.path.getmtime(h) for h in HEADERS + [os.path.abspath(__file__)])
     jobs, objs = [], []
     dc_only = bool(extra_flags) and all(f.startswith("-DGAT_DC_") or f == "-DGAT_DEV" for f in extra_flags)
-    # ... and flags that only touch the split-bf16 matrix-core kernel (-DGAT_ABLATE=, -DGAT_MB_*)
-    mb_only = bool(extra_flags) and all(f.startswith("-DGAT_ABLATE") or f.startswith("-DGAT_MB_") or f == "-DGAT_DEV" for f in extra_flags)
     base_objdir = os.path.join(ROOT, "build", "obj")
     os.makedirs(base_objdir, exist_ok=True)
     for src in SOURCES:
@@ -117,13 +115,9 @@ def build_libgat(force: bool = False, verbose: bool = False, extra_flags: tuple[
         # flags that only touch the fused vector kernel (-DGAT_DC_*): every other object is shared with the main build
         vector_tu = src.startswith("gat_dc_f") or src.startswith("gat_resident_f")  # both are made of gat_dc_body.inc
         shared = dc_only and not vector_tu and src not in ("gat_api.cpp", "gat_planner.cpp", "gat_resident_api.cpp")  # the planner shares gat_internal.h
-        shared = shared or (mb_only and src not in ("gat_mfma_bf16.hip", "gat_api.cpp", "gat_planner.cpp"))
         obj = os.path.join(base_objdir if shared else objdir, os.path.splitext(src)[0] + ".o")
         objs.append(obj)
-        if shared:
-            extra_here = ()
-        else:
-            extra_here = extra_flags
+        extra_here = () if shared else extra_flags
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(sp), hdr_t):
             # the fused vector kernel is written with scalar FMAs on purpose (gat_dc.h): keep the SLP vectoriser from
             # re-packing them into v_pk_fma_f32 + operand-pairing moves
@@ -185,8 +179,4 @@ if __name__ == "__main__":
         print(build_libgat(extra_flags=flags, out=os.path.join(ROOT, "build", f"libgat_{name}.so"), verbose=False))
         sys.exit(0)
 
-    if "--stamps" in sys.argv:  # diagnostic build of the matrix kernels with per-wave cycle stamps
-        print(build_libgat(extra_flags=("-DGAT_MFMA_STAMPS",), out=os.path.join(ROOT, "build", "libgat_stamps.so"),
-                           verbose=True))
-    else:
-        print(build_libgat(force="--force" in sys.argv, verbose=True))
+    print(build_libgat(force="--force" in sys.argv, verbose=True))

@@ -866,16 +866,6 @@ GAT_API int32_t gat_debug_read_stream(gat_ctx *c, const void *dev, size_t bytes,
     return GAT_OK;
 }
 
-#ifdef GAT_MFMA_STAMPS
-extern "C" GAT_API int32_t gat_debug_read(gat_ctx *c, unsigned long long *host, size_t count)
-{
-    if (!c || !c->dbg_ptr) return GAT_ERR_STATE;
-    GAT_HIP(c, hipStreamSynchronize(c->stream));
-    GAT_HIP(c, hipMemcpy(host, c->dbg_ptr, count * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return GAT_OK;
-}
-#endif
-
 GAT_API int32_t gat_set_matrix_core(gat_ctx *c, int32_t enable)
 {
     if (!c) return GAT_ERR_ARG;

@@ -36,9 +36,6 @@ struct gat_resident {
     long long ticks_per_us = 100;
     unsigned last_exit = 0;
     uint64_t launches = 0, calls = 0;
-#ifdef GAT_RES_STAMPS
-    double host_us[2] = {}; // sums over the calls: ring written -> first workgroup taken -> every workgroup taken
-#endif
 };
 
 struct gat_ctx {
@@ -77,7 +74,6 @@ struct gat_ctx {
     std::vector<hipEvent_t> lap_events; // gat_timer_lap: pool, grows to the most laps ever outstanding
     size_t laps = 0;                    // laps recorded since the last gat_timer_laps
     int num_cus = 256;
-    unsigned long long *dbg_ptr = nullptr; // diagnostic builds only
     int max_ant_tile = gat::kMaxAntTile; // option max_ant_tile (gat_set_option)
     int max_aw = 4, max_kt = 4, max_bpw = 16; // options dc_aw / dc_kt / dc_bpw (gat_set_vector_tiling): caps of the vector kernel's geometry
     int force_bpw = 0;                        // option dc_bpw_force: blocks per workgroup whatever the planner's rule says (A/B runs)

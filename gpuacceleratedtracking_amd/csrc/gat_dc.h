@@ -233,22 +233,6 @@ __device__ __forceinline__ void completion_flag(unsigned *done_counter, unsigned
     }
 }
 
-// Diagnostic builds (-DGAT_DC_LAT_CUT=n, r03_latency_cuts.sh of an earlier round: git history): the kernel ends at cut point n -- 1 entry, 2 block
-// set-up + chip tables, 3 first replica segment + carrier anchors, 4 step loop -- so that the single-block latency can be
-// attributed to its phases (5: + reduction up to its barrier, 6: everything but the result stores).  Results are wrong by
-// construction; never part of the product build.
-#ifdef GAT_DC_LAT_CUT
-#define GAT_DC_LAT_CUT_AT(n)                                                                  \
-    do {                                                                                      \
-        if (GAT_DC_LAT_CUT == (n)) {                                                          \
-            completion_flag(a.done_counter, a.host_flag, a.flag_seq, a.total_wgs);            \
-            return;                                                                           \
-        }                                                                                     \
-    } while (0)
-#else
-#define GAT_DC_LAT_CUT_AT(n) do { } while (0)
-#endif
-
 template <int MT, int L, int VEC, int FMT, int AW, int KT, bool KEEP, int NW, int D>
 __global__ void __launch_bounds__(64 * NW, dc_min_waves(MT, L, KT, D, FMT, AW)) dc_kernel(const DcArgs a)
 {

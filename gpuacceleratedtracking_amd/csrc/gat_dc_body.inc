@@ -60,7 +60,6 @@
     const int kg = (int)(jq % (unsigned)a.KG);
     unsigned tile = (jq / (unsigned)a.KG) * 8u + xcd;
     if (tile >= (unsigned)a.num_tiles) return; // padding of the last group of 8 (whole workgroup exits)
-    GAT_DC_LAT_CUT_AT(1);
     const int split = tile % a.splits;
     tile /= a.splits;
     const int ag = tile % a.ant_groups;
@@ -172,10 +171,7 @@
         // 16-byte loads of antenna m's group at byte offset `off` of the block that starts at (bre, bim) (KEEP: plain
         // loads that stay in L2 for the other channel groups, otherwise non-temporal: aux bit 1)
         auto load_ant = [&](i32x4 (&raw)[IO::NV], int m, __amdgpu_buffer_rsrc_t rr, __amdgpu_buffer_rsrc_t ri, unsigned off) {
-#if defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 1)
-            off &= 0x3ff0u; // every load hits the same 16 KB (cache-resident): the arithmetic without the HBM stream
-#endif
-#if GAT_DC_BODY_RESIDENT && !defined(GAT_RES_FENCE)
+#if GAT_DC_BODY_RESIDENT
             // system-scope loads (sc0 sc1): no cache of this XCD answers them, so the call needs no cache invalidate between the
             // ring and its first loads (gat_resident.h)
             constexpr int aux = 1 | 16;
@@ -206,7 +202,6 @@
                 }
         }
 
-        GAT_DC_LAT_CUT_AT(8);
         // ---- per-channel constants of this block --------------------------------------------------------------
         // The double-precision ones (code rate, code phase, carrier step, carrier phase) are needed at segment starts
         // and on ragged ends only: they live in LDS.  In registers (wave-uniform -> scalar): the one-sample and
@@ -262,7 +257,6 @@
             restage |= valid && prn_k[kk] != staged_prn[kk];
             if (tid == 0) s_const[kk] = ChanConst{ratio, tau, step, phi};
         }
-        GAT_DC_LAT_CUT_AT(7);
         valid_mask = uni(valid_mask);
         bad_mask = uni(bad_mask);
 
@@ -278,7 +272,6 @@
             }
         }
         __syncthreads(); // s_const and the tables are in place
-        GAT_DC_LAT_CUT_AT(2);
 
         // ---- replica producer: walk constants of this thread's channel ----------------------------------------
         // one producer step advances RPC samples (the thread's next entry)
@@ -328,10 +321,6 @@
         constexpr int SB = dc_sub_batch(S, MT, L, KT, AW);
         constexpr int NH = S / SB;
         auto get_chips_sub = [&](float (&chip)[SB][L], int rel, const float *rep) {
-#if defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 2)
-            for (int j = 0; j < SB; ++j) for (int l = 0; l < L; ++l) chip[j][l] = __int_as_float(0x3f800000 + ((rel + j + l) & 1));
-            return;
-#endif
             typedef float f32x4a8 __attribute__((ext_vector_type(4), aligned(8)));
             typedef float f32x2a8 __attribute__((ext_vector_type(2), aligned(8)));
 #pragma unroll
@@ -627,9 +616,6 @@
             for (; j0 < run; ++j0) batch(std::integral_constant<int, 1>{}, j0);
         };
         auto fill_segment = [&](int c0, int seg_cnt) {
-#if defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 4)
-            return;
-#endif
             if (!g_valid) return;
             // (launch-uniform switches: taps at odd distances need the shifted copy; long codes are staged as sign bits)
             // (each form costs the instance scalar registers whether it runs or not: quads exist in the channel-looping 2 x 2 tile
@@ -656,9 +642,7 @@
         const int c_last = VEC == 4 ? c_stop : c_end;
         for (int c0 = c_begin; c0 < c_last; c0 += SEG) {
             const int c1 = min(c0 + SEG, c_last);
-#if !(defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 8))
             if (c0 > c_begin) __syncthreads(); // everybody has finished reading the previous segment's replica
-#endif
             fill_segment(c0, (c1 - c0) * CHUNK + a.rep_span);
             // the segment's carrier table U: one exact evaluation (src/algorithms.jl:172: double-precision phase, reduced,
             // float sincos) per (channel, step, sample of a lane's groups) -- KT * steps * G * S <= 256 entries, one thread each
@@ -677,10 +661,7 @@
                 *reinterpret_cast<f32x2 *>(s_ucar + ((kk * kUcarSteps + st) * (G * S) + e) * 2) = f32x2{cr, ci};
                 }
             }
-#if !(defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 8))
             __syncthreads();
-#endif
-            GAT_DC_LAT_CUT_AT(3);
 
             // ---- whole chunks.  The samples of step c+1 are loaded while step c is consumed: antenna by antenna, into
             // the registers that antenna's samples of step c have just left (loads in flight all the time, no second
@@ -740,15 +721,11 @@
                                 else
                                     accumulate_sub(acc[0][m], raw[DI][g][m], h * SB, pr, pi, chip, []() {});
                                 if (h + 1 == NH) {
-#if !(defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 16))
                                     load_ant(raw[DI][g][m], m, n_rr, n_ri, n_off[g]);
-#endif
                                 }
                                 // antenna by antenna: left alone the scheduler wipes off all antennas first (their
                                 // products and the refilled sample registers are then live together: + 30 registers)
-#if !(defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 32))
                                 __builtin_amdgcn_sched_barrier(0);
-#endif
                             }
                         }
                     }
@@ -781,12 +758,8 @@
                                     accumulate(acc[kk][m], xr, xi, pr[kk][j], pi[kk][j], chip[kk][j]);
                                 }
                             }
-#if !(defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 16))
                             load_ant(raw[DI][g][m], m, n_rr, n_ri, n_off[g]);
-#endif
-#if !(defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 32))
                             __builtin_amdgcn_sched_barrier(0);
-#endif
                         }
                         } else {
                         // the 2 x 2 tile with two channels (AW = 2, MT = 2, KT = 2): SB samples at a time -- chips and phasors
@@ -806,13 +779,9 @@
                                 for (int kk = 0; kk < KT; ++kk)
                                     accumulate_sub(acc[kk][m], raw[DI][g][m], h * SB, pr[kk], pi[kk], chip[kk], []() {});
                                 if (h + 1 == NH) {
-#if !(defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 16))
                                     load_ant(raw[DI][g][m], m, n_rr, n_ri, n_off[g]);
-#endif
                                 }
-#if !(defined(GAT_DC_ABLATE) && (GAT_DC_ABLATE & 32))
                                 __builtin_amdgcn_sched_barrier(0);
-#endif
                             }
                         }
                         }
@@ -839,7 +808,6 @@
             }
         }
 
-        GAT_DC_LAT_CUT_AT(4);
         // ---- block reduction: per channel 2*MT*L values per wave -> butterfly -> waves sharing an antenna tile ----
         // (everything below that is derived from the thread id -- the lane's first sample as a double, the butterfly's slot, the
         // output element's address, the tap-index select chain -- is invariant over the block loop: left alone the compiler
@@ -875,11 +843,7 @@
             s_part[(kk * NW + wave) * 64 + Butterfly<NV, 32>::index(lane_e)] = v[0];
         }
         __syncthreads();
-        GAT_DC_LAT_CUT_AT(5);
 
-#if defined(GAT_DC_LAT_CUT) && GAT_DC_LAT_CUT == 6
-        if (false)
-#endif
         for (int o = tid_e; o < KT * AW * NV; o += T) {
             const int kk = o / (AW * NV);
             const int r = o - kk * (AW * NV);

@@ -6,12 +6,10 @@
 
 #include "gat.h"
 
-// Diagnostic code (ablations, latency cuts, cycle stamps: kernels that compute WRONG results on purpose) and the
-// environment knobs of gat_create exist in development builds only; gat_version() names every flag of a build.
-#if (defined(GAT_DC_ABLATE) || defined(GAT_DC_LAT_CUT) || defined(GAT_ABLATE) || defined(GAT_MFMA_STAMPS) || defined(GAT_MB_CW8) || defined(GAT_MB_NT_LOADS) || defined(GAT_MB_NO_RING) || defined(GAT_MB_X2_ITEMS4) || defined(GAT_MB_X2_DEPTH2) || \
-     defined(GAT_RES_STAMPS) || defined(GAT_RES_FENCE)) &&                                                                                                 \
-    !defined(GAT_DEV)
-#error "diagnostic builds (-DGAT_DC_ABLATE, -DGAT_DC_LAT_CUT, -DGAT_ABLATE, -DGAT_MFMA_STAMPS, -DGAT_MB_CW8, -DGAT_RES_STAMPS, -DGAT_RES_FENCE) need -DGAT_DEV"
+// The reduced instance set (-DGAT_DC_DEV) and the environment knobs of gat_create exist in development builds only
+// (-DGAT_DEV); gat_version() names every flag of a build.
+#if defined(GAT_DC_DEV) && !defined(GAT_DEV)
+#error "-DGAT_DC_DEV needs -DGAT_DEV"
 #endif
 
 namespace gat {
@@ -28,16 +26,13 @@ constexpr int kMaxLaunchSpan = 2048;  // largest tap span one launch serves (the
 // Sample ownership of one lane per step in dc_kernel: G groups of S consecutive samples, one
 // 16-byte load per plane and group (vec == 4) or scalar loads (vec == 1).  S by format:
 // planar f32 4, interleaved ComplexF32 2, interleaved int16 4, interleaved int8 8.
-#ifndef GAT_PLANAR_GROUPS
-#define GAT_PLANAR_GROUPS 1
-#endif
 constexpr int dc_group_samples(int vec, int fmt)
 {
     return vec != 4 ? 1 : fmt == GAT_LAYOUT_PLANAR ? 4 : fmt == GAT_LAYOUT_INTERLEAVED ? 2 : fmt == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 8;
 }
 constexpr int dc_groups(int vec, int fmt)
 {
-    return vec != 4 ? 1 : fmt == GAT_LAYOUT_PLANAR ? GAT_PLANAR_GROUPS : fmt == GAT_LAYOUT_INTERLEAVED ? 2 : 1;
+    return vec == 4 && fmt == GAT_LAYOUT_INTERLEAVED ? 2 : 1;
 }
 // samples one workgroup covers per step: the nw / aw waves that share an antenna tile, 64 lanes each (nw = 4 waves per
 // workgroup, or 1: one-wave workgroups for short blocks, see gat_dc.h)
@@ -155,9 +150,6 @@ template <int FMT> hipError_t launch_dc_resident_fmt(const DcArgs &a, const DcLa
 // carrier table of one segment: [steps <= kUcarSteps][samples of a lane's groups, G * S <= 8][re, im] floats per channel
 constexpr int kUcarSteps = 8;
 constexpr int kUcarFloats = kUcarSteps * 8 * 2;
-#ifndef GAT_DC_SEG_ENTRIES
-#define GAT_DC_SEG_ENTRIES 8192
-#endif
 // Most steps whose code replica one workgroup produces at once (a "segment").  One channel per workgroup: ~8192 entries
 // (39 KB of LDS) when a wave carries 3-4 antennas -- those instances are limited to 3 workgroups per CU by registers
 // anyway, and longer segments mean fewer barriers (configs[1]: 0.846 vs 0.822 of HBM) --, ~4096 entries (25 KB) for 1-2
@@ -165,7 +157,7 @@ constexpr int kUcarFloats = kUcarSteps * 8 * 2;
 // looping workgroup.  The host may ask for fewer (short blocks).
 constexpr int dc_segment_steps(int chunk, int kt, int mt)
 {
-    const int s = (kt == 1 ? (mt >= 3 ? GAT_DC_SEG_ENTRIES : 4096) : 8192 / kt) / chunk;
+    const int s = (kt == 1 ? (mt >= 3 ? 8192 : 4096) : 8192 / kt) / chunk;
     return s < 2 ? 2 : (s > kUcarSteps ? kUcarSteps : s);
 }
 // Floats of LDS per channel for one segment's replica: entry i <-> sample (segment start) + shifts[0] + i, linear, so
@@ -296,7 +288,6 @@ struct MfArgs {
     int codes_in_lds;    // 1: the workgroup's chip tables are staged in LDS (they fit)
     int rep_ring;        // split-bf16 kernel: entries of a channel slot's chip-sign ring (a multiple of the tile, >= rep_span + 2 tiles; rep_stride >= rep_ring + rep_span + tile)
     int mb_mode;         // split-bf16 kernel: MbMode of this launch (the host's choice: mb_mode(), or kMbThree on request for int16)
-    unsigned long long *dbg; // diagnostic builds only (GAT_MFMA_STAMPS): per-wave cycle sums
     unsigned flags;
     int shifts[kMfmaMaxTaps];    // ascending
     int tap_index[kMfmaMaxTaps]; // position in the caller's list
@@ -305,12 +296,8 @@ struct MfArgs {
 // split-bf16 kernel: workgroup size -- 4 consumer waves + 12 producer waves (4 per SIMD, 128 VGPRs) where the instance fits
 // that register budget, otherwise + 8 producer waves (3 per SIMD, 168 VGPRs)
 constexpr int mb_threads(int RT, int NCT) { return ((RT == 2 && NCT == 1) || (RT == 4 && NCT == 2)) ? 768 : 1024; }
-// consumer waves: one per SIMD, or (experiment GAT_MB_CW8) two per SIMD for the 4 x 4 instance
-#ifdef GAT_MB_CW8
-constexpr int mb_consumer_waves(int RT, int NCT) { return (RT == 4 && NCT == 4) ? 8 : 4; }
-#else
+// consumer waves: one per SIMD
 constexpr int mb_consumer_waves(int, int) { return 4; }
-#endif
 constexpr int kMbMaxChain = 8192;  // samples per accumulation chain (f32 rounding of the running sum)
 constexpr int kMbMaxSlots = 24;    // channel slots per workgroup (header size)
 constexpr int kMbHeader = 1536;    // ChanInfoB[<= 20] (64 B each) + slack, 16-byte aligned
@@ -343,11 +330,7 @@ constexpr int mb_mode(int rt, int nct, int fmt, bool force_three = false)
 constexpr int mb_two_row_bytes(int T) { return ((10 * T + 15) / 16 * 16) | 16; }
 // chip-sign ring of the split-bf16 kernel: ring length and the least row length for a tap span (gat_mfma_bf16.hip, s_rep)
 // (instances of two or four row tiles; those of one keep two buffers of span + T entries and copy the overlap)
-#ifdef GAT_MB_NO_RING // A/B build: two buffers and the overlap copy in every instance, as up to round 4
-constexpr bool mb_rep_ring_rows(int) { return false; }
-#else
 constexpr bool mb_rep_ring_rows(int rt) { return rt >= 2; }
-#endif
 constexpr int mb_rep_ring(int rt, int T, int span) { return mb_rep_ring_rows(rt) ? (span + 2 * T + T - 1) / T * T : 0; }
 constexpr int mb_rep_row(int rt, int T, int span) { return mb_rep_ring_rows(rt) ? mb_rep_ring(rt, T, span) + span + T : span + T; }
 constexpr size_t mb_lds_bytes(int rt, int nct, int fmt, int nslots, int rep_stride, int code_bits_stride, int mode = -1)

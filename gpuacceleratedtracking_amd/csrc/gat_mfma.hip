@@ -307,12 +307,6 @@ __global__ void __launch_bounds__(2 * kThreads) mfma_kernel(const MfArgs a)
     };
 
     // ---- pipeline ----------------------------------------------------------------------------------
-#ifdef GAT_MFMA_STAMPS
-    unsigned long long t_work = 0, t_wait = 0, t0_ = 0, t1_ = 0;
-#define GAT_STAMP(v) v = __builtin_amdgcn_s_memtime()
-#else
-#define GAT_STAMP(v)
-#endif
     if (producer && s_begin < s_end) {
         load_x(s_begin);
         produce(s_begin, 0);
@@ -320,25 +314,13 @@ __global__ void __launch_bounds__(2 * kThreads) mfma_kernel(const MfArgs a)
     __syncthreads();
     for (int st = s_begin; st < s_end; ++st) {
         const int buf = (st - s_begin) & 1;
-        GAT_STAMP(t0_);
         if (producer) {
             if (st + 1 < s_end) produce(st + 1, buf ^ 1);
         } else {
             consume(st, buf);
         }
-        GAT_STAMP(t1_);
         __syncthreads();
-#ifdef GAT_MFMA_STAMPS
-        t_work += t1_ - t0_;
-        t_wait += __builtin_amdgcn_s_memtime() - t1_;
-#endif
     }
-#ifdef GAT_MFMA_STAMPS
-    if (lane == 0 && a.dbg) { // [workgroup][wave][2]
-        a.dbg[((size_t)blockIdx.x * 8 + wave) * 2 + 0] = t_work;
-        a.dbg[((size_t)blockIdx.x * 8 + wave) * 2 + 1] = t_wait;
-    }
-#endif
 
     // ---- epilogue ----------------------------------------------------------------------------
     if constexpr (WPT > 1) { // sum the accumulators of the consumer waves that shared a channel tile

@@ -29,7 +29,7 @@
 // ONE bf16 term: 3 products {x*hi, x*mid, x*lo} = 4 slots per sample, a slice covers 4 samples (half the MFMAs) and
 // both fragments come ready-made from LDS (X = {x|x, x|0}, W = {hi|mid, lo|0} per sample; see X1 below).  int16 samples are
 // exact in TWO terms: 5 products per sample laid as a stream over consecutive MFMAs (round 5, FragSet<RT, kMbTwo> below).
-// What bounds the kernel (profiles/r05/mfma_cycle_stamps_*.txt, mfma_bf16_ablation_*.txt): float samples --
+// What bounds the kernel (round 5's diagnostic builds, profiles/r05/mfma_cycle_stamps_*.txt, mfma_bf16_ablation_*.txt): float samples --
 // the consumers (matrix pipe + fragment fetches + operand preparation) at the power cap's clock; int16 / int8 -- the producer
 // waves' chains and the consumers about level, coupled through LDS and the issue ports.
 // One accumulation chain covers at most kMaxChain samples (the planner splits longer blocks over
@@ -77,13 +77,9 @@ __device__ __forceinline__ Split3 split3(float v)
 // prefetch distance).  The compiler does not see these loads; every use of the destination goes
 // through wait_loads(), which ties the registers to the wait -- in straight-line code only: a branch
 // around the wait makes the register allocator COPY the registers before it, i.e. before the data is there.
-__device__ __forceinline__ void gload_nt(f32x4_ &dst, const void *p)
+__device__ __forceinline__ void gload_plain(f32x4_ &dst, const void *p)
 {
-#ifdef GAT_MB_NT_LOADS // A/B build: non-temporal sample loads, as up to round 4
-    asm volatile("global_load_dwordx4 %0, %1, off nt" : "=v"(dst) : "v"(p) : "memory");
-#else
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p) : "memory");
-#endif
 }
 template <int XI> // XI loads per register set; the two other sets' 2 * XI loads are newer and may stay in flight
 __device__ __forceinline__ void wait_loads(f32x4_ (&xv)[XI])
@@ -125,18 +121,12 @@ struct FragSet {
     u32x4 w;
     unsigned m;
     u32x2 xa[RT];
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 64)
-    u32x2 wl;
-#endif
 };
 template <int RT>
 struct FragSet<RT, kMbOne> {
     u32x4 w;
     u32x2 m;
     u32x4 xa[RT];
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 64)
-    u32x2 wl;
-#endif
 };
 template <int RT>
 struct FragSet<RT, kMbTwo> {
@@ -159,19 +149,7 @@ constexpr int frag_newer(int J, int n, int NM)
 template <int J, int RT, int XM>
 __device__ __forceinline__ void frag_issue(FragSet<RT, XM> &s, unsigned w_addr, unsigned r_addr, const unsigned (&x_addr)[RT])
 {
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 256) // diagnostic: no fragment fetches (one LDS read keeps the counted waits meaningful)
-    {
-        unsigned one;
-        asm volatile("ds_read_b32 %0, %1" : "=v"(one) : "v"(r_addr));
-        if constexpr (XM == kMbThree) s.m = one; else s.m[0] = one;
-        return;
-    }
-#endif
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 64) // diagnostic: half the W fragment bytes (results wrong)
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(s.wl) : "v"(w_addr), "n"(J * 16));
-#else
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(s.w) : "v"(w_addr), "n"(J * 16));
-#endif
     if constexpr (XM == kMbTwo) {
         constexpr int j = J % 5, sb = 8 * (J / 5);
         constexpr int o0 = sb + (j == 0 ? 0 : j == 1 ? 1 : j == 2 ? 3 : j == 3 ? 4 : 6); // first sample of the slice
@@ -220,11 +198,9 @@ template <int RT, int XM = kMbThree>
 constexpr int frag_depth()
 {
     constexpr int per = XM == kMbTwo ? 3 + RT : 2 + RT;
-#ifndef GAT_MB_X2_DEPTH2
     // (four row tiles on the two-term and one-term paths: 64 accumulator registers + 23 per fragment set -- three sets do not fit the 128 of a
     // 16-wave workgroup, and what the allocator then spills are fragments that LDS reads may still have in flight: two sets)
     if ((XM == kMbTwo || XM == kMbOne) && RT == 4) return 1; // (one term: 22 registers per set, the same arithmetic)
-#endif
     return (15 / per) < 4 ? (15 / per) : 4;
 }
 
@@ -251,23 +227,7 @@ template <int J, int RT, int XM>
 __device__ __forceinline__ void mfma_apply(f32x16 (&acc)[RT == 1 ? 2 : RT], FragSet<RT, XM> &cur)
 {
     constexpr bool X1 = XM == kMbOne;
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 128) // diagnostic (results wrong): the arithmetic of two k-slices out of three -- what a
-    if constexpr (XM == kMbThree && J % 3 == 2) return;   // 2-term split of the SAMPLE operand (5 products, 3 samples per MFMA) would issue
-#endif
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 512) // diagnostic: no vector preparation of the operands (3-term path)
-    if constexpr (XM == kMbThree) {
-        const bf16x8 bw0 = __builtin_bit_cast(bf16x8, cur.w);
-#pragma unroll
-        for (int t = 0; t < RT; ++t)
-            acc[RT == 1 ? (J & 1) : t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                __builtin_bit_cast(bf16x8, u32x4{cur.xa[t][0], cur.xa[t][1], cur.xa[t][0], cur.xa[t][1]}), bw0, acc[RT == 1 ? (J & 1) : t], 0, 0, 0);
-        return;
-    }
-#endif
     u32x4 w = cur.w;
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 64)
-    if constexpr (XM == kMbThree) w = u32x4{cur.wl[0], cur.wl[1], cur.wl[0], cur.wl[1]};
-#endif
     if constexpr (XM == kMbTwo) {
         // chip signs of the slice's two or three samples onto the dwords (= slot pairs) of the W fragment; LH(a, b) = low half of
         // a | high half of b, where a sample ends inside a dword
@@ -360,9 +320,7 @@ __device__ __forceinline__ void xstep_slice(f32x16 (&acc)[RT == 1 ? 2 : RT], Fra
     } else {
         if constexpr (J + D == NM) { // the first fetch that belongs to the next step: this step's reads are home, then the barrier
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if !(defined(GAT_ABLATE) && (GAT_ABLATE & 32)) // diagnostic: no step barrier (both roles)
             __syncthreads();
-#endif
         }
         unsigned x_next[RT]; // the other buffer: a wave-uniform distance away
 #pragma unroll
@@ -415,14 +373,9 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
     // of a wave (consecutive q) store CONSECUTIVE 16-byte W entries and consecutive replica words (round 2 owned the
     // adjacent samples 2q, 2q + 1: every W store 32 bytes from its neighbour's -- every other bank group, 2-way conflicts,
     // SQ_LDS_BANK_CONFLICT 24.6 % of SQ_LDS_IDX_ACTIVE at configs[4]; 18.3 % now, profiles/r03).  1-term path (int8): the
-    // consumers read adjacent sample pairs as one 16-byte entry, the item keeps 2q, 2q + 1.  2-term path: an item is FOUR
-    // adjacent samples 4q .. 4q + 3 (40 bytes of a slot-ordered row, five 8-byte stores), rotated one sample at a time.
+    // consumers read adjacent sample pairs as one 16-byte entry, the item keeps 2q, 2q + 1, and so does the 2-term path.
     constexpr int OS = XM == kMbThree ? T / 2 : 1;
-#ifdef GAT_MB_X2_ITEMS4 // A/B build: four samples per item of the two-term path (40 bytes, five 8-byte stores)
-    constexpr int IS = X2 ? 4 : 2;    // samples per producer item
-#else
     constexpr int IS = 2;             // samples per producer item (2-term path: 20 bytes of a slot-ordered row, five 4-byte stores)
-#endif
     constexpr int RB = mb_two_row_bytes(T); // 2-term path: bytes per X / W row (10 per sample, slot order)
     // LDS row strides in entries.  3-term: X 8 B / W 16 B per sample, odd (32 planes x one sample = 32 distinct
     // bank pairs).  1-term: X 8 B / W 8 B per sample, read in 16-byte pairs: even, rows 4 banks apart.
@@ -573,21 +526,12 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
             const bool ok = id < NG && st < s_end && n < N;
             const long long off = PLANAR ? ((row & 1) ? im_delta : 0ll) + 4ll * ((long long)(row >> 1) * a.ant_stride + n)
                                          : (long long)BYTES * ((long long)row * a.ant_stride + n);
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 16) // diagnostic: no sample loads at all
-            (void)ok; (void)off; xv[it] = f32x4_{1.f, 1.f, 1.f, 1.f};
-#else
-            gload_nt(xv[it], ok ? re_base + off : reinterpret_cast<const char *>(a.zeros));
-#endif
+            gload_plain(xv[it], ok ? re_base + off : reinterpret_cast<const char *>(a.zeros));
         }
     };
     auto store_x = [&](auto &xv, int st, int buf) {
         constexpr int XI = sizeof(xv) / sizeof(xv[0]);
-#if !(defined(GAT_ABLATE) && (GAT_ABLATE & 16))
         wait_loads<XI>(xv);
-#endif
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 4) // diagnostic: samples are split / stored only for the first two steps
-        if (st >= s_begin + 2) return;
-#endif
         const int nb = st * T;
         u32x2 *xb = X2 ? s_x + buf * RT * 32 * (RB / 8) : s_x + buf * RT * 32 * XS;
 #pragma unroll
@@ -631,14 +575,8 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
                     const unsigned fb = __float_as_uint(v);
                     xb[plane * XS + rel] = u32x2{GAT_PERM(fb, fb, 0x03020302u), fb >> 16};
                 } else {
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 128) // diagnostic: the producers' share of a 2-term sample split (no lo term)
-                    const unsigned fb = __float_as_uint(v);
-                    const float r = v - __uint_as_float(fb & 0xffff0000u);
-                    xb[plane * XS + rel] = u32x2{GAT_PERM(__float_as_uint(r), fb, 0x07060302u), 0u};
-#else
                     const Split3 sp = split3(v);
                     xb[plane * XS + rel] = u32x2{GAT_PERM(sp.r, sp.v, 0x07060302u), GAT_PERM(sp.r2, sp.r2, 0x03020302u)};
-#endif
                 }
             };
             if constexpr (PLANAR) {
@@ -714,11 +652,11 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
     // carries its phasor and code index from step to step: one complex rotation by e^{j 2 pi T step}
     // instead of an FP64 range reduction + sincos; re-anchored in FP64 every kReanchor steps.
     float car_r = 0.f, car_i = 0.f;
-    int rep_ip = 0, rep_t = 0, rep_ip2 = 0, rep_t2 = 0;
+    int rep_ip = 0, rep_t = 0;
     // (2-term path: the items of 16 consecutive lanes are two slots 2 apart -- rows 4 apart, complementary banks, as for X)
     const int item_i = ptid / (T / IS), item_q = ptid % (T / IS);
     const int item_slot = X2 ? ((item_i & ~3) | ((item_i & 1) << 1) | ((item_i >> 1) & 1)) : item_i;
-    const int item_s0 = X2 ? IS * item_q : X1 ? 2 * item_q : item_q; // the item's first sample (step-relative); its second one is OS further
+    const int item_s0 = X2 || X1 ? IS * item_q : item_q; // the item's first sample (step-relative); its second one is OS further
     const bool have_item = producer && item_slot < nslots;
     int p_win = 0; // ring position of the window of the step being produced (wave-uniform)
     auto produce = [&](int st, int buf, bool first) { // everything of step st except the samples
@@ -746,19 +684,8 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
         if (!have_item) return;
         if (!c.valid) return;
         const bool anchor = first || ((st - s_begin) % kReanchor) == 0; // wave-uniform
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 1) // diagnostic builds (ablate_mfma_bf16.sh of an earlier round: git history; results wrong on purpose): no replica
-        if (first)
-#endif
-        {
-            gen_rep2(c, s_code + item_slot * a.code_bits_stride, rb + item_slot * RS, win, nb, span + item_s0, OS, span + T,
-                     anchor || !c.inc_ok, rep_ip, rep_t);
-            if constexpr (X2 && IS == 4) // the item's samples 2 and 3
-                gen_rep2(c, s_code + item_slot * a.code_bits_stride, rb + item_slot * RS, win, nb, span + item_s0 + 2, 1, span + T,
-                         anchor || !c.inc_ok, rep_ip2, rep_t2);
-        }
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 2) // diagnostic: carrier fragments only in the first step
-        if (!first) return;
-#endif
+        gen_rep2(c, s_code + item_slot * a.code_bits_stride, rb + item_slot * RS, win, nb, span + item_s0, OS, span + T,
+                 anchor || !c.inc_ok, rep_ip, rep_t);
         float cr, ci;
         if (anchor) {
             const double th = __builtin_fma((double)(nb + item_s0), c.step, c.phi);
@@ -769,7 +696,7 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
         }
         car_r = cr;
         car_i = ci;
-        if constexpr (X2 && IS == 2) { // slot order of a sample: h m l h m  (against a a a b b); two samples = five dwords
+        if constexpr (X2) { // slot order of a sample: h m l h m  (against a a a b b); two samples = five dwords
             const Split3 c0 = split3(cr), s0 = split3(-ci);
             const float tr = __builtin_fmaf(cr, c.wr, -(ci * c.wi));
             ci = __builtin_fmaf(cr, c.wi, ci * c.wr);
@@ -779,30 +706,6 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
             unsigned *dim = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(dre) + RB);
             dre[0] = GAT_P2(c0.r, c0.v); dre[1] = GAT_P2(c0.v, c0.r2); dre[2] = GAT_P2(c1.v, c0.r); dre[3] = GAT_P2(c1.r2, c1.r); dre[4] = GAT_P2(c1.r, c1.v);
             dim[0] = GAT_P2(s0.r, s0.v); dim[1] = GAT_P2(s0.v, s0.r2); dim[2] = GAT_P2(s1.v, s0.r); dim[3] = GAT_P2(s1.r2, s1.r); dim[4] = GAT_P2(s1.r, s1.v);
-            return;
-        } else if constexpr (X2) {
-            unsigned ch[4], cm[4], cl[4], sh[4], sm[4], sl[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const Split3 sc = split3(cr), ss = split3(-ci);
-                ch[u] = sc.v; cm[u] = sc.r; cl[u] = sc.r2;
-                sh[u] = ss.v; sm[u] = ss.r; sl[u] = ss.r2;
-                if (u < 3) {
-                    const float tr = __builtin_fmaf(cr, c.wr, -(ci * c.wi));
-                    ci = __builtin_fmaf(cr, c.wi, ci * c.wr);
-                    cr = tr;
-                }
-            }
-            auto put4 = [&](int wrow, const unsigned (&H)[4], const unsigned (&M)[4], const unsigned (&Lo)[4]) {
-                u32x2 *d = reinterpret_cast<u32x2 *>(reinterpret_cast<unsigned char *>(wb) + wrow * RB + 40 * item_q);
-                d[0] = u32x2{GAT_P2(M[0], H[0]), GAT_P2(H[0], Lo[0])};
-                d[1] = u32x2{GAT_P2(H[1], M[0]), GAT_P2(Lo[1], M[1])};
-                d[2] = u32x2{GAT_P2(M[1], H[1]), GAT_P2(M[2], H[2])};
-                d[3] = u32x2{GAT_P2(H[2], Lo[2]), GAT_P2(H[3], M[2])};
-                d[4] = u32x2{GAT_P2(Lo[3], M[3]), GAT_P2(M[3], H[3])};
-            };
-            put4(2 * item_slot, ch, cm, cl);
-            put4(2 * item_slot + 1, sh, sm, sl);
             return;
         }
         u32x2 *w_re = wb + ((2 * item_slot) * WS + item_s0) * WE;
@@ -864,9 +767,6 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
     const unsigned lds_x = (unsigned)(uintptr_t)s_x, lds_w = (unsigned)(uintptr_t)s_w, lds_r = (unsigned)(uintptr_t)s_rep;
     int c_win = 0; // ring position of the window of the step being consumed (wave-uniform)
     auto consume = [&](int buf) {
-#if defined(GAT_ABLATE) && (GAT_ABLATE & 8) // diagnostic: no MFMA work
-        return;
-#endif
         unsigned x_addr[RT];
 #pragma unroll
         for (int t = 0; t < RT; ++t) x_addr[t] = lds_x + (unsigned)(buf * XBUF + t * XTILE + XU * x_off);
@@ -877,14 +777,6 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
     };
 
     // ---- pipeline ----------------------------------------------------------------------------------
-#ifdef GAT_MFMA_STAMPS // per wave: [0] work, [1] barrier wait, [2] producers: carriers + replica, [3] producers: split/store
-    unsigned long long t_work = 0, t_wait = 0, t_gen = 0, t_st = 0, t0_ = 0, t1_ = 0, t2_ = 0;
-#define GAT_STAMP(v) v = __builtin_amdgcn_s_memtime()
-#define GAT_ACC(dst, a_, b_) dst += (b_) - (a_)
-#else
-#define GAT_STAMP(v)
-#define GAT_ACC(dst, a_, b_)
-#endif
     // one instance of the producer loop per prefetch-group size: the counted waits need straight-line code
     auto producer_loop = [&](auto xi_tag) {
         constexpr int XI = decltype(xi_tag)::value;
@@ -907,25 +799,14 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
         // phase j of an iteration: the consumers work on step st + j (buffer j & 1) while step st + j + 1 is produced
         // into the other buffer from register set (j + 1) % 3 (the iteration advances by 6 = lcm(2 buffers, 3 sets))
         auto phase = [&](int step, int buf, auto &xv) {
-            GAT_STAMP(t0_);
             if (step < s_end) {
                 produce(step, buf, false);
-                GAT_STAMP(t2_);
                 if constexpr (XI > 0) {
                     store_x(xv, step, buf);
                     load_x(xv, step + 3);
                 }
-                GAT_STAMP(t1_);
-                GAT_ACC(t_gen, t0_, t2_);
-                GAT_ACC(t_st, t2_, t1_);
             }
-            GAT_STAMP(t1_);
-#if !(defined(GAT_ABLATE) && (GAT_ABLATE & 32))
             __syncthreads();
-#endif
-            GAT_STAMP(t2_);
-            GAT_ACC(t_work, t0_, t1_);
-            GAT_ACC(t_wait, t1_, t2_);
         };
         for (int st = s_begin; st < s_end; st += 6) {
             phase(st + 1, 1, xv1);
@@ -952,26 +833,6 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
         default: producer_loop(std::integral_constant<int, 4>{}); break;
         }
     } else {
-#if defined(GAT_MB_STEP_PIPELINE_OFF) || defined(GAT_MFMA_STAMPS) || (defined(GAT_ABLATE) && (GAT_ABLATE & 8))
-        __syncthreads();
-        for (int st = s_begin; st < s_end; st += 2) {
-            GAT_STAMP(t0_);
-            consume(0);
-            GAT_STAMP(t1_);
-            __syncthreads();
-            GAT_STAMP(t2_);
-            GAT_ACC(t_work, t0_, t1_);
-            GAT_ACC(t_wait, t1_, t2_);
-            if (st + 1 >= s_end) break;
-            GAT_STAMP(t0_);
-            consume(1);
-            GAT_STAMP(t1_);
-            __syncthreads();
-            GAT_STAMP(t2_);
-            GAT_ACC(t_work, t0_, t1_);
-            GAT_ACC(t_wait, t1_, t2_);
-        }
-#else
         // k-slices pipelined across the step barrier (xstep above): one barrier per step as before, inside the slice stream.
         // The ring position of a step's first slice advances by NM mod RING per step, so RING consecutive steps are
         // unrolled (each with its position as a constant: no run-time choice between code copies -- a merge of copies
@@ -1028,14 +889,7 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
             consume((st - s_begin) & 1);
             __syncthreads();
         }
-#endif
     }
-#ifdef GAT_MFMA_STAMPS
-    if (lane == 0 && a.dbg) { // [workgroup][wave][4]
-        unsigned long long *d = a.dbg + ((size_t)blockIdx.x * 16 + wave) * 4;
-        d[0] = t_work; d[1] = t_wait; d[2] = t_gen; d[3] = t_st;
-    }
-#endif
 
     if constexpr (RT == 1) acc[0] += acc[1];
 

@@ -575,14 +575,6 @@ int32_t enqueue_plan(gat_ctx *c, const Call &call, Plan &p)
     }
     if (p.kind) {
         p.m.partial = c->d_partial;
-#ifdef GAT_MFMA_STAMPS
-        {
-            static unsigned long long *dbg = nullptr;
-            if (!dbg) hipMalloc(reinterpret_cast<void **>(&dbg), 8u << 20);
-            p.m.dbg = dbg;
-            c->dbg_ptr = dbg;
-        }
-#endif
         if (p.kind == 2)
             GAT_HIP(c, launch_mfma_bf16(p.m, p.rt, p.nct, call.sig->layout, p.grid, p.lds, c->stream));
         else

@@ -92,9 +92,6 @@ __global__ void __launch_bounds__(256) dc_resident_kernel(const DcArgs a, const 
     long long t_last = t_start;
     const ResidentEnv env{s_bell, s_out};
 
-#ifdef GAT_RES_STAMPS
-    long long t_seen_ = 0;
-#endif
     for (;;) {
         // ---- wait for a ring: wave 0 reads all K lines with ONE 16-byte load per lane (lane i <-> dwords 4i .. 4i+3: a line is
         // four lanes; sixteen channels are one load -- K > 4 used to cost a second trip, ~1 us).  Doorbell in device memory (the
@@ -177,9 +174,6 @@ __global__ void __launch_bounds__(256) dc_resident_kernel(const DcArgs a, const 
             }
             *reinterpret_cast<u32x4 *>(&s_bell[4 * ln]) = v;
             if (ln == 0) s_ctl[0] = seq;
-#ifdef GAT_RES_STAMPS
-            t_seen_ = wall_clock64();
-#endif
         }
         __syncthreads();
         const unsigned seq = uni(s_ctl[0]);
@@ -189,18 +183,7 @@ __global__ void __launch_bounds__(256) dc_resident_kernel(const DcArgs a, const 
         // nothing of it may come from this XCD's caches.  The body's sample loads are system-scope loads for that -- a cache
         // invalidate here (a system-scope acquire fence) costs every workgroup ~0.3 us and the invalidates of an XCD's workgroups
         // queue up behind each other: 1.8 us from the ring to the first loads with 20 workgroups, 8.3 us with 240
-        // (profiles/r04/resident/v10_*; -DGAT_RES_FENCE builds that form).
-#ifdef GAT_RES_FENCE
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-#endif
-
-#ifdef GAT_RES_STAMPS // development builds: where a call's time goes (100 MHz clock), read back by gat_resident_close
-        long long st_[10] = {};
-        st_[0] = wall_clock64();
-        const long long cyc0_ = clock64();
-#undef GAT_DC_LAT_CUT_AT
-#define GAT_DC_LAT_CUT_AT(n) do { st_[n] = wall_clock64(); } while (0)
-#endif
+        // (profiles/r04/resident/v10_*, measured with a diagnostic build of round 4).
         { // the correlator itself: the text dc_kernel is made of
 #define GAT_DC_BODY_RESIDENT 1
 #include "gat_dc_body.inc"
@@ -218,17 +201,6 @@ __global__ void __launch_bounds__(256) dc_resident_kernel(const DcArgs a, const 
             if (i == 15) v = seq;
             __hip_atomic_store(r.host_lines + (size_t)slot * (LW * 16) + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
-#ifdef GAT_RES_STAMPS
-        st_[6] = wall_clock64();
-        if (master && threadIdx.x == 0)
-            for (int i = 0; i < 7; ++i) r.host_state[4 + i] = (unsigned)(st_[i] - st_[0]);
-        if (master && threadIdx.x == 0) {
-            r.host_state[11] = (unsigned)(st_[0] - t_seen_);
-            r.host_state[12] = (unsigned)(st_[8] - st_[0]);
-            r.host_state[13] = (unsigned)(st_[7] - st_[0]);
-            r.host_state[14] = (unsigned)(clock64() - cyc0_); // shader-clock cycles of the same span as st_[6] - st_[0]
-        }
-#endif
         ++calls;
         t_last = wall_clock64();
     }

@@ -3,7 +3,6 @@
 // host memory, ring / wait + second stage, restart after the kernel has left, park before anything that waits for the whole
 // device, the host-closed tracking loop.
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 #include <ctime>
 #include <new>
@@ -323,14 +322,8 @@ GAT_API int32_t gat_resident_correlate(gat_resident *res, const gat_channel_para
         return true;
     };
     const double t0 = mono_us(), deadline = (double)res->life_ms * 1000.0 + 1.0e6;
-#ifdef GAT_RES_STAMPS
-    double t_first = 0.0;
-#endif
     for (unsigned spins = 0;; ++spins) {
         if (take_arrived()) break;
-#ifdef GAT_RES_STAMPS
-        if (t_first == 0.0 && slot > 0) t_first = mono_us();
-#endif
         if ((spins & 15u) != 15u) continue;
         if (__atomic_load_n(&res->h_state[0], __ATOMIC_ACQUIRE) != kResidentRuns) {
             // the kernel has left (idle, lifetime, call budget) -- with this call served or not
@@ -344,12 +337,6 @@ GAT_API int32_t gat_resident_correlate(gat_resident *res, const gat_channel_para
             return fail(c, GAT_ERR_STATE, "resident correlator: no answer from the device");
         }
     }
-#ifdef GAT_RES_STAMPS
-    const double t_all = mono_us();
-    if (t_first == 0.0) t_first = t_all;
-    res->host_us[0] += t_first - t0;
-    res->host_us[1] += t_all - t_first;
-#endif
     ++res->calls;
     return GAT_OK;
 }
@@ -418,13 +405,6 @@ GAT_API int32_t gat_resident_close(gat_resident *res)
     gat_ctx *c = res->ctx;
     (void)hipSetDevice(c->device);
     const int32_t rc = resident_park(res);
-#ifdef GAT_RES_STAMPS
-    std::fprintf(stderr, "resident stamps of the last call (10 ns ticks): ring seen -> barrier + acquire %u; then tile decode %u, first loads issued %u, parameters %u, setup (barrier) %u, first segment %u, steps %u, reduction %u, result lines %u (= %u counts of clock64)\n",
-                 res->h_state[11], res->h_state[4 + 1], res->h_state[12], res->h_state[13], res->h_state[4 + 2], res->h_state[4 + 3], res->h_state[4 + 4], res->h_state[4 + 5], res->h_state[4 + 6], res->h_state[14]);
-    if (res->calls)
-        std::fprintf(stderr, "host side, mean over %llu calls (us): ring written -> first workgroup's result lines whole and added %.2f, -> all %d lines of %d workgroups %.2f\n",
-                     (unsigned long long)res->calls, res->host_us[0] / (double)res->calls, res->wgs * res->lines_per_wg, res->wgs, res->host_us[1] / (double)res->calls);
-#endif
     c->residents.erase(std::remove(c->residents.begin(), c->residents.end(), res), c->residents.end());
     resident_free(res);
     return rc;

@@ -3,7 +3,7 @@
 //   -DGAT_BUILD_FLAGS="<the -D flags of the build beyond the product recipe | none>"
 // so that a benchmark record can name the kernels it timed (the reference tags every saved result with the git
 // commit: @tagsave, scripts/run_benchmarks_gpsl1.jl:24-27).  A product build reports "flags:none"; development
-// builds (-DGAT_DEV: environment knobs, diagnostic kernels that compute wrong results on purpose) name theirs.
+// builds (-DGAT_DEV: environment knobs, -DGAT_DC_DEV: a reduced instance set) name theirs.
 #include "gat.h"
 
 #ifndef GAT_GIT_SHA

@@ -119,7 +119,7 @@ GAT_API const char *gat_last_error(const gat_ctx *ctx);
 /* "libgat <version> (gfx950) git:<short commit of the kernel sources>[+dirty] flags:<-D flags beyond the product recipe | none>":
  * which library a result came from (the reference tags saved results with its commit: @tagsave,
  * scripts/run_benchmarks_gpsl1.jl:24-27).  A product build says "flags:none"; development builds (-DGAT_DEV: A/B knobs
- * from the environment, diagnostic kernels) name theirs. */
+ * from the environment, -DGAT_DC_DEV: a reduced instance set) name theirs. */
 GAT_API const char *gat_version(void);
 
 /* Device properties used for metadata (add_metadata!, src/benchmarks.jl:11-32: GPU_model, CUDA

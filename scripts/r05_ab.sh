@@ -3,7 +3,6 @@
 # profiles/r05/).  One series per call:  scripts/r05_ab.sh SERIES       (run through gpurun; builds are made on the CPU first)
 # Variant libraries: python -m gpuacceleratedtracking_amd.build --variant NAME -DGAT_DC_DEV [-D...]  -> build/libgat_NAME.so
 # (development builds: only the BASELINE shapes' instances; `base` = the current text without extra flags).
-#   ablate   base + -DGAT_DC_ABLATE={1,2,4,8,12,16,13,29} as abl1 ... abl29      what each part of the kernel costs (c2, i8)
 #   rule     base                                                                 where the two-channel 2 x 2 tile pays
 #   quads    base                                                                 quads / sign-bit tables on the two-channel tile
 #   k32      (product library)                                                    configs[3] as a whole on one GPU: tilings
@@ -16,9 +15,6 @@ series=$1; out=gpurun_out/r05/ab_$series.txt; : > $out
 q() { tag=$1; lib=$2; opts=$3; shift 3; QARGS="$opts" GAT_LIBRARY=${lib:+$PWD/$lib} bash scripts/r05_quick.sh $tag "$@" | tee -a $out; }
 B=build/libgat_base.so
 case $series in
-ablate)
-  L="base:$B"; for n in 1 2 4 8 12 16 13 29; do L="$L abl$n:build/libgat_abl$n.so"; done
-  bash scripts/r05_ablate.sh r05/ablate_c2.txt c2 $L; bash scripts/r05_ablate.sh r05/ablate_i8.txt i8 $L ;;
 rule)
   SH="c1k2 c1k3 c1k4 c1k5 c1k7 i16k8 ilk8 m8k4 m12k4 c2i16 lat12 lat4"
   for rep in 1 2; do q one_channel $B "--option dc_aw2=0" $SH; q two_channel $B "--option dc_aw2=1" $SH; done ;;
@@ -35,5 +31,5 @@ k32)
     q kt4 "" "" c3k32; q kt2 "" "--option dc_kt=2" c3k32; q kt1 "" "--option dc_kt=1" c3k32
     q split_bf16 "" "--matrix-core 3" c3k32; q two_by_two "" "--option dc_aw=2 --option dc_aw2=1" c3k32
   done ;;
-*) echo "series: ablate rule quads k32"; exit 2 ;;
+*) echo "series: rule quads k32"; exit 2 ;;
 esac

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Round 5, first GPU call: the whole -m gpu suite, the default bench line + the constellation leg, the ablation matrix of
-# configs[2] and of the int8 stream (what bounds them), extended SQ counters of configs[2].  Output: gpurun_out/r05/
+# Round 5, first GPU call: the whole -m gpu suite, the default bench line + the constellation leg, extended SQ counters of
+# configs[2].  Output: $OUT below.
 set -o pipefail
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/r05; mkdir -p $OUT
@@ -29,11 +29,6 @@ for f in ("bench_default", "bench_constellation"):
         print("  constellation:", c["workload"], "| ms/step", c["ms_per_step"], "RTF", c["real_time_factor"], "step_ms", c["step_ms"],
               "launch", c["launch"], "frac", c["roofline"]["frac"], c["roofline"]["bound"], "hbm_frac", c["roofline"]["hbm_frac"], "err", c["parity_max_rel_err_vs_f64_oracle"])
 PY
-fi
-if [ "$PART" = "all" ] || [ "$PART" = "ablate" ]; then
-  LIBS="base:build/libgat_base.so abl1:build/libgat_abl1.so abl2:build/libgat_abl2.so abl4:build/libgat_abl4.so abl8:build/libgat_abl8.so abl12:build/libgat_abl12.so abl16:build/libgat_abl16.so abl13:build/libgat_abl13.so abl29:build/libgat_abl29.so"
-  bash scripts/r05_ablate.sh r05/ablate_c2.txt c2 $LIBS
-  bash scripts/r05_ablate.sh r05/ablate_i8.txt i8 $LIBS
 fi
 if [ "$PART" = "all" ] || [ "$PART" = "pmc" ]; then
   rocprofv3 -L > $OUT/counters_available.txt 2>&1 || true
