@@ -23,6 +23,9 @@ SAMPLE_BYTES = {0: 8, 1: 8, 2: 4, 3: 2}
 GAT_MAX_TAPS = 32
 # kernel selection (gat_set_matrix_core)
 GAT_MC_VECTOR, GAT_MC_AUTO, GAT_MC_F32, GAT_MC_BF16_SPLIT = 0, 1, 2, 3
+# antenna-array processing (gat_array_weights modes; the array functions' antenna limit)
+GAT_BF_CONVENTIONAL, GAT_BF_MVDR, GAT_BF_POWER_INVERSION = 0, 1, 2
+GAT_MAX_ARRAY_ANTS = 64
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -43,6 +46,9 @@ EXPORTS = [
     "gat_timer_lap", "gat_timer_laps", "gat_debug_read_stream", "gat_gen_code_replica_texaddr",
     # acquisition: the PRN x Doppler x code-phase search that seeds the tracking loops
     "gat_acquire", "gat_acq_stats_host",
+    # antenna-array processing: spatial covariance, beamformer weights, beamformed accumulators and loop
+    "gat_spatial_covariance", "gat_array_weights", "gat_array_weights_host", "gat_beamform", "gat_tracking_update_weighted",
+    "gat_tracking_update_host_weighted", "gat_tracking_run_weighted",
 ]
 
 
@@ -215,6 +221,14 @@ def load(build_if_missing: bool = True):
         "gat_gen_code_replica_texaddr": (i32, [vp, vp, i64, i32, dbl, dbl, dbl, i64, i32, i32]),
         "gat_acquire": (i32, [vp, sp, i32, i32p, i32, dbl, C.POINTER(AcqConfig), vp, vp]),
         "gat_acq_stats_host": (i32, [vp, i32, i32, i32, C.POINTER(AcqConfig), dbl, i64, vp]),
+        "gat_spatial_covariance": (i32, [vp, sp, i32, i32, vp, vp]),
+        "gat_array_weights": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, dbl, vp, vp]),
+        "gat_array_weights_host": (i32, [vp, vp, i32, vp, vp, i32, i32, dbl, vp, vp]),
+        "gat_beamform": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
+        "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
+        "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,
+                                            C.POINTER(LoopConfig), vp, vp, vp, vp, vp, i64, C.c_uint32, C.POINTER(C.c_int32), vp, vp]),
     }
     assert sorted(sigs) == sorted(EXPORTS)
     for name, (res, args) in sigs.items():

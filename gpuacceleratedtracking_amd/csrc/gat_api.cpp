@@ -105,10 +105,12 @@ int32_t upload_params(gat_ctx *c, const gat_channel_params *params_host, size_t 
 
 namespace {
 
+// `update`: the loop's update step for one block's accumulators (gat_tracking_update, or a weighted one handed in by
+// gat_array_api.cpp: this file names no launcher of the array kernels)
 int32_t tracking_run_enqueue(gat_ctx *c, const gat_signal_desc *sig, int32_t num_blocks, int32_t K, int32_t L,
-                             const int32_t *shifts, double fs, const gat_loop_config *cfg, gat_loop_state *state,
-                             gat_channel_params *params_a, gat_channel_params *params_b, float *acc_re, float *acc_im,
-                             int64_t acc_block_stride, uint32_t flags, int32_t *current_is_b)
+                             const int32_t *shifts, double fs, gat_channel_params *params_a, gat_channel_params *params_b,
+                             float *acc_re, float *acc_im, int64_t acc_block_stride, uint32_t flags, int32_t *current_is_b,
+                             const LoopUpdateFn &update)
 {
     const size_t sample_bytes = sig->layout == GAT_LAYOUT_PLANAR ? 4 : sig->layout == GAT_LAYOUT_INTERLEAVED ? 8
                               : sig->layout == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 2;
@@ -121,7 +123,7 @@ int32_t tracking_run_enqueue(gat_ctx *c, const gat_signal_desc *sig, int32_t num
         float *o_re = acc_re + (size_t)b * (size_t)acc_block_stride, *o_im = acc_im + (size_t)b * (size_t)acc_block_stride;
         int32_t rc = correlate_impl(c, &d, cur, 1, K, L, shifts, fs, o_re, o_im, flags);
         if (rc != GAT_OK) return rc;
-        rc = gat_tracking_update(c, o_re, o_im, K, sig->num_ants, cfg, state, cur, nxt);
+        rc = update(o_re, o_im, cur, nxt);
         if (rc != GAT_OK) return rc;
         std::swap(cur, nxt);
     }
@@ -260,6 +262,55 @@ int32_t set_option(gat_ctx *c, const char *name, long long v)
 }
 
 } // namespace
+
+namespace gat {
+
+// gat_tracking_run and gat_tracking_run_weighted (gat_array_api.cpp): validation, the eager sequence, the graph cache
+int32_t tracking_run_shared(gat_ctx *c, const gat_signal_desc *sig, int32_t num_blocks, int32_t K, int32_t L, const int32_t *shifts,
+                            double fs, const gat_loop_config *cfg, gat_loop_state *state, gat_channel_params *params_a,
+                            gat_channel_params *params_b, float *acc_re, float *acc_im, int64_t acc_block_stride, uint32_t flags,
+                            int32_t *current_is_b, const double *w_re, const double *w_im, const LoopUpdateFn &update)
+{
+    if (!c || !sig || !shifts || !cfg || !state || !params_a || !params_b || !acc_re || !acc_im)
+        return fail(c, GAT_ERR_ARG, "null argument");
+    if (num_blocks < 1 || acc_block_stride < 0) return fail(c, GAT_ERR_ARG, "bad block count / stride");
+    if (cfg->num_taps != L || L < 1 || L > GAT_MAX_TAPS) return fail(c, GAT_ERR_ARG, "loop configuration and tap list disagree");
+    if (flags & ~(GAT_FLAG_ATOMIC | GAT_FLAG_GRAPH)) return fail(c, GAT_ERR_ARG, "unknown flag bits");
+    GAT_HIP(c, hipSetDevice(c->device));
+    const TraceRange trace("gat_tracking_run");
+    const uint32_t kflags = flags & ~GAT_FLAG_GRAPH;
+    if (!(flags & GAT_FLAG_GRAPH))
+        return tracking_run_enqueue(c, sig, num_blocks, K, L, shifts, fs, params_a, params_b, acc_re, acc_im, acc_block_stride, kflags,
+                                    current_is_b, update);
+
+    // hipGraph path: the 2-3 launches per block are too short to hide their launch gaps.  Every argument that
+    // shapes the launch sequence is part of the key -- field by field (struct padding of a C caller is not
+    // initialised) --, together with the library-owned pointers and sizes the recorded launches bake in; a call with
+    // a known key replays its instantiated graph.  Up to kMaxLoopGraphs graphs are kept (least recently used goes).
+    auto make_key = [&]() {
+        std::vector<unsigned char> key;
+        key_put(key, sig->re); key_put(key, sig->im); key_put(key, sig->layout); key_put(key, sig->num_ants);
+        key_put(key, sig->num_samples); key_put(key, sig->ant_stride); key_put(key, sig->block_stride);
+        key_put(key, sig->chan_stride); key_put(key, num_blocks); key_put(key, K); key_put(key, L); key_put(key, fs);
+        key_put(key, cfg->block_seconds); key_put(key, cfg->pll_bandwidth_hz); key_put(key, cfg->dll_bandwidth_hz);
+        key_put(key, cfg->code_freq_nominal_hz); key_put(key, cfg->carrier_center_hz); key_put(key, cfg->if_hz);
+        key_put(key, cfg->early_late_spacing_chips); key_put(key, cfg->code_length); key_put(key, cfg->num_taps);
+        key_put(key, cfg->early_index); key_put(key, cfg->prompt_index); key_put(key, cfg->late_index);
+        key_put(key, state); key_put(key, params_a); key_put(key, params_b); key_put(key, acc_re); key_put(key, acc_im);
+        key_put(key, acc_block_stride); key_put(key, kflags); key_put(key, (int)1 /* sequence: tracking run */);
+        key_put(key, w_re); key_put(key, w_im); // the recorded update launches read these (null: the unweighted run)
+        key_put_ctx(key, c);
+        for (int l = 0; l < L; ++l) key_put(key, shifts[l]);
+        return key;
+    };
+    if (current_is_b) *current_is_b = (num_blocks & 1) ? 1 : 0; // the buffers swap once per block
+    return graph_replay_or_record(c, make_key, [&]() {
+        return tracking_run_enqueue(c, sig, num_blocks, K, L, shifts, fs, params_a, params_b, acc_re, acc_im, acc_block_stride, kflags,
+                                    nullptr, update);
+    });
+}
+
+} // namespace gat
 
 extern "C" {
 
@@ -706,42 +757,12 @@ GAT_API int32_t gat_tracking_run(gat_ctx *c, const gat_signal_desc *sig, int32_t
                                  gat_channel_params *params_a, gat_channel_params *params_b, float *acc_re,
                                  float *acc_im, int64_t acc_block_stride, uint32_t flags, int32_t *current_is_b)
 {
-    if (!c || !sig || !shifts || !cfg || !state || !params_a || !params_b || !acc_re || !acc_im)
-        return fail(c, GAT_ERR_ARG, "null argument");
-    if (num_blocks < 1 || acc_block_stride < 0) return fail(c, GAT_ERR_ARG, "bad block count / stride");
-    if (cfg->num_taps != L || L < 1 || L > GAT_MAX_TAPS) return fail(c, GAT_ERR_ARG, "loop configuration and tap list disagree");
-    if (flags & ~(GAT_FLAG_ATOMIC | GAT_FLAG_GRAPH)) return fail(c, GAT_ERR_ARG, "unknown flag bits");
-    GAT_HIP(c, hipSetDevice(c->device));
-    const TraceRange trace("gat_tracking_run");
-    const uint32_t kflags = flags & ~GAT_FLAG_GRAPH;
-    if (!(flags & GAT_FLAG_GRAPH))
-        return tracking_run_enqueue(c, sig, num_blocks, K, L, shifts, fs, cfg, state, params_a, params_b, acc_re, acc_im,
-                                    acc_block_stride, kflags, current_is_b);
-
-    // hipGraph path: the 2-3 launches per block are too short to hide their launch gaps.  Every argument that
-    // shapes the launch sequence is part of the key -- field by field (struct padding of a C caller is not
-    // initialised) --, together with the library-owned pointers and sizes the recorded launches bake in; a call with
-    // a known key replays its instantiated graph.  Up to kMaxLoopGraphs graphs are kept (least recently used goes).
-    auto make_key = [&]() {
-        std::vector<unsigned char> key;
-        key_put(key, sig->re); key_put(key, sig->im); key_put(key, sig->layout); key_put(key, sig->num_ants);
-        key_put(key, sig->num_samples); key_put(key, sig->ant_stride); key_put(key, sig->block_stride);
-        key_put(key, sig->chan_stride); key_put(key, num_blocks); key_put(key, K); key_put(key, L); key_put(key, fs);
-        key_put(key, cfg->block_seconds); key_put(key, cfg->pll_bandwidth_hz); key_put(key, cfg->dll_bandwidth_hz);
-        key_put(key, cfg->code_freq_nominal_hz); key_put(key, cfg->carrier_center_hz); key_put(key, cfg->if_hz);
-        key_put(key, cfg->early_late_spacing_chips); key_put(key, cfg->code_length); key_put(key, cfg->num_taps);
-        key_put(key, cfg->early_index); key_put(key, cfg->prompt_index); key_put(key, cfg->late_index);
-        key_put(key, state); key_put(key, params_a); key_put(key, params_b); key_put(key, acc_re); key_put(key, acc_im);
-        key_put(key, acc_block_stride); key_put(key, kflags); key_put(key, (int)1 /* sequence: tracking run */);
-        key_put_ctx(key, c);
-        for (int l = 0; l < L; ++l) key_put(key, shifts[l]);
-        return key;
-    };
-    if (current_is_b) *current_is_b = (num_blocks & 1) ? 1 : 0; // the buffers swap once per block
-    return graph_replay_or_record(c, make_key, [&]() {
-        return tracking_run_enqueue(c, sig, num_blocks, K, L, shifts, fs, cfg, state, params_a, params_b, acc_re, acc_im,
-                                    acc_block_stride, kflags, nullptr);
-    });
+    if (!c || !sig || !cfg || !state) return fail(c, GAT_ERR_ARG, "null argument");
+    return tracking_run_shared(c, sig, num_blocks, K, L, shifts, fs, cfg, state, params_a, params_b, acc_re, acc_im, acc_block_stride,
+                               flags, current_is_b, nullptr, nullptr,
+                               [&](const float *o_re, const float *o_im, const gat_channel_params *cur, gat_channel_params *nxt) {
+                                   return gat_tracking_update(c, o_re, o_im, K, sig->num_ants, cfg, state, cur, nxt);
+                               });
 }
 
 GAT_API int32_t gat_malloc(gat_ctx *c, size_t bytes, void **out)

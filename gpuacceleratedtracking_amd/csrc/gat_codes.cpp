@@ -1,4 +1,5 @@
-// gat_codes.cpp -- host-side PRN code generators behind gat_gen_codes (include/gat.h).
+// gat_codes.cpp -- host-side PRN code generators behind gat_gen_codes (include/gat.h), and the host-only twins of device
+// entry points (the loop update, the beamformer weights): nothing here touches a kernel launcher.
 //
 // Stand-in for GNSSSignals.GPSL1() / GPSL5() `system.codes` (reference: src/benchmarks.jl:93,
 // src/GPUAcceleratedTracking.jl:39-42; GNSSSignals.jl itself is an un-vendored dependency).
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "gat.h"
+#include "gat_array.h"
 #include "gat_loop.h"
 
 namespace {
@@ -125,5 +127,60 @@ extern "C" GAT_API int32_t gat_tracking_update_host(const float *acc_re_host, co
         gat::loop_update_channel(acc_re_host, acc_im_host, k, num_ants, *config, state_host[k], cur_host[k], n);
         next_host[k] = n;
     }
+    return GAT_OK;
+}
+
+// The weighted update on the HOST: gat_tracking_update_host with the antenna sum replaced by sum_m conj(w[k][m]) * R[m, tap]
+// (w: host double [K][M]).  Both weight pointers NULL: the unweighted call itself.
+extern "C" GAT_API int32_t gat_tracking_update_host_weighted(const float *acc_re_host, const float *acc_im_host, int32_t num_channels,
+                                                             int32_t num_ants, const gat_loop_config *config, gat_loop_state *state_host,
+                                                             const gat_channel_params *cur_host, gat_channel_params *next_host,
+                                                             const double *w_re_host, const double *w_im_host)
+{
+    if (!w_re_host && !w_im_host)
+        return gat_tracking_update_host(acc_re_host, acc_im_host, num_channels, num_ants, config, state_host, cur_host, next_host);
+    if (!w_re_host || !w_im_host) return GAT_ERR_ARG;
+    if (!acc_re_host || !acc_im_host || !config || !state_host || !cur_host || !next_host) return GAT_ERR_ARG;
+    if (num_channels < 1 || num_ants < 1) return GAT_ERR_ARG;
+    const int L = config->num_taps;
+    if (L < 1 || L > GAT_MAX_TAPS || config->early_index < 0 || config->early_index >= L || config->prompt_index < 0 || config->prompt_index >= L ||
+        config->late_index < 0 || config->late_index >= L || config->code_length < 1 || !(config->block_seconds > 0.0))
+        return GAT_ERR_RANGE;
+    for (int k = 0; k < num_channels; ++k) {
+        gat_channel_params n;
+        gat::loop_update_channel(acc_re_host, acc_im_host, k, num_ants, *config, state_host[k], cur_host[k], n, w_re_host, w_im_host);
+        next_host[k] = n;
+    }
+    return GAT_OK;
+}
+
+// Beamformer weights on the HOST: the arithmetic of gat_array_weights (the same text, gat_array.h).  A covariance that is not
+// positive definite, or a steering vector of zeros: GAT_ERR_RANGE (the device entry point answers those with NaN weights).
+extern "C" GAT_API int32_t gat_array_weights_host(const float *cov_re, const float *cov_im, int32_t M, const double *steer_re, const double *steer_im,
+                                                  int32_t K, int32_t mode, double loading, double *w_re, double *w_im)
+{
+    if (!w_re || !w_im || K < 1 || M < 1) return GAT_ERR_ARG;
+    if (mode != GAT_BF_CONVENTIONAL && mode != GAT_BF_MVDR && mode != GAT_BF_POWER_INVERSION) return GAT_ERR_ARG;
+    if (mode != GAT_BF_POWER_INVERSION && (!steer_re || !steer_im)) return GAT_ERR_ARG;
+    if (mode != GAT_BF_CONVENTIONAL && (!cov_re || !cov_im)) return GAT_ERR_ARG;
+    if (!(loading >= 0.0) || !std::isfinite(loading)) return GAT_ERR_ARG;
+    if (M > GAT_MAX_ARRAY_ANTS) return GAT_ERR_RANGE;
+    if (mode == GAT_BF_CONVENTIONAL) {
+        for (int k = 0; k < K; ++k)
+            if (!gat::array_conventional_weights(M, steer_re + (size_t)k * M, steer_im + (size_t)k * M, w_re + (size_t)k * M, w_im + (size_t)k * M))
+                return GAT_ERR_RANGE;
+        return GAT_OK;
+    }
+    std::vector<double> l_re((size_t)M * M, 0.0), l_im((size_t)M * M, 0.0), z_re((size_t)M), z_im((size_t)M);
+    const double load = gat::array_loading_term(cov_re, M, loading);
+    for (int j = 0; j < M; ++j) {
+        if (!gat::array_chol_diag(cov_re, load, l_re.data(), l_im.data(), M, j)) return GAT_ERR_RANGE;
+        for (int i = j + 1; i < M; ++i) gat::array_chol_offdiag(cov_re, cov_im, l_re.data(), l_im.data(), M, i, j);
+    }
+    const bool pi = mode == GAT_BF_POWER_INVERSION;
+    for (int k = 0; k < K; ++k)
+        if (!gat::array_solve_weights(l_re.data(), l_im.data(), M, pi ? nullptr : steer_re + (size_t)k * M, pi ? nullptr : steer_im + (size_t)k * M,
+                                      z_re.data(), z_im.data(), w_re + (size_t)k * M, w_im + (size_t)k * M))
+            return GAT_ERR_RANGE;
     return GAT_OK;
 }

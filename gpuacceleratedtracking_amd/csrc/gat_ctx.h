@@ -3,6 +3,7 @@
 #pragma once
 
 #include <cmath>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -139,6 +140,15 @@ struct TraceRange {
 void drop_loop_graphs(gat_ctx *c);
 int32_t ensure_partial(gat_ctx *c, size_t bytes);
 int32_t upload_params(gat_ctx *c, const gat_channel_params *params_host, size_t n);
+
+// The closed loop's native run (gat_api.cpp), shared by gat_tracking_run and gat_tracking_run_weighted (gat_array_api.cpp):
+// `update` enqueues the loop's update step for one block's accumulators and parameter pair; w_re / w_im (null: the
+// unweighted run) are what that step reads besides, and belong to the key of a recorded graph.
+using LoopUpdateFn = std::function<int32_t(const float *acc_re, const float *acc_im, const gat_channel_params *cur, gat_channel_params *next)>;
+int32_t tracking_run_shared(gat_ctx *c, const gat_signal_desc *sig, int32_t num_blocks, int32_t K, int32_t L, const int32_t *shifts,
+                            double fs, const gat_loop_config *cfg, gat_loop_state *state, gat_channel_params *params_a,
+                            gat_channel_params *params_b, float *acc_re, float *acc_im, int64_t acc_block_stride, uint32_t flags,
+                            int32_t *current_is_b, const double *w_re, const double *w_im, const LoopUpdateFn &update);
 
 // What planning returns: GAT_OK, or a refusal's code and message (the caller reports it with fail()).
 struct Refusal {

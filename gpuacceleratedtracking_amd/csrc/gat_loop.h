@@ -18,13 +18,24 @@
 namespace gat {
 
 // acc_re / acc_im: [K][L][M] of ONE block; k: the channel; st / cur: its loop state and this block's parameters; returns the
-// next block's parameters in `next`
+// next block's parameters in `next`.  w_re / w_im: beamformer weights [K][M] (gat_array.h), or both null: the plain sum over
+// identical antennas.  With weights a tap is sum_m conj(w[k][m]) * acc[k][tap][m].
 GAT_HD inline void loop_update_channel(const float *acc_re, const float *acc_im, int k, int M, const gat_loop_config &cfg, gat_loop_state &st,
-                                       const gat_channel_params &c, gat_channel_params &next)
+                                       const gat_channel_params &c, gat_channel_params &next, const double *w_re = nullptr,
+                                       const double *w_im = nullptr)
 {
     const int L = cfg.num_taps;
     auto tap = [&](int l, double &re, double &im) {
         re = im = 0.0;
+        if (w_re && w_im) {
+            for (int m = 0; m < M; ++m) {
+                const size_t o = ((size_t)k * L + l) * M + m;
+                const double ar = (double)acc_re[o], ai = (double)acc_im[o], wr = w_re[(size_t)k * M + m], wi = w_im[(size_t)k * M + m];
+                re += wr * ar + wi * ai;
+                im += wr * ai - wi * ar;
+            }
+            return;
+        }
         for (int m = 0; m < M; ++m) {
             const size_t o = ((size_t)k * L + l) * M + m;
             re += (double)acc_re[o];

@@ -2,7 +2,9 @@
 ``track`` provides and the reference only touches to borrow buffers (``TrackingState``,
 src/benchmarks.jl:54-61).  One ``TrackingLoop.step`` = one fused correlate launch for K channels
 on one integration block + one ``gat_tracking_update`` launch that turns the accumulators into
-the next block's parameters ON THE DEVICE (ping-pong parameter buffers, no host round trip)."""
+the next block's parameters ON THE DEVICE (ping-pong parameter buffers, no host round trip).  With beamformer
+weights (``TrackingLoop(weights=w)``, ``array.beamformer_weights``) the update forms prompt, early and late as
+``sum_m conj(w[k, m]) R[m, tap]`` instead of the plain sum over antennas."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,7 +23,7 @@ class TrackingLoop:
     def __init__(self, system: GNSSSystem, prns, num_samples: int, num_ants: int, sampling_frequency: float,
                  correlator_sample_shifts, init_carrier_doppler, init_code_phase, if_hz: float = 0.0,
                  carrier_center_hz: float = 1575.42e6, pll_bandwidth_hz: float = 18.0, dll_bandwidth_hz: float = 1.0,
-                 init_carrier_phase=0.0, device=None, ctx: Context | None = None):
+                 init_carrier_phase=0.0, device=None, ctx: Context | None = None, weights=None):
         self.ctx = ctx if ctx is not None else get_context(device)
         self.ctx.set_codes(system.codes)
         self.system = system
@@ -57,6 +59,31 @@ class TrackingLoop:
         self.out_re = torch.empty((1, self.K, self.L, self.M), dtype=torch.float32, device=dev)
         self.out_im = torch.empty_like(self.out_re)
         self.blocks_done = 0
+        self._w_re = self._w_im = None
+        self.set_weights(weights)
+
+    def set_weights(self, weights):
+        """Beamformer weights complex [K, M] (``array.beamformer_weights``; a tensor or an array), or None: prompt, early and
+        late become ``sum_m conj(w[k, m]) R[m, tap]`` instead of the plain sum over antennas.  The values are copied into
+        buffers the loop keeps, so a graph recorded by ``run(graph=True)`` sees later weights too."""
+        if weights is None:
+            self._w_re = self._w_im = None
+            return
+        w = torch.as_tensor(weights).to(self.ctx.device)
+        if tuple(w.shape) != (self.K, self.M):
+            raise ValueError(f"weights must be [K, M] = [{self.K}, {self.M}]")
+        w_re = (w.real if w.is_complex() else w).to(torch.float64)
+        w_im = w.imag.to(torch.float64) if w.is_complex() else torch.zeros_like(w_re)
+        if self._w_re is None:
+            self._w_re, self._w_im = w_re.contiguous().clone(), w_im.contiguous().clone()
+        else:
+            self._w_re.copy_(w_re)
+            self._w_im.copy_(w_im)
+
+    def _weight_ptrs(self):
+        if self._w_re is None:
+            return None, None
+        return C.c_void_p(self._w_re.data_ptr()), C.c_void_p(self._w_im.data_ptr())
 
     def step(self, re: torch.Tensor, im: torch.Tensor | None = None, start: int = 0):
         """Correlate the block starting at sample ``start`` of the given signal with the current
@@ -65,11 +92,12 @@ class TrackingLoop:
         desc = _signal_desc(re, im, self.N, start=start)
         cur, nxt = self._params[self._cur], self._params[1 - self._cur]
         self.ctx.downconvert_and_correlate(desc, cur, 1, self.K, self.shifts, self.fs, self.out_re, self.out_im)
-        rc = self.ctx.lib.gat_tracking_update(self.ctx._h, C.c_void_p(self.out_re.data_ptr()),
-                                              C.c_void_p(self.out_im.data_ptr()), self.K, self.M,
-                                              C.byref(self.config), C.c_void_p(self._state.data_ptr()),
-                                              C.c_void_p(cur.data_ptr()), C.c_void_p(nxt.data_ptr()))
-        self.ctx.check(rc, "gat_tracking_update")
+        args = (self.ctx._h, C.c_void_p(self.out_re.data_ptr()), C.c_void_p(self.out_im.data_ptr()), self.K, self.M,
+                C.byref(self.config), C.c_void_p(self._state.data_ptr()), C.c_void_p(cur.data_ptr()), C.c_void_p(nxt.data_ptr()))
+        if self._w_re is None:
+            self.ctx.check(self.ctx.lib.gat_tracking_update(*args), "gat_tracking_update")
+        else:
+            self.ctx.check(self.ctx.lib.gat_tracking_update_weighted(*args, *self._weight_ptrs()), "gat_tracking_update_weighted")
         self._cur = 1 - self._cur
         self.blocks_done += 1
 
@@ -98,14 +126,14 @@ class TrackingLoop:
             acc_re, acc_im, stride = self.out_re, self.out_im, 0
         a, b = self._params[self._cur], self._params[1 - self._cur]
         is_b = C.c_int32(0)
-        rc = self.ctx.lib.gat_tracking_run(self.ctx._h, C.byref(desc), nb, self.K, self.L,
-                                           self.shifts.ctypes.data_as(C.POINTER(C.c_int32)), self.fs,
-                                           C.byref(self.config), C.c_void_p(self._state.data_ptr()),
-                                           C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
-                                           C.c_void_p(acc_re.data_ptr()), C.c_void_p(acc_im.data_ptr()), stride,
-                                           _lib.GAT_FLAG_GRAPH if graph else 0,
-                                           C.byref(is_b))
-        self.ctx.check(rc, "gat_tracking_run")
+        args = (self.ctx._h, C.byref(desc), nb, self.K, self.L, self.shifts.ctypes.data_as(C.POINTER(C.c_int32)), self.fs,
+                C.byref(self.config), C.c_void_p(self._state.data_ptr()), C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
+                C.c_void_p(acc_re.data_ptr()), C.c_void_p(acc_im.data_ptr()), stride, _lib.GAT_FLAG_GRAPH if graph else 0,
+                C.byref(is_b))
+        if self._w_re is None:
+            self.ctx.check(self.ctx.lib.gat_tracking_run(*args), "gat_tracking_run")
+        else:
+            self.ctx.check(self.ctx.lib.gat_tracking_run_weighted(*args, *self._weight_ptrs()), "gat_tracking_run_weighted")
         if is_b.value:
             self._cur = 1 - self._cur
         self.blocks_done += nb

@@ -279,7 +279,8 @@ GAT_API int32_t gat_reduce_cplx_multi(gat_ctx *ctx, const float *in_re_dev, cons
  * the accumulators of the block just correlated into the parameters of the next block, ON THE
  * DEVICE, so a receiver loop is {correlate, update} with no host round trip.  Textbook loop
  * (Kaplan & Hegarty ch. 5; the same structure Tracking.jl uses):
- *   prompt/early/late = sum over antennas of R[m, tap]                      (identical antennas)
+ *   prompt/early/late = sum over antennas of R[m, tap]                      (identical antennas;
+ *                       the *_weighted entry points below form sum_m conj(w_m) R[m, tap] instead)
  *   PLL: Costas arctan discriminator atan(Q/I)/2pi [cycles] -> 3rd-order bilinear loop filter
  *   DLL: (2-d)/2 * (|L|-|E|)/(|E|+|L|) [chips], d = E-L spacing in chips -> 2nd-order bilinear
  *        filter, carrier aided (code_doppler += carrier_doppler * code_freq / carrier_center)
@@ -603,6 +604,73 @@ GAT_API int32_t gat_acquire(gat_ctx *ctx, const gat_signal_desc *signal, int32_t
 GAT_API int32_t gat_acq_stats_host(const float *power_host, int32_t num_prns, int32_t num_doppler_bins, int32_t num_code_bins,
                                    const gat_acq_config *config, double sampling_freq_hz, int64_t num_samples,
                                    gat_acq_result *results_host);
+
+/* ---- antenna-array processing: spatial covariance, beamformer weights, beamformed accumulators and loop -------------
+ * The correlators return accumulators per antenna; what an array receiver does with its antennas happens here.
+ * Correlation is linear -- w^H (sum_n x_n c_n) = sum_n (w^H x_n) c_n -- so a beam or a null is applied to the
+ * accumulators the correlators already produce: one pass over the raw samples estimates the spatial covariance, a small
+ * FP64 solver turns it into weights, and the weights enter where the loop forms its antenna sum.  The reference has no
+ * counterpart (its antennas are identical and only summed). */
+#define GAT_MAX_ARRAY_ANTS 64    /* antennas of the array functions                                            */
+#define GAT_BF_CONVENTIONAL 0    /* w = a / (a^H a)                                                            */
+#define GAT_BF_MVDR 1            /* w = R'^-1 a / (a^H R'^-1 a)                                                */
+#define GAT_BF_POWER_INVERSION 2 /* w = R'^-1 e0 / (e0^H R'^-1 e0): no steering vector, antenna 0 is the reference */
+
+/* Spatial covariance of the raw samples, one estimate per blocks_per_estimate consecutive blocks (the last estimate
+ * takes what is left): E = ceil(num_blocks / blocks_per_estimate),
+ *   R_e[i][j] = sum_{b in e} sum_{n<N} x[n,i,b] * conj(x[n,j,b])                      (a plain sum, not a mean)
+ * cov_re/cov_im: dev float [E][M][M] planar.  Every sample layout, 1 <= M <= GAT_MAX_ARRAY_ANTS (else GAT_ERR_RANGE),
+ * any N, base alignment and strides; chan_stride must be 0 (GAT_ERR_UNSUPPORTED).  M <= 8 with every block of every
+ * antenna starting on a 16-byte boundary (the correlator's fast-path rule) streams the samples once with 16-byte loads
+ * and keeps the upper triangle in registers; everything else is staged through LDS and tiled over the upper triangle.
+ * The result is exactly Hermitian (only the upper triangle is computed; the mirror is its conjugate, the diagonal's
+ * imaginary part is +0) and deterministic (workgroups write partial sums to slices of the context's scratch, a second
+ * kernel adds them in a fixed order; no float atomics).  Sums are float32 in two levels; integer samples whose sums stay
+ * below 2^24 (int8 pairs up to N = 256) come back exact. */
+GAT_API int32_t gat_spatial_covariance(gat_ctx *ctx, const gat_signal_desc *signal, int32_t num_blocks,
+                                       int32_t blocks_per_estimate, float *cov_re_dev, float *cov_im_dev);
+
+/* Beamformer weights w [K][M] (planar, FP64) from ONE covariance [M][M] (planar float32, as gat_spatial_covariance
+ * writes it; the lower triangle and the diagonal's real part are read) and K steering vectors a [K][M] (planar, FP64),
+ * by `mode` (GAT_BF_*).  Diagonal loading: R' = R + loading * trace(R) / M * I, loading >= 0.  FP64 Cholesky R' = L L^H
+ * (done once, shared by the K channels) and two triangular solves per channel.  GAT_BF_CONVENTIONAL reads no covariance
+ * (cov_* may be NULL); GAT_BF_POWER_INVERSION reads no steering vector (steer_* may be NULL) and gives every channel the
+ * same weights.  A covariance that is not positive definite (or a steering vector of zeros): NaN weights from the device
+ * entry point -- the convention of bad channel records --, GAT_ERR_RANGE from the host one. */
+GAT_API int32_t gat_array_weights(gat_ctx *ctx, const float *cov_re_dev, const float *cov_im_dev, int32_t num_ants,
+                                  const double *steer_re_dev, const double *steer_im_dev, int32_t num_channels,
+                                  int32_t mode, double loading, double *w_re_dev, double *w_im_dev);
+/* The same arithmetic on the HOST (csrc/gat_array.h, shared with the device); all pointers are host memory.  Needs no
+ * context and no device. */
+GAT_API int32_t gat_array_weights_host(const float *cov_re_host, const float *cov_im_host, int32_t num_ants,
+                                       const double *steer_re_host, const double *steer_im_host, int32_t num_channels,
+                                       int32_t mode, double loading, double *w_re_host, double *w_im_host);
+
+/* Beamformed accumulators: y[b][k][l] = sum_m conj(w[k][m]) * acc[b][k][l][m].  acc: dev float [B][K][L][M] (what the
+ * correlators write), w: dev double [K][M] planar, out: dev float [B][K][L] planar. */
+GAT_API int32_t gat_beamform(gat_ctx *ctx, const float *acc_re_dev, const float *acc_im_dev, int32_t num_blocks,
+                             int32_t num_channels, int32_t num_taps, int32_t num_ants, const double *w_re_dev,
+                             const double *w_im_dev, float *out_re_dev, float *out_im_dev);
+
+/* gat_tracking_update / gat_tracking_update_host / gat_tracking_run with the antenna sum of prompt, early and late
+ * replaced by sum_m conj(w[k][m]) * R[m, tap]; w: double [K][M] planar (device memory for the device entry points, host
+ * memory for the host one).  w_re = w_im = NULL is the unweighted call: the same code path and the same bits.  The
+ * graph cache of gat_tracking_run is shared (the weight pointers are part of a recorded sequence's key). */
+GAT_API int32_t gat_tracking_update_weighted(gat_ctx *ctx, const float *acc_re_dev, const float *acc_im_dev,
+                                             int32_t num_channels, int32_t num_ants, const gat_loop_config *config_host,
+                                             gat_loop_state *state_dev, const gat_channel_params *cur_dev,
+                                             gat_channel_params *next_dev, const double *w_re_dev, const double *w_im_dev);
+GAT_API int32_t gat_tracking_update_host_weighted(const float *acc_re_host, const float *acc_im_host, int32_t num_channels,
+                                                  int32_t num_ants, const gat_loop_config *config_host,
+                                                  gat_loop_state *state_host, const gat_channel_params *cur_host,
+                                                  gat_channel_params *next_host, const double *w_re_host,
+                                                  const double *w_im_host);
+GAT_API int32_t gat_tracking_run_weighted(gat_ctx *ctx, const gat_signal_desc *sig, int32_t num_blocks, int32_t num_channels,
+                                          int32_t num_taps, const int32_t *shifts_host, double sampling_freq_hz,
+                                          const gat_loop_config *config_host, gat_loop_state *state_dev,
+                                          gat_channel_params *params_a_dev, gat_channel_params *params_b_dev,
+                                          float *acc_re_dev, float *acc_im_dev, int64_t acc_block_stride, uint32_t flags,
+                                          int32_t *current_is_b, const double *w_re_dev, const double *w_im_dev);
 
 #ifdef __cplusplus
 }

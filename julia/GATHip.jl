@@ -713,4 +713,67 @@ function acq_stats_host(power::Array{Float32,3}, cfg::AcqConfig, sampling_freque
     res
 end
 
+# ---- antenna-array processing (include/gat.h): spatial covariance of the raw samples, beamformer weights from it, the
+#      weights applied to accumulators and inside the loop's update.  Device pointers unless a name says host.
+const GAT_BF_CONVENTIONAL, GAT_BF_MVDR, GAT_BF_POWER_INVERSION = Int32(0), Int32(1), Int32(2)
+# cov_re / cov_im: device Float32 [M x M x E] (Julia's view of [E][M][M]), E = cld(num_blocks, blocks_per_estimate)
+function spatial_covariance!(ctx::Context, desc::SignalDesc, num_blocks::Integer, blocks_per_estimate::Integer, cov_re::Ptr{Cfloat},
+                             cov_im::Ptr{Cfloat})
+    check(ctx, ccall((:gat_spatial_covariance, libgat), Int32, (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Int32, Ptr{Cfloat}, Ptr{Cfloat}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), Int32(blocks_per_estimate), cov_re, cov_im))
+end
+# w [M x K] Float64 planes from one covariance and K steering vectors [M x K]
+function array_weights!(ctx::Context, cov_re::Ptr{Cfloat}, cov_im::Ptr{Cfloat}, num_ants::Integer, steer_re::Ptr{Float64},
+                        steer_im::Ptr{Float64}, num_channels::Integer, mode::Int32, loading::Float64, w_re::Ptr{Float64},
+                        w_im::Ptr{Float64})
+    check(ctx, ccall((:gat_array_weights, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}),
+                     ctx.handle, cov_re, cov_im, Int32(num_ants), steer_re, steer_im, Int32(num_channels), mode, loading, w_re, w_im))
+end
+# the same on the host: cov [M x M] planes, steering [M x K] planes (ignored for power inversion); returns ComplexF64 [M x K]
+function array_weights_host(cov_re::Matrix{Float32}, cov_im::Matrix{Float32}, steer_re::Matrix{Float64}, steer_im::Matrix{Float64},
+                            mode::Int32, loading::Float64 = 0.0)
+    M, K = size(cov_re, 1), size(steer_re, 2)
+    w_re, w_im = Matrix{Float64}(undef, M, K), Matrix{Float64}(undef, M, K)
+    rc = ccall((:gat_array_weights_host, libgat), Int32,
+               (Ptr{Cfloat}, Ptr{Cfloat}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}),
+               cov_re, cov_im, Int32(M), steer_re, steer_im, Int32(K), mode, loading, w_re, w_im)
+    rc == GAT_OK || throw(GatError(rc, "gat_array_weights_host"))
+    complex.(w_re, w_im)
+end
+# y [L x K x B] = sum_m conj(w[m, k]) acc[m, l, k, b]
+function beamform!(ctx::Context, acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, num_blocks::Integer, K::Integer, L::Integer, M::Integer,
+                   w_re::Ptr{Float64}, w_im::Ptr{Float64}, out_re::Ptr{Cfloat}, out_im::Ptr{Cfloat})
+    check(ctx, ccall((:gat_beamform, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Cfloat}, Ptr{Cfloat}),
+                     ctx.handle, acc_re, acc_im, Int32(num_blocks), Int32(K), Int32(L), Int32(M), w_re, w_im, out_re, out_im))
+end
+# tracking_update! / tracking_update_host! / tracking_run! with weights [M x K] (C_NULL planes: the unweighted calls)
+function tracking_update_weighted!(ctx::Context, acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, K::Integer, M::Integer, cfg::LoopConfig,
+                                   state_dev::Ptr{Cvoid}, cur_dev::Ptr{Cvoid}, next_dev::Ptr{Cvoid}, w_re::Ptr{Float64}, w_im::Ptr{Float64})
+    check(ctx, ccall((:gat_tracking_update_weighted, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}, Int32, Int32, Ref{LoopConfig}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64},
+                      Ptr{Float64}),
+                     ctx.handle, acc_re, acc_im, Int32(K), Int32(M), Ref(cfg), state_dev, cur_dev, next_dev, w_re, w_im))
+end
+tracking_update_host_weighted!(acc_re::Array{Float32}, acc_im::Array{Float32}, num_channels::Integer, num_ants::Integer, cfg::LoopConfig,
+                               state::Vector{LoopState}, cur::Vector{ChannelParams}, next::Vector{ChannelParams}, w_re::Matrix{Float64},
+                               w_im::Matrix{Float64}) =
+    ccall((:gat_tracking_update_host_weighted, libgat), Int32,
+          (Ptr{Cfloat}, Ptr{Cfloat}, Int32, Int32, Ref{LoopConfig}, Ptr{LoopState}, Ptr{ChannelParams}, Ptr{ChannelParams}, Ptr{Float64}, Ptr{Float64}),
+          acc_re, acc_im, Int32(num_channels), Int32(num_ants), Ref(cfg), state, cur, next, w_re, w_im) == GAT_OK ||
+    throw(GatError(Int32(1), "gat_tracking_update_host_weighted"))
+function tracking_run_weighted!(ctx::Context, desc::SignalDesc, num_blocks::Integer, K::Integer, shifts::Vector{Int32},
+                                sampling_frequency_hz::Float64, cfg::LoopConfig, state_dev::Ptr{Cvoid}, params_a_dev::Ptr{Cvoid},
+                                params_b_dev::Ptr{Cvoid}, acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, w_re::Ptr{Float64}, w_im::Ptr{Float64},
+                                acc_block_stride::Integer = 0, flags::UInt32 = UInt32(0))
+    cur_is_b = Ref{Int32}(0)
+    check(ctx, ccall((:gat_tracking_run_weighted, libgat), Int32,
+                     (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Int32, Int32, Ptr{Int32}, Float64, Ref{LoopConfig}, Ptr{Cvoid}, Ptr{Cvoid},
+                      Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, UInt32, Ref{Int32}, Ptr{Float64}, Ptr{Float64}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), Int32(K), Int32(length(shifts)), shifts, sampling_frequency_hz,
+                     Ref(cfg), state_dev, params_a_dev, params_b_dev, acc_re, acc_im, Int64(acc_block_stride), flags, cur_is_b, w_re, w_im))
+    cur_is_b[] != 0
+end
+
 end # module
