@@ -136,7 +136,7 @@ GAT_API int32_t gat_acquire(gat_ctx *c, const gat_signal_desc *sig, int32_t B, c
     const size_t off_part = off_pow + pow_bytes;
     const size_t bytes = off_part + (G > 1 ? (size_t)G * cells * sizeof(float) : 0) + (size_t)P * sizeof(int32_t);
     const size_t off_prn = bytes - (size_t)P * sizeof(int32_t);
-    GAT_HIP(c, hipSetDevice(c->device));
+    GAT_ENTER(c, "gat_acquire");
     {
         const int32_t rc = ensure_partial(c, bytes);
         if (rc != GAT_OK) return rc;
@@ -145,8 +145,6 @@ GAT_API int32_t gat_acquire(gat_ctx *c, const gat_signal_desc *sig, int32_t B, c
     int *d_prns = reinterpret_cast<int *>(scr + off_prn);
     gat_acq_result *d_res = reinterpret_cast<gat_acq_result *>(scr + off_res);
     float *power = power_dev ? power_dev : reinterpret_cast<float *>(scr + off_pow);
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
-    const TraceRange trace("gat_acquire");
     GAT_HIP(c, hipMemcpyAsync(d_prns, prns, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
 
     AcqArgs a{};

@@ -1,6 +1,7 @@
 // gat_api.cpp -- the C ABI declared in include/gat.h: context, validation, the stand-alone operators, timers, options, the
 // closed tracking loop with its graph cache.  The launch planner of the correlator is gat_planner.cpp, the device groups
-// gat_group.cpp, the resident correlator's host side gat_resident_api.cpp; all four share gat_ctx.h.
+// gat_group.cpp, the resident correlator's host side gat_resident_api.cpp, acquisition gat_acq_api.cpp, the antenna-array
+// entry points gat_array_api.cpp; all six share gat_ctx.h.
 #include <algorithm>
 #include <cctype>
 #include <cmath>
@@ -39,8 +40,9 @@ struct Roctx {
         if (!push || !pop) push = nullptr, pop = nullptr;
     }
 };
-TraceRange::TraceRange(const char *name)
+TraceRange::TraceRange(const char *name) : rx(nullptr)
 {
+    if (!name) return;
     static const Roctx r; // resolved once, thread-safe
     rx = &r;
     if (r.push) (void)r.push(name);
@@ -48,7 +50,7 @@ TraceRange::TraceRange(const char *name)
 TraceRange::~TraceRange()
 {
     const Roctx *r = static_cast<const Roctx *>(rx);
-    if (r->pop) (void)r->pop();
+    if (r && r->pop) (void)r->pop();
 }
 
 constexpr size_t kMaxLoopGraphs = 4;
@@ -65,41 +67,43 @@ void drop_loop_graphs(gat_ctx *c)
     c->loop_graphs.clear();
 }
 
-
-int32_t ensure_partial(gat_ctx *c, size_t bytes)
+int32_t grow_scratch(gat_ctx *c, void **buf, size_t *cap_bytes, size_t bytes, bool in_graphs)
 {
-    if (bytes <= c->partial_bytes) return GAT_OK;
-    drop_loop_graphs(c); // recorded launches point at the old buffer
-    if (c->d_partial) {
+    if (bytes <= *cap_bytes) return GAT_OK;
+    if (in_graphs) drop_loop_graphs(c); // recorded launches point at the old buffer
+    if (*buf) {
         GAT_HIP(c, hipStreamSynchronize(c->stream)); // previous launches may still read it
-        park_residents(c);
-        GAT_HIP(c, hipFree(c->d_partial));
-        c->d_partial = nullptr;
-        c->partial_bytes = 0;
+        park_residents(c);                           // hipFree waits for the whole device
+        GAT_HIP(c, hipFree(*buf));
+        *buf = nullptr;
+        *cap_bytes = 0;
     }
-    GAT_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_partial), bytes));
-    c->partial_bytes = bytes;
+    GAT_HIP(c, hipMalloc(buf, bytes));
+    *cap_bytes = bytes;
     return GAT_OK;
 }
 
 // the parameter records of a host call reach the device: into the context's buffer, on the context's stream
 int32_t upload_params(gat_ctx *c, const gat_channel_params *params_host, size_t n)
 {
-    if (n > c->params_cap) {
-        if (c->d_params) {
-            GAT_HIP(c, hipStreamSynchronize(c->stream));
-            park_residents(c);
-            GAT_HIP(c, hipFree(c->d_params));
-            c->d_params = nullptr;
-            c->params_cap = 0;
-        }
-        GAT_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_params), n * sizeof(gat_channel_params)));
-        c->params_cap = n;
-    }
+    const int32_t rc = ensure_params(c, n * sizeof(gat_channel_params));
+    if (rc != GAT_OK) return rc;
     GAT_HIP(c, hipMemcpyAsync(c->d_params, params_host, n * sizeof(gat_channel_params), hipMemcpyHostToDevice, c->stream));
     return GAT_OK;
 }
 
+int32_t check_loop_config(gat_ctx *c, const gat_loop_config *cfg)
+{
+    const int L = cfg->num_taps;
+    if (L < 1 || L > GAT_MAX_TAPS || cfg->early_index < 0 || cfg->early_index >= L || cfg->prompt_index < 0 ||
+        cfg->prompt_index >= L || cfg->late_index < 0 || cfg->late_index >= L)
+        return fail(c, GAT_ERR_RANGE, "tap indices outside the tap list");
+    if (!(cfg->block_seconds > 0.0) || !(cfg->pll_bandwidth_hz >= 0.0) || !(cfg->dll_bandwidth_hz >= 0.0) ||
+        !(cfg->code_freq_nominal_hz > 0.0) || !(cfg->carrier_center_hz > 0.0) || cfg->code_length < 1 ||
+        !(cfg->early_late_spacing_chips > 0.0 && cfg->early_late_spacing_chips < 2.0))
+        return fail(c, GAT_ERR_ARG, "bad loop configuration");
+    return GAT_OK;
+}
 
 } // namespace gat
 
@@ -112,8 +116,7 @@ int32_t tracking_run_enqueue(gat_ctx *c, const gat_signal_desc *sig, int32_t num
                              float *acc_re, float *acc_im, int64_t acc_block_stride, uint32_t flags, int32_t *current_is_b,
                              const LoopUpdateFn &update)
 {
-    const size_t sample_bytes = sig->layout == GAT_LAYOUT_PLANAR ? 4 : sig->layout == GAT_LAYOUT_INTERLEAVED ? 8
-                              : sig->layout == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 2;
+    const size_t sample_bytes = (size_t)layout_sample_bytes(sig->layout);
     gat_channel_params *cur = params_a, *nxt = params_b;
     for (int32_t b = 0; b < num_blocks; ++b) { // everything is enqueued on the ctx stream, nothing synchronises
         gat_signal_desc d = *sig;
@@ -151,7 +154,7 @@ int32_t graph_replay_or_record(gat_ctx *c, MakeKey make_key, Enqueue enqueue)
         const std::vector<unsigned char> key = make_key();
         for (auto &g : c->loop_graphs)
             if (g.exec && g.key == key) {
-                c->wait_seq = 0;
+                c->wait_seq = 0; // (gat_downconvert_and_correlate_dev comes here without the entry preamble)
                 g.last_use = ++c->loop_graph_clock;
                 GAT_HIP(c, hipGraphLaunch(g.exec, c->stream));
                 return GAT_OK;
@@ -189,7 +192,15 @@ int32_t graph_replay_or_record(gat_ctx *c, MakeKey make_key, Enqueue enqueue)
     return GAT_OK;
 }
 
-// the part of a graph key every recorded launch sequence shares: kernel-selection knobs and library-owned buffers
+// The parts of a graph key that recorded launch sequences share.  A signal descriptor, field by field (struct padding of a
+// C caller is not initialised): a field added to gat_signal_desc is added here.
+void key_put_sig(std::vector<unsigned char> &key, const gat_signal_desc *sig)
+{
+    key_put(key, sig->re); key_put(key, sig->im); key_put(key, sig->layout); key_put(key, sig->num_ants);
+    key_put(key, sig->num_samples); key_put(key, sig->ant_stride); key_put(key, sig->block_stride); key_put(key, sig->chan_stride);
+}
+// The context: kernel-selection knobs and library-owned buffers.  This is the one place that knows which members of the
+// context a recorded launch bakes in (gat_ctx.h, LoopGraph).
 void key_put_ctx(std::vector<unsigned char> &key, const gat_ctx *c)
 {
     key_put(key, c->mc_mode); key_put(key, c->mc_i16_terms); key_put(key, c->mc_nct); key_put(key, c->max_aw); key_put(key, c->max_kt); key_put(key, c->max_bpw); key_put(key, c->force_bpw);
@@ -199,66 +210,49 @@ void key_put_ctx(std::vector<unsigned char> &key, const gat_ctx *c)
     key_put(key, c->d_partial); key_put(key, c->partial_bytes);
 }
 
-} // namespace
-
-namespace {
-
 // gat_set_option: launch-geometry options (tests force a code path on a small case with them, A/B measurements compare
-// geometries).  None changes a result beyond summation order.
+// geometries).  None changes a result beyond summation order.  One entry per option: its name, its range, the store into
+// the context's member, its meaning.
 struct OptionDesc {
     const char *name;
     long long lo, hi;
+    void (*set)(gat_ctx &, long long);
 };
+#define GAT_OPT_INT(member) [](gat_ctx &c, long long v) { c.member = (int)v; }
 constexpr OptionDesc kOptions[] = {
-    {"sync_flag_wgs", 0, 1 << 20},   // largest launch (workgroups) that carries the completion flag; 0: never
-    {"max_ant_tile", 1, kMaxAntTile}, // antennas per wave
-    {"dc_aw", 1, 4},                 // antenna tiles (waves) per workgroup, cap
-    {"dc_kt", 1, 4},                 // channels per workgroup, cap
-    {"dc_bpw", 1, 1 << 20},          // consecutive blocks per workgroup, cap
-    {"dc_bpw_force", 0, 1 << 20},    // blocks per workgroup whatever the planner's rule says (0: planner)
-    {"dc_wgs_per_cu", 0, 1024},      // workgroups per CU the split planner aims for (0: by instance)
-    {"dc_one_wave", 0, 1},           // one-wave workgroups allowed
-    {"dc_one_wave_min", -1, 1ll << 40}, // fewest (block, channel, tile) groups for them (-1: 32 per CU)
-    {"dc_ow_seg", 1, kUcarSteps},    // steps per replica segment of a one-wave workgroup
-    {"dc_depth", 1, 2},              // cap of the sample prefetch depth (register sets per wave)
-    {"dc_keep_l2", -1, 1},           // sample loads: -1 by rule (plain when channel groups share a tile through L2), 0 non-temporal, 1 plain
-    {"dc_quads", -1, 1},             // replica fill four entries at a time: -1 by rule (the two-channel 2 x 2 tile), 0 never, 1 wherever the code rate allows
-    {"dc_bits", 0, 2},               // chip tables in LDS as sign bits: 0 never, 1 long codes (> 2 KB per PRN), 2 whenever every chip is +-1
-    {"dc_aw2", -1, 1},               // the two-channel 2 x 2 tile (two waves of two antennas, two channels each): -1 by rule, 0 never, 1 wherever an instance exists
-    {"dc_seg", 0, kUcarSteps},       // cap of the steps per replica segment of a four-wave workgroup (0: by instance)
-    {"mc_nct", 0, 4},                // split-bf16 kernel: 32-column channel tiles per workgroup to try first (1, 2, 4; 0 = by rule)
-    {"mc_i16_terms", 2, 3},          // split-bf16 kernel, int16 samples: 2 = the exact two-term split (5 products per sample), 3 = the float path's three terms (8)
-    {"dc_align", 0, 1},              // blocks walked from the 128-byte line their first sample lies in (1) or from the sample itself (0)
+    {"sync_flag_wgs", 0, 1 << 20, GAT_OPT_INT(flag_max_wgs)},  // largest launch (workgroups) that carries the completion flag; 0: never
+    {"max_ant_tile", 1, kMaxAntTile, GAT_OPT_INT(max_ant_tile)}, // antennas per wave
+    {"dc_aw", 1, 4, GAT_OPT_INT(max_aw)},                      // antenna tiles (waves) per workgroup, cap
+    {"dc_kt", 1, 4, GAT_OPT_INT(max_kt)},                      // channels per workgroup, cap
+    {"dc_bpw", 1, 1 << 20, GAT_OPT_INT(max_bpw)},              // consecutive blocks per workgroup, cap
+    {"dc_bpw_force", 0, 1 << 20, GAT_OPT_INT(force_bpw)},      // blocks per workgroup whatever the planner's rule says (0: planner; A/B runs)
+    {"dc_wgs_per_cu", 0, 1024, GAT_OPT_INT(wgs_per_cu)},       // workgroups per CU the split planner aims for (0: by instance)
+    {"dc_one_wave", 0, 1, GAT_OPT_INT(one_wave)},              // one-wave workgroups allowed (0: never)
+    // (the one member that is no int)
+    {"dc_one_wave_min", -1, 1ll << 40, [](gat_ctx &c, long long v) { c.one_wave_min = v; }}, // fewest (block, channel, tile) groups for them (-1: 32 per CU)
+    {"dc_ow_seg", 1, kUcarSteps, GAT_OPT_INT(one_wave_seg)},   // steps per replica segment of a one-wave workgroup
+    {"dc_depth", 1, 2, GAT_OPT_INT(max_depth)},                // cap of the sample prefetch depth (register sets per wave)
+    {"dc_keep_l2", -1, 1, GAT_OPT_INT(keep_l2)},               // sample loads: -1 by rule (plain when channel groups share a tile through L2), 0 non-temporal, 1 plain
+    {"dc_quads", -1, 1, GAT_OPT_INT(quads)},                   // replica fill four entries at a time: -1 by rule (the two-channel 2 x 2 tile), 0 never, 1 wherever the code rate allows
+    {"dc_bits", 0, 2, GAT_OPT_INT(bit_tables)},                // chip tables in LDS as sign bits: 0 never, 1 long codes (> 2 KB per PRN), 2 whenever every chip is +-1
+    {"dc_aw2", -1, 1, GAT_OPT_INT(aw2)},                       // the two-channel 2 x 2 tile (two waves of two antennas, two channels each): -1 by rule, 0 never, 1 wherever an instance exists
+    {"dc_seg", 0, kUcarSteps, GAT_OPT_INT(seg_cap)},           // cap of the steps per replica segment of a four-wave workgroup (0: by instance)
+    // (the one value that is not stored as given: the tiles per workgroup are 1, 2 or 4, and 3 means 2)
+    {"mc_nct", 0, 4, [](gat_ctx &c, long long v) { c.mc_nct = v == 3 ? 2 : (int)v; }}, // split-bf16 kernel: 32-column channel tiles per workgroup to try first (0 = by rule; A/B runs)
+    {"mc_i16_terms", 2, 3, GAT_OPT_INT(mc_i16_terms)},         // split-bf16 kernel, int16 samples: 2 = the exact two-term split (5 products per sample), 3 = the float path's three terms (8)
+    {"dc_align", 0, 1, GAT_OPT_INT(align_head)},               // blocks walked from the 128-byte line their first sample lies in (1) or from the sample itself (0)
 };
+#undef GAT_OPT_INT
 
 int32_t set_option(gat_ctx *c, const char *name, long long v)
 {
-    const OptionDesc *o = nullptr;
-    for (const auto &d : kOptions)
-        if (std::strcmp(d.name, name) == 0) o = &d;
-    if (!o) return fail(c, GAT_ERR_ARG, "unknown option");
-    if (v < o->lo || v > o->hi) return fail(c, GAT_ERR_RANGE, "option value out of range");
-    const std::string n = name;
-    if (n == "sync_flag_wgs") c->flag_max_wgs = (int)v;
-    else if (n == "max_ant_tile") c->max_ant_tile = (int)v;
-    else if (n == "dc_aw") c->max_aw = (int)v;
-    else if (n == "dc_kt") c->max_kt = (int)v;
-    else if (n == "dc_bpw") c->max_bpw = (int)v;
-    else if (n == "dc_bpw_force") c->force_bpw = (int)v;
-    else if (n == "dc_wgs_per_cu") c->wgs_per_cu = (int)v;
-    else if (n == "dc_one_wave") c->one_wave = (int)v;
-    else if (n == "dc_one_wave_min") c->one_wave_min = v;
-    else if (n == "dc_ow_seg") c->one_wave_seg = (int)v;
-    else if (n == "dc_depth") c->max_depth = (int)v;
-    else if (n == "dc_keep_l2") c->keep_l2 = (int)v;
-    else if (n == "dc_quads") c->quads = (int)v;
-    else if (n == "dc_bits") c->bit_tables = (int)v;
-    else if (n == "dc_aw2") c->aw2 = (int)v;
-    else if (n == "dc_seg") c->seg_cap = (int)v;
-    else if (n == "dc_align") c->align_head = (int)v;
-    else if (n == "mc_i16_terms") c->mc_i16_terms = (int)v;
-    else if (n == "mc_nct") c->mc_nct = v == 3 ? 2 : (int)v;
-    return GAT_OK;
+    for (const auto &o : kOptions)
+        if (std::strcmp(o.name, name) == 0) {
+            if (v < o.lo || v > o.hi) return fail(c, GAT_ERR_RANGE, "option value out of range");
+            o.set(*c, v);
+            return GAT_OK;
+        }
+    return fail(c, GAT_ERR_ARG, "unknown option");
 }
 
 } // namespace
@@ -276,8 +270,7 @@ int32_t tracking_run_shared(gat_ctx *c, const gat_signal_desc *sig, int32_t num_
     if (num_blocks < 1 || acc_block_stride < 0) return fail(c, GAT_ERR_ARG, "bad block count / stride");
     if (cfg->num_taps != L || L < 1 || L > GAT_MAX_TAPS) return fail(c, GAT_ERR_ARG, "loop configuration and tap list disagree");
     if (flags & ~(GAT_FLAG_ATOMIC | GAT_FLAG_GRAPH)) return fail(c, GAT_ERR_ARG, "unknown flag bits");
-    GAT_HIP(c, hipSetDevice(c->device));
-    const TraceRange trace("gat_tracking_run");
+    GAT_ENTER(c, "gat_tracking_run");
     const uint32_t kflags = flags & ~GAT_FLAG_GRAPH;
     if (!(flags & GAT_FLAG_GRAPH))
         return tracking_run_enqueue(c, sig, num_blocks, K, L, shifts, fs, params_a, params_b, acc_re, acc_im, acc_block_stride, kflags,
@@ -289,9 +282,8 @@ int32_t tracking_run_shared(gat_ctx *c, const gat_signal_desc *sig, int32_t num_
     // a known key replays its instantiated graph.  Up to kMaxLoopGraphs graphs are kept (least recently used goes).
     auto make_key = [&]() {
         std::vector<unsigned char> key;
-        key_put(key, sig->re); key_put(key, sig->im); key_put(key, sig->layout); key_put(key, sig->num_ants);
-        key_put(key, sig->num_samples); key_put(key, sig->ant_stride); key_put(key, sig->block_stride);
-        key_put(key, sig->chan_stride); key_put(key, num_blocks); key_put(key, K); key_put(key, L); key_put(key, fs);
+        key_put_sig(key, sig);
+        key_put(key, num_blocks); key_put(key, K); key_put(key, L); key_put(key, fs);
         key_put(key, cfg->block_seconds); key_put(key, cfg->pll_bandwidth_hz); key_put(key, cfg->dll_bandwidth_hz);
         key_put(key, cfg->code_freq_nominal_hz); key_put(key, cfg->carrier_center_hz); key_put(key, cfg->if_hz);
         key_put(key, cfg->early_late_spacing_chips); key_put(key, cfg->code_length); key_put(key, cfg->num_taps);
@@ -395,8 +387,7 @@ GAT_API int32_t gat_destroy(gat_ctx *c)
 GAT_API int32_t gat_set_stream(gat_ctx *c, void *hip_stream)
 {
     if (!c) return GAT_ERR_ARG;
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
+    GAT_ENTER(c, nullptr);
     GAT_HIP(c, hipStreamSynchronize(c->stream));
     drop_loop_graphs(c);
     if (c->own_stream) {
@@ -527,9 +518,8 @@ GAT_API int32_t gat_downconvert_and_correlate_dev(gat_ctx *c, const gat_signal_d
     auto make_key = [&]() {
         std::vector<unsigned char> key;
         key_put(key, (int)2 /* sequence: one correlate call */);
-        key_put(key, sig->re); key_put(key, sig->im); key_put(key, sig->layout); key_put(key, sig->num_ants);
-        key_put(key, sig->num_samples); key_put(key, sig->ant_stride); key_put(key, sig->block_stride);
-        key_put(key, sig->chan_stride); key_put(key, params_dev); key_put(key, B); key_put(key, K); key_put(key, L);
+        key_put_sig(key, sig);
+        key_put(key, params_dev); key_put(key, B); key_put(key, K); key_put(key, L);
         key_put(key, fs); key_put(key, out_re); key_put(key, out_im); key_put(key, kflags);
         for (int l = 0; l < L; ++l) key_put(key, shifts[l]);
         key_put_ctx(key, c);
@@ -565,8 +555,9 @@ GAT_API int32_t gat_downconvert_and_correlate(gat_ctx *c, const gat_signal_desc 
     return correlate_impl(c, sig, c->d_params, B, K, L, shifts, fs, out_re, out_im, flags);
 }
 
-static int32_t gen_code_replica_impl(gat_ctx *c, float *rep, int64_t count, int32_t prn, double fc, double fs,
-                                     double tau, int64_t first_shift, bool f32_coordinates)
+// what the one-channel replica generators check alike; each adds its own checks behind these
+static int32_t check_gen_code_replica(gat_ctx *c, const float *rep, int64_t count, int32_t prn, double fc, double fs, double tau,
+                                      int64_t first_shift)
 {
     if (!c || !rep) return fail(c, GAT_ERR_ARG, "null argument");
     if (!c->d_codes) return fail(c, GAT_ERR_STATE, "gat_set_codes has not been called");
@@ -574,11 +565,17 @@ static int32_t gen_code_replica_impl(gat_ctx *c, float *rep, int64_t count, int3
     if (prn < 0 || prn >= c->P) return fail(c, GAT_ERR_RANGE, "prn outside the code table");
     if (!(fs > 0.0) || !std::isfinite(fc) || !std::isfinite(tau)) return fail(c, GAT_ERR_ARG, "bad frequency / phase");
     if (count + std::llabs((long long)first_shift) >= (1ll << 30)) return fail(c, GAT_ERR_RANGE, "replica too long");
+    return GAT_OK;
+}
+
+static int32_t gen_code_replica_impl(gat_ctx *c, float *rep, int64_t count, int32_t prn, double fc, double fs,
+                                     double tau, int64_t first_shift, bool f32_coordinates)
+{
+    const int32_t rc = check_gen_code_replica(c, rep, count, prn, fc, fs, tau, first_shift);
+    if (rc != GAT_OK) return rc;
     if (!f32_coordinates && !code_span_ok(fc / fs, tau, (double)count + (double)std::llabs((long long)first_shift), c->Lc))
         return fail(c, GAT_ERR_RANGE, "code phase span too large");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
-    const TraceRange trace("gat_gen_code_replica");
+    GAT_ENTER(c, "gat_gen_code_replica");
     GAT_HIP(c, launch_gen_code_replica(rep, count, c->d_codes + (size_t)prn * c->code_row_stride, c->Lc, fc, fs, tau,
                                        first_shift, f32_coordinates, c->stream));
     return GAT_OK;
@@ -599,17 +596,11 @@ GAT_API int32_t gat_gen_code_replica_f32coord(gat_ctx *c, float *rep, int64_t co
 GAT_API int32_t gat_gen_code_replica_texaddr(gat_ctx *c, float *rep, int64_t count, int32_t prn, double fc, double fs, double tau,
                                              int64_t first_shift, int32_t coord_frac_bits, int32_t texel_frac_bits)
 {
-    if (!c || !rep) return fail(c, GAT_ERR_ARG, "null argument");
-    if (!c->d_codes) return fail(c, GAT_ERR_STATE, "gat_set_codes has not been called");
-    if (count < 1) return fail(c, GAT_ERR_ARG, "count must be positive");
-    if (prn < 0 || prn >= c->P) return fail(c, GAT_ERR_RANGE, "prn outside the code table");
-    if (!(fs > 0.0) || !std::isfinite(fc) || !std::isfinite(tau)) return fail(c, GAT_ERR_ARG, "bad frequency / phase");
-    if (count + std::llabs((long long)first_shift) >= (1ll << 30)) return fail(c, GAT_ERR_RANGE, "replica too long");
+    const int32_t rc = check_gen_code_replica(c, rep, count, prn, fc, fs, tau, first_shift);
+    if (rc != GAT_OK) return rc;
     if (coord_frac_bits < 0 || coord_frac_bits > 32 || texel_frac_bits < -1 || texel_frac_bits > 24)
         return fail(c, GAT_ERR_RANGE, "coord_frac_bits 0 .. 32, texel_frac_bits -1 .. 24");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
-    const TraceRange trace("gat_gen_code_replica_texaddr");
+    GAT_ENTER(c, "gat_gen_code_replica_texaddr");
     GAT_HIP(c, launch_gen_code_replica_texaddr(rep, count, c->d_codes + (size_t)prn * c->code_row_stride, c->Lc, fc, fs, tau,
                                                first_shift, coord_frac_bits, texel_frac_bits, c->stream));
     return GAT_OK;
@@ -622,9 +613,7 @@ GAT_API int32_t gat_gen_code_replica_multi(gat_ctx *c, float *rep, int64_t count
     if (!c->d_codes) return fail(c, GAT_ERR_STATE, "gat_set_codes has not been called");
     if (count < 1 || K < 1 || K > 65535 || row_stride < count) return fail(c, GAT_ERR_ARG, "bad sizes");
     if (!(fs > 0.0) || count + std::llabs((long long)first_shift) >= (1ll << 30)) return fail(c, GAT_ERR_RANGE, "replica too long");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
-    const TraceRange trace("gat_gen_code_replica_multi");
+    GAT_ENTER(c, "gat_gen_code_replica_multi");
     GAT_HIP(c, launch_gen_code_replica_multi(rep, count, row_stride, K, params_dev, c->d_codes, c->code_row_stride, c->Lc,
                                              c->P, fs, first_shift, c->stream));
     return GAT_OK;
@@ -648,22 +637,11 @@ GAT_API int32_t gat_downconvert_and_accumulate(gat_ctx *c, const gat_signal_desc
     if (sig->num_samples + max_shift >= (1ll << 30)) return fail(c, GAT_ERR_RANGE, "num_samples + |shift| must stay below 2^30");
     if (!code_span_ok(p->code_freq_hz / fs, p->code_phase_chips, (double)(sig->num_samples + max_shift), c->Lc))
         return fail(c, GAT_ERR_RANGE, "code phase span too large");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
-    const TraceRange trace("gat_downconvert_and_accumulate");
-    // the tap list goes through the library's parameter scratch (device memory the kernel can read)
+    GAT_ENTER(c, "gat_downconvert_and_accumulate");
+    // the tap list goes through the library's parameter scratch (device memory the kernel can read), in whole records
     const size_t need = ((size_t)L * sizeof(int32_t) + sizeof(gat_channel_params) - 1) / sizeof(gat_channel_params);
-    if (need > c->params_cap) {
-        if (c->d_params) {
-            GAT_HIP(c, hipStreamSynchronize(c->stream));
-            park_residents(c);
-            GAT_HIP(c, hipFree(c->d_params));
-            c->d_params = nullptr;
-            c->params_cap = 0;
-        }
-        GAT_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_params), need * sizeof(gat_channel_params)));
-        c->params_cap = need;
-    }
+    const int32_t rc = ensure_params(c, need * sizeof(gat_channel_params));
+    if (rc != GAT_OK) return rc;
     GAT_HIP(c, hipMemcpyAsync(c->d_params, shifts, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     GAT_HIP(c, launch_accumulate_debug(static_cast<const float *>(sig->re), static_cast<const float *>(sig->im),
                                        sig->num_samples, sig->num_ants, sig->ant_stride, *p,
@@ -675,7 +653,20 @@ GAT_API int32_t gat_downconvert_and_accumulate(gat_ctx *c, const gat_signal_desc
 
 static int32_t gen_signal_impl(gat_ctx *c, void *re, void *im, int32_t layout, int64_t N, int32_t M, int64_t ant_stride,
                                int64_t block_stride, int32_t B, int32_t K, const gat_channel_params *params_dev, double fs,
-                               double amplitude, const float *steering_cycles_dev, double noise_sigma, uint64_t seed);
+                               double amplitude, const float *steering_cycles_dev, double noise_sigma, uint64_t seed)
+{
+    if (!c || !re || !params_dev) return fail(c, GAT_ERR_ARG, "null argument");
+    if (!c->d_codes) return fail(c, GAT_ERR_STATE, "gat_set_codes has not been called");
+    if (layout < GAT_LAYOUT_PLANAR || layout > GAT_LAYOUT_INTERLEAVED_I8) return fail(c, GAT_ERR_ARG, "unknown layout");
+    if ((layout == GAT_LAYOUT_PLANAR) != (im != nullptr)) return fail(c, GAT_ERR_ARG, "signal pointers do not match the layout");
+    if (N < 1 || N >= (1ll << 30) || M < 1 || B < 1 || B > 65535 || K < 1) return fail(c, GAT_ERR_RANGE, "size out of range");
+    if (!(fs > 0.0) || !std::isfinite(amplitude)) return fail(c, GAT_ERR_ARG, "bad sampling frequency / amplitude");
+    GAT_ENTER(c, "gat_gen_signal");
+    GAT_HIP(c, launch_gen_signal(re, im, layout, N, M, ant_stride, block_stride, B, K, params_dev, c->d_codes,
+                                 c->code_row_stride, c->Lc, c->P, fs, (float)amplitude, steering_cycles_dev, (float)noise_sigma,
+                                 (unsigned long long)seed, c->stream));
+    return GAT_OK;
+}
 
 GAT_API int32_t gat_gen_signal(gat_ctx *c, void *re, void *im, int32_t layout, int64_t N, int32_t M,
                                int64_t ant_stride, int64_t block_stride, int32_t B, int32_t K,
@@ -694,33 +685,12 @@ GAT_API int32_t gat_gen_signal_noisy(gat_ctx *c, void *re, void *im, int32_t lay
                            steering_cycles_dev, noise_sigma, seed);
 }
 
-static int32_t gen_signal_impl(gat_ctx *c, void *re, void *im, int32_t layout, int64_t N, int32_t M, int64_t ant_stride,
-                               int64_t block_stride, int32_t B, int32_t K, const gat_channel_params *params_dev, double fs,
-                               double amplitude, const float *steering_cycles_dev, double noise_sigma, uint64_t seed)
-{
-    if (!c || !re || !params_dev) return fail(c, GAT_ERR_ARG, "null argument");
-    if (!c->d_codes) return fail(c, GAT_ERR_STATE, "gat_set_codes has not been called");
-    if (layout < GAT_LAYOUT_PLANAR || layout > GAT_LAYOUT_INTERLEAVED_I8) return fail(c, GAT_ERR_ARG, "unknown layout");
-    if ((layout == GAT_LAYOUT_PLANAR) != (im != nullptr)) return fail(c, GAT_ERR_ARG, "signal pointers do not match the layout");
-    if (N < 1 || N >= (1ll << 30) || M < 1 || B < 1 || B > 65535 || K < 1) return fail(c, GAT_ERR_RANGE, "size out of range");
-    if (!(fs > 0.0) || !std::isfinite(amplitude)) return fail(c, GAT_ERR_ARG, "bad sampling frequency / amplitude");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
-    const TraceRange trace("gat_gen_signal");
-    GAT_HIP(c, launch_gen_signal(re, im, layout, N, M, ant_stride, block_stride, B, K, params_dev, c->d_codes,
-                                 c->code_row_stride, c->Lc, c->P, fs, (float)amplitude, steering_cycles_dev, (float)noise_sigma,
-                                 (unsigned long long)seed, c->stream));
-    return GAT_OK;
-}
-
 GAT_API int32_t gat_reduce_cplx_multi(gat_ctx *c, const float *in_re, const float *in_im, int64_t n,
                                       int32_t cols, float *out_re, float *out_im)
 {
     if (!c || !in_re || !in_im || !out_re || !out_im) return fail(c, GAT_ERR_ARG, "null argument");
     if (n < 1 || cols < 1 || cols > 65535) return fail(c, GAT_ERR_ARG, "sizes must be positive");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
-    const TraceRange trace("gat_reduce_cplx_multi");
+    GAT_ENTER(c, "gat_reduce_cplx_multi");
     long long chunks = (n + 4 * kThreads - 1) / (4 * kThreads);
     const long long want = std::max<long long>(1, (4ll * c->num_cus + cols - 1) / cols);
     chunks = std::max<long long>(1, std::min(chunks, want));
@@ -737,17 +707,9 @@ GAT_API int32_t gat_tracking_update(gat_ctx *c, const float *acc_re, const float
 {
     if (!c || !acc_re || !acc_im || !cfg || !state || !cur || !next) return fail(c, GAT_ERR_ARG, "null argument");
     if (K < 1 || M < 1) return fail(c, GAT_ERR_ARG, "sizes must be positive");
-    const int L = cfg->num_taps;
-    if (L < 1 || L > GAT_MAX_TAPS || cfg->early_index < 0 || cfg->early_index >= L || cfg->prompt_index < 0 ||
-        cfg->prompt_index >= L || cfg->late_index < 0 || cfg->late_index >= L)
-        return fail(c, GAT_ERR_RANGE, "tap indices outside the tap list");
-    if (!(cfg->block_seconds > 0.0) || !(cfg->pll_bandwidth_hz >= 0.0) || !(cfg->dll_bandwidth_hz >= 0.0) ||
-        !(cfg->code_freq_nominal_hz > 0.0) || !(cfg->carrier_center_hz > 0.0) || cfg->code_length < 1 ||
-        !(cfg->early_late_spacing_chips > 0.0 && cfg->early_late_spacing_chips < 2.0))
-        return fail(c, GAT_ERR_ARG, "bad loop configuration");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
-    const TraceRange trace("gat_tracking_update");
+    const int32_t rc = check_loop_config(c, cfg);
+    if (rc != GAT_OK) return rc;
+    GAT_ENTER(c, "gat_tracking_update");
     GAT_HIP(c, launch_tracking_update(acc_re, acc_im, K, M, *cfg, state, cur, next, c->stream));
     return GAT_OK;
 }
@@ -757,7 +719,7 @@ GAT_API int32_t gat_tracking_run(gat_ctx *c, const gat_signal_desc *sig, int32_t
                                  gat_channel_params *params_a, gat_channel_params *params_b, float *acc_re,
                                  float *acc_im, int64_t acc_block_stride, uint32_t flags, int32_t *current_is_b)
 {
-    if (!c || !sig || !cfg || !state) return fail(c, GAT_ERR_ARG, "null argument");
+    // (the null checks are tracking_run_shared's: the update below is not called before them)
     return tracking_run_shared(c, sig, num_blocks, K, L, shifts, fs, cfg, state, params_a, params_b, acc_re, acc_im, acc_block_stride,
                                flags, current_is_b, nullptr, nullptr,
                                [&](const float *o_re, const float *o_im, const gat_channel_params *cur, gat_channel_params *nxt) {
@@ -785,8 +747,7 @@ GAT_API int32_t gat_free(gat_ctx *c, void *p)
 GAT_API int32_t gat_memcpy_h2d(gat_ctx *c, void *dst, const void *src, size_t bytes)
 {
     if (!c || !dst || !src) return fail(c, GAT_ERR_ARG, "null argument");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
+    GAT_ENTER(c, nullptr);
     GAT_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
     GAT_HIP(c, hipStreamSynchronize(c->stream));
     return GAT_OK;
@@ -795,8 +756,7 @@ GAT_API int32_t gat_memcpy_h2d(gat_ctx *c, void *dst, const void *src, size_t by
 GAT_API int32_t gat_memcpy_d2h(gat_ctx *c, void *dst, const void *src, size_t bytes)
 {
     if (!c || !dst || !src) return fail(c, GAT_ERR_ARG, "null argument");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
+    GAT_ENTER(c, nullptr);
     GAT_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     GAT_HIP(c, hipStreamSynchronize(c->stream));
     return GAT_OK;
@@ -805,8 +765,7 @@ GAT_API int32_t gat_memcpy_d2h(gat_ctx *c, void *dst, const void *src, size_t by
 GAT_API int32_t gat_memset(gat_ctx *c, void *dst, int32_t value, size_t bytes)
 {
     if (!c || !dst) return fail(c, GAT_ERR_ARG, "null argument");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
+    GAT_ENTER(c, nullptr);
     GAT_HIP(c, hipMemsetAsync(dst, value, bytes, c->stream));
     return GAT_OK;
 }
@@ -814,8 +773,7 @@ GAT_API int32_t gat_memset(gat_ctx *c, void *dst, int32_t value, size_t bytes)
 GAT_API int32_t gat_timer_start(gat_ctx *c)
 {
     if (!c) return GAT_ERR_ARG;
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
+    GAT_ENTER(c, nullptr);
     GAT_HIP(c, hipEventRecord(c->ev0, c->stream));
     c->timer_running = true;
     return GAT_OK;
@@ -825,8 +783,7 @@ GAT_API int32_t gat_timer_stop(gat_ctx *c, float *ms)
 {
     if (!c || !ms) return fail(c, GAT_ERR_ARG, "null argument");
     if (!c->timer_running) return fail(c, GAT_ERR_STATE, "timer not started");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
+    GAT_ENTER(c, nullptr);
     GAT_HIP(c, hipEventRecord(c->ev1, c->stream));
     GAT_HIP(c, hipEventSynchronize(c->ev1));
     GAT_HIP(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
@@ -838,14 +795,13 @@ GAT_API int32_t gat_timer_stop(gat_ctx *c, float *ms)
 GAT_API int32_t gat_timer_lap(gat_ctx *c)
 {
     if (!c) return GAT_ERR_ARG;
-    GAT_HIP(c, hipSetDevice(c->device));
+    if (c->laps >= (size_t)1 << 20) return fail(c, GAT_ERR_RANGE, "too many laps outstanding: call gat_timer_laps"); // (laps <= the pool's size)
+    GAT_ENTER(c, nullptr);
     if (c->laps == c->lap_events.size()) {
-        if (c->laps >= (size_t)1 << 20) return fail(c, GAT_ERR_RANGE, "too many laps outstanding: call gat_timer_laps");
         hipEvent_t e = nullptr;
         GAT_HIP(c, hipEventCreate(&e));
         c->lap_events.push_back(e);
     }
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
     GAT_HIP(c, hipEventRecord(c->lap_events[c->laps], c->stream));
     ++c->laps;
     return GAT_OK;
@@ -872,11 +828,9 @@ GAT_API int32_t gat_debug_read_stream(gat_ctx *c, const void *dev, size_t bytes,
     if (!c || !dev || !ms_each) return fail(c, GAT_ERR_ARG, "null argument");
     if (bytes < 16 || bytes % 16 != 0 || !aligned16(dev)) return fail(c, GAT_ERR_ARG, "the range must be whole, aligned 16-byte groups");
     if (launches < 1 || launches > 4096 || variant < 0 || variant > 15) return fail(c, GAT_ERR_RANGE, "1 .. 4096 launches, variants 0 .. 15");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
+    GAT_ENTER(c, "gat_debug_read_stream");
     int32_t rc = ensure_partial(c, 64);
     if (rc != GAT_OK) return rc;
-    const TraceRange trace("gat_debug_read_stream");
     for (int32_t i = 0; i < launches; ++i) {
         GAT_HIP(c, hipEventRecord(c->ev0, c->stream));
         GAT_HIP(c, launch_read_stream(dev, bytes, variant, c->num_cus, c->d_partial, c->stream));

@@ -14,11 +14,6 @@ namespace {
 
 constexpr size_t kMaxCovScratch = (size_t)256 << 20; // bytes of the workgroups' slices of one launch; more estimates go in batches
 
-size_t sample_bytes(int layout)
-{
-    return layout == GAT_LAYOUT_PLANAR ? 4 : layout == GAT_LAYOUT_INTERLEAVED ? 8 : layout == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 2;
-}
-
 // B blocks, E estimates of bpe blocks (the last one shorter), from `re` / `im`
 int32_t covariance_launches(gat_ctx *c, const gat_signal_desc *sig, const void *re, const void *im, int B, int bpe, int E, bool vec, float *cov_re,
                             float *cov_im)
@@ -27,7 +22,7 @@ int32_t covariance_launches(gat_ctx *c, const gat_signal_desc *sig, const void *
     const long long N = sig->num_samples;
     const CovTileGeom geo = cov_tile_geom(M);
     // the smallest piece of a block worth a work unit, and what a segment's length is rounded up to
-    const long long vs = cov_vec_samples(layout);
+    const long long vs = layout_vec_samples(layout);
     const long long round_to = vec ? vs * kCovSmallThreads : geo.chunk;
     const long long min_seg = vec ? 4 * round_to : 8ll * geo.chunk;
     const long long want = (long long)c->num_cus * (vec ? 8 : 4); // workgroups of the launch
@@ -61,18 +56,6 @@ int32_t covariance_launches(gat_ctx *c, const gat_signal_desc *sig, const void *
     return GAT_OK;
 }
 
-int32_t check_loop_config(gat_ctx *c, const gat_loop_config *cfg)
-{
-    const int L = cfg->num_taps;
-    if (L < 1 || L > GAT_MAX_TAPS || cfg->early_index < 0 || cfg->early_index >= L || cfg->prompt_index < 0 || cfg->prompt_index >= L ||
-        cfg->late_index < 0 || cfg->late_index >= L)
-        return fail(c, GAT_ERR_RANGE, "tap indices outside the tap list");
-    if (!(cfg->block_seconds > 0.0) || !(cfg->pll_bandwidth_hz >= 0.0) || !(cfg->dll_bandwidth_hz >= 0.0) || !(cfg->code_freq_nominal_hz > 0.0) ||
-        !(cfg->carrier_center_hz > 0.0) || cfg->code_length < 1 || !(cfg->early_late_spacing_chips > 0.0 && cfg->early_late_spacing_chips < 2.0))
-        return fail(c, GAT_ERR_ARG, "bad loop configuration");
-    return GAT_OK;
-}
-
 } // namespace
 
 GAT_API int32_t gat_spatial_covariance(gat_ctx *c, const gat_signal_desc *sig, int32_t B, int32_t bpe, float *cov_re, float *cov_im)
@@ -92,12 +75,10 @@ GAT_API int32_t gat_spatial_covariance(gat_ctx *c, const gat_signal_desc *sig, i
         return fail(c, GAT_ERR_RANGE, "signal extent too large");
     const int M = sig->num_ants;
     // the streaming kernel's rule is the correlator's fast-path rule: every block of every antenna starts on a 16-byte boundary
-    const long long vs = cov_vec_samples(layout);
+    const long long vs = layout_vec_samples(layout);
     const bool vec = M <= kCovSmallMaxAnts && aligned16(sig->re) && (layout != GAT_LAYOUT_PLANAR || aligned16(sig->im)) &&
                      (M == 1 || sig->ant_stride % vs == 0) && (B == 1 || sig->block_stride % vs == 0);
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0; // newer work than a flagged launch: gat_sync waits on the stream
-    const TraceRange trace("gat_spatial_covariance");
+    GAT_ENTER(c, "gat_spatial_covariance");
     // estimates per launch: one workgroup each at least, within the scratch bound
     const int E = (B + bpe - 1) / bpe;
     const size_t slice = (size_t)2 * M * M * sizeof(float);
@@ -105,7 +86,7 @@ GAT_API int32_t gat_spatial_covariance(gat_ctx *c, const gat_signal_desc *sig, i
     for (int e0 = 0; e0 < E; e0 += e_max) {
         const int en = std::min(e_max, E - e0);
         const int b0 = e0 * bpe, bn = std::min(B - b0, en * bpe);
-        const size_t off = (size_t)b0 * (size_t)sig->block_stride * sample_bytes(layout);
+        const size_t off = (size_t)b0 * (size_t)sig->block_stride * (size_t)layout_sample_bytes(layout);
         const void *re = static_cast<const char *>(sig->re) + off;
         const void *im = sig->im ? static_cast<const char *>(sig->im) + off : nullptr;
         const int32_t rc = covariance_launches(c, sig, re, im, bn, bpe, en, vec, cov_re + (size_t)e0 * M * M, cov_im + (size_t)e0 * M * M);
@@ -125,11 +106,9 @@ GAT_API int32_t gat_array_weights(gat_ctx *c, const float *cov_re, const float *
     if (!(loading >= 0.0) || !std::isfinite(loading)) return fail(c, GAT_ERR_ARG, "loading must be finite and not negative");
     if (M > GAT_MAX_ARRAY_ANTS) return fail(c, GAT_ERR_RANGE, "more than 64 antennas");
     if (K > 65535) return fail(c, GAT_ERR_RANGE, "too many channels for one call");
-    GAT_HIP(c, hipSetDevice(c->device));
+    GAT_ENTER(c, "gat_array_weights");
     const int32_t rc = ensure_partial(c, ((size_t)2 * M * M + 1) * sizeof(double));
     if (rc != GAT_OK) return rc;
-    c->wait_seq = 0;
-    const TraceRange trace("gat_array_weights");
     GAT_HIP(c, array_weights_allow_lds());
     GAT_HIP(c, launch_array_weights(cov_re, cov_im, M, steer_re, steer_im, K, mode, loading, reinterpret_cast<double *>(c->d_partial), w_re, w_im,
                                     c->stream));
@@ -144,9 +123,7 @@ GAT_API int32_t gat_beamform(gat_ctx *c, const float *acc_re, const float *acc_i
     if (B < 1 || K < 1 || L < 1 || M < 1) return fail(c, GAT_ERR_ARG, "sizes must be positive");
     const long long rows = (long long)B * K * L;
     if (rows > ((long long)1 << 38)) return fail(c, GAT_ERR_RANGE, "too many accumulators for one call");
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0;
-    const TraceRange trace("gat_beamform");
+    GAT_ENTER(c, "gat_beamform");
     GAT_HIP(c, launch_beamform(acc_re, acc_im, rows, K, L, M, w_re, w_im, out_re, out_im, c->stream));
     return GAT_OK;
 }
@@ -160,9 +137,7 @@ GAT_API int32_t gat_tracking_update_weighted(gat_ctx *c, const float *acc_re, co
     if (K < 1 || M < 1) return fail(c, GAT_ERR_ARG, "sizes must be positive");
     const int32_t rc = check_loop_config(c, cfg);
     if (rc != GAT_OK) return rc;
-    GAT_HIP(c, hipSetDevice(c->device));
-    c->wait_seq = 0;
-    const TraceRange trace("gat_tracking_update_weighted");
+    GAT_ENTER(c, "gat_tracking_update_weighted");
     GAT_HIP(c, launch_tracking_update_weighted(acc_re, acc_im, K, M, *cfg, state, cur, next, w_re, w_im, c->stream));
     return GAT_OK;
 }
@@ -175,7 +150,7 @@ GAT_API int32_t gat_tracking_run_weighted(gat_ctx *c, const gat_signal_desc *sig
     if (!w_re && !w_im)
         return gat_tracking_run(c, sig, num_blocks, K, L, shifts, fs, cfg, state, params_a, params_b, acc_re, acc_im, acc_block_stride, flags,
                                 current_is_b);
-    if (!c || !sig || !cfg || !state || !w_re || !w_im) return fail(c, GAT_ERR_ARG, "null argument");
+    if (!w_re || !w_im) return fail(c, GAT_ERR_ARG, "null argument"); // (the other null checks are tracking_run_shared's)
     return tracking_run_shared(c, sig, num_blocks, K, L, shifts, fs, cfg, state, params_a, params_b, acc_re, acc_im, acc_block_stride, flags,
                                current_is_b, w_re, w_im,
                                [&](const float *o_re, const float *o_im, const gat_channel_params *cur, gat_channel_params *nxt) {

@@ -16,12 +16,6 @@ constexpr int kCovTileThreads = 512; // the LDS-tiled kernel: 4 x 4 antenna tile
 constexpr int kCovTile = 4;
 constexpr int kCovFinishLanes = 64;  // the finishing kernel adds a (estimate, element)'s slices in this many interleaved runs
 
-// samples one 16-byte load holds, by layout
-inline int cov_vec_samples(int layout)
-{
-    return layout == GAT_LAYOUT_PLANAR ? 4 : layout == GAT_LAYOUT_INTERLEAVED ? 2 : layout == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 8;
-}
-
 // Geometry of the LDS-tiled kernel for M antennas: nt x nt tiles of 4 x 4, the upper ones (tiles) spread over the
 // workgroup's threads with `phases` sample phases each; a chunk of `chunk` = phases * per_phase samples is staged per step
 // in rows of `row` float2 (the antennas padded to whole tiles, plus two: consecutive samples start 16 bytes further round

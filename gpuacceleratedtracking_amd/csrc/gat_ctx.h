@@ -1,5 +1,7 @@
-// gat_ctx.h -- what the translation units of the C-ABI layer share (gat_api.cpp: contexts, operators, loop; gat_planner.cpp: the
-// correlator call's launch planning; gat_group.cpp: device groups; gat_resident_api.cpp: the resident correlator's host side): the context, error helpers, the planner's entry point.
+// gat_ctx.h -- what the translation units of the C-ABI layer share: the context, error helpers, the entry preamble, scratch and
+// graph housekeeping, the planner's entry points.  The layer: gat_api.cpp (contexts, operators, options, the closed loop),
+// gat_planner.cpp (the correlator call's launch planning), gat_group.cpp (device groups), gat_resident_api.cpp (the resident
+// correlator's host side), gat_acq_api.cpp (acquisition), gat_array_api.cpp (antenna arrays).
 #pragma once
 
 #include <cmath>
@@ -46,7 +48,9 @@ struct gat_ctx {
     bool own_stream = false;
     int8_t *d_codes = nullptr;
     // gat_tracking_run with GAT_FLAG_GRAPH: the launch sequence of the last such call, instantiated (replayed when the
-    // next call has the same arguments: a receiver cycling through one ring buffer)
+    // next call has the same arguments: a receiver cycling through one ring buffer).  Which members of the context a
+    // recorded launch bakes in is known in ONE place, key_put_ctx (gat_api.cpp): whatever changes one of them without
+    // being part of that key must call drop_loop_graphs.
     struct LoopGraph {
         std::vector<unsigned char> key;
         hipGraphExec_t exec = nullptr;
@@ -67,31 +71,32 @@ struct gat_ctx {
     unsigned *d_done = nullptr;      // device: arrival counter of a launch's workgroups
     unsigned flag_seq = 0;           // last sequence number handed to a launch
     unsigned wait_seq = 0;           // != 0: the newest work on the stream is a flagged launch with this number
-    int flag_max_wgs = 1024;         // option sync_flag_wgs: largest launch that carries the flag (0: never)
-    gat_channel_params *d_params = nullptr;
-    size_t params_cap = 0;
+    int flag_max_wgs = 1024;         // option sync_flag_wgs
+    gat_channel_params *d_params = nullptr; // parameter scratch: the records of a host call, the tap list of gat_downconvert_and_accumulate
+    size_t params_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timer_running = false;
     std::vector<hipEvent_t> lap_events; // gat_timer_lap: pool, grows to the most laps ever outstanding
     size_t laps = 0;                    // laps recorded since the last gat_timer_laps
     int num_cus = 256;
-    int max_ant_tile = gat::kMaxAntTile; // option max_ant_tile (gat_set_option)
-    int max_aw = 4, max_kt = 4, max_bpw = 16; // options dc_aw / dc_kt / dc_bpw (gat_set_vector_tiling): caps of the vector kernel's geometry
-    int force_bpw = 0;                        // option dc_bpw_force: blocks per workgroup whatever the planner's rule says (A/B runs)
-    int wgs_per_cu = 0;                       // option dc_wgs_per_cu: workgroups per CU the split planner aims for (0: by instance)
-    int one_wave = 1;                         // option dc_one_wave = 0: never use one-wave workgroups
-    long long one_wave_min = -1;              // option dc_one_wave_min: fewest (block, channel, tile) groups for them (default 32 per CU)
-    int one_wave_seg = gat::kOneWaveSegSteps;      // option dc_ow_seg: steps per replica segment of a one-wave workgroup
-    int max_depth = 2;                        // option dc_depth: cap of the sample prefetch depth (register sets per wave)
-    int keep_l2 = -1;                         // option dc_keep_l2: cache policy of the sample loads (-1: by rule)
-    int quads = -1;                           // option dc_quads: replica fill by quads (-1 by rule, 0 never, 1 wherever possible)
-    int bit_tables = 1;                       // option dc_bits: chip tables staged as sign bits (0 never, 1 long codes, 2 whenever chips are +-1)
-    int aw2 = -1;                             // option dc_aw2: the two-channel 2 x 2 tile (-1 by rule, 0 never, 1 wherever possible)
-    int seg_cap = 0;                          // option dc_seg: cap of the steps per replica segment (0: by instance)
-    int align_head = 1;                       // option dc_align: line-aligned virtual block starts where blocks start off a line
-    int mc_mode = 1; // GAT_MC_* kernel selection (gat_set_matrix_core)
-    int mc_nct = 0;       // option mc_nct: column tiles per workgroup of the split-bf16 kernel to try first (0: by rule; A/B runs)
-    int mc_i16_terms = 2; // option mc_i16_terms: bf16 terms per int16 sample on the split-bf16 kernel (2: exact two-term split; 3: the float path's split)
+    // launch-geometry options: what each means, and its range, is the table kOptions of gat_api.cpp
+    int max_ant_tile = gat::kMaxAntTile;      // option max_ant_tile
+    int max_aw = 4, max_kt = 4, max_bpw = 16; // options dc_aw / dc_kt / dc_bpw (and gat_set_vector_tiling)
+    int force_bpw = 0;                        // option dc_bpw_force
+    int wgs_per_cu = 0;                       // option dc_wgs_per_cu
+    int one_wave = 1;                         // option dc_one_wave
+    long long one_wave_min = -1;              // option dc_one_wave_min
+    int one_wave_seg = gat::kOneWaveSegSteps; // option dc_ow_seg
+    int max_depth = 2;                        // option dc_depth
+    int keep_l2 = -1;                         // option dc_keep_l2
+    int quads = -1;                           // option dc_quads
+    int bit_tables = 1;                       // option dc_bits
+    int aw2 = -1;                             // option dc_aw2
+    int seg_cap = 0;                          // option dc_seg
+    int align_head = 1;                       // option dc_align
+    int mc_mode = 1;                          // GAT_MC_* kernel selection (gat_set_matrix_core)
+    int mc_nct = 0;                           // option mc_nct
+    int mc_i16_terms = 2;                     // option mc_i16_terms
     std::string err;
     gat_launch_info last{};
 };
@@ -128,7 +133,8 @@ inline bool code_span_ok(double ratio, double tau, double reach, int Lc)
 }
 
 // Tracing ranges around the library's launch sequences (the reference wraps every launch of kernel_algorithm in
-// NVTX.@range, src/algorithms.jl:953 ...): roctxRangePush / Pop, resolved at the first use (gat_api.cpp).  RAII.
+// NVTX.@range, src/algorithms.jl:953 ...): roctxRangePush / Pop, resolved at the first use (gat_api.cpp).  RAII; a null
+// name opens nothing.
 struct TraceRange {
     explicit TraceRange(const char *name);
     ~TraceRange();
@@ -136,10 +142,26 @@ struct TraceRange {
     TraceRange &operator=(const TraceRange &) = delete;
     const void *rx;
 };
+
+// The start of every entry point that enqueues on the context's stream, AFTER its validation (a refused call leaves
+// wait_seq alone), in this order: select the device; clear wait_seq -- what follows is newer work than a flagged launch,
+// so gat_sync must wait on the stream (spinning on the older launch's flag would return before the newer work is done) --;
+// open the trace range `range` of the calling scope (null: the entry point has none).  No allocation: this is on the path
+// of the single-block latency.  Entry points that enqueue nothing keep a bare hipSetDevice.
+#define GAT_ENTER(c, range)                \
+    GAT_HIP(c, hipSetDevice(c->device));   \
+    (c)->wait_seq = 0;                     \
+    const gat::TraceRange trace_(range)
+
 // scratch and graph housekeeping shared by the planner, the operators and the loop (gat_api.cpp)
 void drop_loop_graphs(gat_ctx *c);
-int32_t ensure_partial(gat_ctx *c, size_t bytes);
+// Room for `bytes` in a library-owned device buffer; in_graphs: recorded graphs bake its pointer in and go when it moves.
+int32_t grow_scratch(gat_ctx *c, void **buf, size_t *cap_bytes, size_t bytes, bool in_graphs);
+inline int32_t ensure_partial(gat_ctx *c, size_t bytes) { return grow_scratch(c, reinterpret_cast<void **>(&c->d_partial), &c->partial_bytes, bytes, true); }
+inline int32_t ensure_params(gat_ctx *c, size_t bytes) { return grow_scratch(c, reinterpret_cast<void **>(&c->d_params), &c->params_bytes, bytes, false); }
 int32_t upload_params(gat_ctx *c, const gat_channel_params *params_host, size_t n);
+// validation of a loop configuration (gat_tracking_update and the weighted update)
+int32_t check_loop_config(gat_ctx *c, const gat_loop_config *cfg);
 
 // The closed loop's native run (gat_api.cpp), shared by gat_tracking_run and gat_tracking_run_weighted (gat_array_api.cpp):
 // `update` enqueues the loop's update step for one block's accumulators and parameter pair; w_re / w_im (null: the

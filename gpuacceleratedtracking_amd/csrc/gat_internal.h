@@ -23,13 +23,17 @@ constexpr int kMaxReplicaSpan = 512;  // tap span the LDS replica segment of a l
 constexpr int kMaxLaunchSpan = 2048;  // largest tap span one launch serves (the replica's LDS grows with the span beyond
                                       // kMaxReplicaSpan; wider tap lists are cut into several launches)
 
-// Sample ownership of one lane per step in dc_kernel: G groups of S consecutive samples, one
-// 16-byte load per plane and group (vec == 4) or scalar loads (vec == 1).  S by format:
-// planar f32 4, interleaved ComplexF32 2, interleaved int16 4, interleaved int8 8.
-constexpr int dc_group_samples(int vec, int fmt)
+// Layout arithmetic, stated here once.  Bytes of one sample in one plane: planar f32 4, interleaved ComplexF32 8,
+// interleaved int16 4, interleaved int8 2 -- and the samples one 16-byte load holds: 4, 2, 4, 8.
+constexpr int layout_sample_bytes(int fmt)
 {
-    return vec != 4 ? 1 : fmt == GAT_LAYOUT_PLANAR ? 4 : fmt == GAT_LAYOUT_INTERLEAVED ? 2 : fmt == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 8;
+    return fmt == GAT_LAYOUT_PLANAR ? 4 : fmt == GAT_LAYOUT_INTERLEAVED ? 8 : fmt == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 2;
 }
+constexpr int layout_vec_samples(int fmt) { return 16 / layout_sample_bytes(fmt); }
+
+// Sample ownership of one lane per step in dc_kernel: G groups of S consecutive samples, one
+// 16-byte load per plane and group (vec == 4: S = layout_vec_samples) or scalar loads (vec == 1: S = 1).
+constexpr int dc_group_samples(int vec, int fmt) { return vec != 4 ? 1 : layout_vec_samples(fmt); }
 constexpr int dc_groups(int vec, int fmt)
 {
     return vec == 4 && fmt == GAT_LAYOUT_INTERLEAVED ? 2 : 1;

@@ -110,7 +110,7 @@ Refusal plan_correlate(const gat_ctx &c, const Call &call, long long resident_wg
     // 16-byte vector loads need every group start 16-byte aligned: plane bases and all strides
     // multiples of the samples one 16-byte load holds (4 / 2 / 4 / 8 by format)
     const int spv = dc_group_samples(4, fmt);
-    const long long plane_bytes = fmt == GAT_LAYOUT_PLANAR ? 4 : fmt == GAT_LAYOUT_INTERLEAVED ? 8 : fmt == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 2;
+    const long long plane_bytes = layout_sample_bytes(fmt);
     int vec = 1;
     // ... in a block that a 32-bit descriptor length can describe.  The block LENGTH may be anything (the reference
     // bounds each thread by num_samples, src/algorithms.jl:170): lanes beyond the last whole group read zeros through
@@ -635,6 +635,7 @@ int32_t gat::correlate_impl(gat_ctx *c, const gat_signal_desc *sig, const gat_ch
                             int32_t B, int32_t K, int32_t L, const int32_t *shifts, double fs,
                             float *out_re, float *out_im, uint32_t flags, const gat_channel_params *params_inline)
 {
+    // (not the entry preamble of gat_ctx.h: every caller arrives here after its own hipSetDevice, the loop once per block)
     c->wait_seq = 0;
     const TraceRange trace("gat_downconvert_and_correlate");
     if (!sig || (!params_dev && !params_inline) || !shifts || !out_re || !out_im) return fail(c, GAT_ERR_ARG, "null argument");

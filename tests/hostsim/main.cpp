@@ -1,4 +1,5 @@
-// main.cpp -- drives libgat's C ABI (the real gat_api.cpp + gat_codes.cpp + gat_version.cpp) on the host-only stand-ins of
+// main.cpp -- drives libgat's C ABI (the real gat_api.cpp, gat_planner.cpp, gat_group.cpp, gat_resident_api.cpp, gat_acq_api.cpp,
+// gat_codes.cpp and gat_version.cpp; not gat_array_api.cpp, whose launchers have no stand-ins yet) on the host-only stand-ins of
 // this directory, under AddressSanitizer + UndefinedBehaviorSanitizer:
 //   1. thousands of random correlate calls on L1 / L5 and random caller's tables (formats, alignments, ragged lengths, strides, tap lists, flags, options) -- every
 //      launch the planner emits is checked against the kernel's contract by fake_kernels.cpp; error paths must return
@@ -44,8 +45,11 @@ static long long uni(long long lo, long long hi) { return std::uniform_int_distr
 static double unif(double lo, double hi) { return std::uniform_real_distribution<double>(lo, hi)(rng); }
 template <class T> static T pick(std::initializer_list<T> l) { return *(l.begin() + uni(0, (long long)l.size() - 1)); }
 
-static const int kBytes[4] = {4, 8, 4, 2};   // bytes of one sample in one plane, by layout
-static const int kSpv[4] = {4, 2, 4, 8};     // samples of one 16-byte load
+// bytes of one sample in one plane and samples of one 16-byte load, by layout: the library's arithmetic (gat_internal.h), pinned here
+using gat::layout_sample_bytes;
+using gat::layout_vec_samples;
+static_assert(layout_sample_bytes(0) == 4 && layout_sample_bytes(1) == 8 && layout_sample_bytes(2) == 4 && layout_sample_bytes(3) == 2, "bytes per sample");
+static_assert(layout_vec_samples(0) == 4 && layout_vec_samples(1) == 2 && layout_vec_samples(2) == 4 && layout_vec_samples(3) == 8, "samples per load");
 
 // A caller's chip table (gat_set_codes takes any int8 chips, 1 .. 120 000 per row), [Lc x P] column-major.  kind 0: random
 // +-1; 1: +-1 with some chips 0; 2: {-1, 0, +1}; 3: the whole int8 range, -128 and 127 included.
@@ -221,10 +225,10 @@ int main(int argc, char **argv)
         const int B = M * K >= 256 ? (int)pick<long long>({1, 1, 2, 3}) : (int)pick<long long>({1, 1, 1, 2, 3, 7, 16, 64, 500});
         const int L = (int)pick<long long>({1, 2, 3, 3, 5, 7, 8, 11, 17, 32});
         long long N = pick<long long>({uni(1, 64), uni(64, 5000), 2048, 2500, 4096, 20000, 50000, uni(5000, 300000), 262144});
-        if (uni(0, 3) == 0) N -= N % kSpv[fmt];
-        if (N < 1) N = kSpv[fmt];
-        const long long pad = pick<long long>({0, 0, 0, kSpv[fmt], 1, 3, 32});
-        long long bstride = N + pad, astride = bstride * B + pick<long long>({0, 0, kSpv[fmt] * 4, 1});
+        if (uni(0, 3) == 0) N -= N % layout_vec_samples(fmt);
+        if (N < 1) N = layout_vec_samples(fmt);
+        const long long pad = pick<long long>({0, 0, 0, layout_vec_samples(fmt), 1, 3, 32});
+        long long bstride = N + pad, astride = bstride * B + pick<long long>({0, 0, layout_vec_samples(fmt) * 4, 1});
         const long long cstride = (K > 1 && uni(0, 5) == 0) ? astride * M : 0;
         const uintptr_t mis = pick<long long>({0, 0, 0, 0, 4, 8, 2});
         gat_signal_desc sig = {(void *)(uintptr_t)(0x10000000 + mis), fmt == 0 ? (void *)(uintptr_t)(0x50000000 + mis) : nullptr, fmt, M, N, astride, bstride, cstride};
@@ -274,8 +278,8 @@ int main(int argc, char **argv)
             ++ok_calls;
             gat_launch_info li;
             EXPECT(gat_last_launch_info(ctx, &li, sizeof li) == GAT_OK && li.workgroups > 0 && (li.vec == 4 || li.vec == 1), "launch info");
-            const bool aligned = mis % 16 == 0 && (M == 1 || astride % kSpv[fmt] == 0) && (B == 1 || bstride % kSpv[fmt] == 0) && cstride % kSpv[fmt] == 0;
-            EXPECT((li.vec == 4) == (aligned && N * kBytes[fmt] < (1ll << 31)), "vector path: vec %d for aligned %d (fmt %d N %lld M %d B %d)", li.vec, (int)aligned, fmt, N, M, B);
+            const bool aligned = mis % 16 == 0 && (M == 1 || astride % layout_vec_samples(fmt) == 0) && (B == 1 || bstride % layout_vec_samples(fmt) == 0) && cstride % layout_vec_samples(fmt) == 0;
+            EXPECT((li.vec == 4) == (aligned && N * layout_sample_bytes(fmt) < (1ll << 31)), "vector path: vec %d for aligned %d (fmt %d N %lld M %d B %d)", li.vec, (int)aligned, fmt, N, M, B);
         } else {
             ++rejected;
         }
@@ -651,8 +655,8 @@ int main(int argc, char **argv)
     for (int it = 0; it < 60; ++it) {
         const int fmt = (int)uni(0, 3), M = (int)pick<long long>({1, 2, 3, 4, 8, 16}), K = (int)pick<long long>({1, 1, 2, 3, 4, 5, 9, 12, 16, 17}), L = (int)pick<long long>({1, 3, 5, 7, 8, 9});
         long long N = pick<long long>({2048, 2500, 4096, 16384, 20000, 65536, 262144, uni(100, 100000)});
-        if (uni(0, 4) != 0) N -= N % kSpv[fmt];
-        if (N < kSpv[fmt]) N = kSpv[fmt];
+        if (uni(0, 4) != 0) N -= N % layout_vec_samples(fmt);
+        if (N < layout_vec_samples(fmt)) N = layout_vec_samples(fmt);
         std::vector<int32_t> sh(L);
         const int spread = (int)pick<long long>({1, 8, 300, 1000, 1500});
         for (int l = 0; l < L; ++l) sh[l] = (int32_t)uni(-spread, spread);
@@ -665,7 +669,7 @@ int main(int argc, char **argv)
         const int32_t rc = gat_resident_open(ctx, &sig, K, L, sh.data(), N / 1e-3, cfgp, &res);
         std::vector<int32_t> sorted(sh);
         std::sort(sorted.begin(), sorted.end());
-        const bool servable = K <= 16 && L <= 8 && sorted.back() - sorted.front() <= 2048 && N % kSpv[fmt] == 0 && mis == 0;
+        const bool servable = K <= 16 && L <= 8 && sorted.back() - sorted.front() <= 2048 && N % layout_vec_samples(fmt) == 0 && mis == 0;
         if (rc == GAT_ERR_UNSUPPORTED && servable) {
             // refused for want of room: the same geometry opens on a context without open correlators, and its workgroups
             // together with those left open here are more than the device's 256 units hold
@@ -714,7 +718,7 @@ int main(int argc, char **argv)
                 prm[0].prn = 77;
                 EXPECT(gat_resident_correlate(res, prm.data(), off, r_re.data(), r_im.data()) == GAT_ERR_RANGE, "resident: bad prn");
                 prm[0].prn = 4;
-                EXPECT(gat_resident_correlate(res, prm.data(), 1, r_re.data(), r_im.data()) != GAT_OK || kSpv[fmt] == 1, "resident: misaligned offset");
+                EXPECT(gat_resident_correlate(res, prm.data(), 1, r_re.data(), r_im.data()) != GAT_OK || layout_vec_samples(fmt) == 1, "resident: misaligned offset");
             }
             std::fill(r_re.begin(), r_re.end(), -1.f);
             const int32_t rcc = gat_resident_correlate(res, prm.data(), off, r_re.data(), r_im.data());
