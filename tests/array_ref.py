@@ -5,16 +5,51 @@ import numpy as np
 import oracle
 
 
+def block_view(x, N, B, block_stride=None):
+    """x [M, ld] -> the B blocks of N samples, block_stride apart, as a read-only view [B, M, N]"""
+    S = N if block_stride is None else block_stride
+    assert x.ndim == 2 and (B - 1) * S + N <= x.shape[1], (x.shape, N, B, S)
+    return np.lib.stride_tricks.as_strided(x, shape=(B, x.shape[0], N), strides=(S * x.strides[1], x.strides[0], x.strides[1]), writeable=False)
+
+
+def _block_products(x, N, B, bpe, block_stride):
+    """one matrix product x_b x_b^H per block in x's own precision, the blocks of an estimate added in order"""
+    xb = block_view(x, N, B, block_stride)
+    R = xb @ xb.conj().transpose(0, 2, 1)
+    return R if bpe == 1 else np.add.reduceat(R, np.arange(0, B, bpe), axis=0)
+
+
 def covariance(x, N, B, bpe, block_stride=None):
     """x complex128 [M, ld]: R_e[i, j] = sum_{b in e} sum_{n < N} x[i, b S + n] conj(x[j, b S + n]), [E, M, M]."""
-    S = N if block_stride is None else block_stride
-    M = x.shape[0]
-    E = -(-B // bpe)
-    R = np.zeros((E, M, M), dtype=np.complex128)
-    for b in range(B):
-        xb = x[:, b * S:b * S + N]
-        R[b // bpe] += xb @ xb.conj().T
-    return R
+    return _block_products(np.asarray(x, dtype=np.complex128), N, B, bpe, block_stride)
+
+
+def covariance_error(got, ref):
+    """Per estimate, max_ij |got_ij - ref_ij| / sqrt(ref_ii ref_jj): every element on its own natural scale (what bounds
+    both |R_ij| and its float32 summation error), so that an error confined to a weak antenna's sub-matrix counts as much
+    as one on the strongest.  got, ref complex [E, M, M]; returns float64 [E].  Where a diagonal element of ref is exactly
+    0 (an antenna of zeros) that row and column of got must be exactly 0 (asserted); they take no part in the maximum.
+    Elements that are not finite in got or ref give NaN (or inf), which no bound passes."""
+    got = np.asarray(got, dtype=np.complex128)
+    ref = np.asarray(ref, dtype=np.complex128)
+    assert got.shape == ref.shape and got.ndim == 3 and got.shape[1] == got.shape[2], (got.shape, ref.shape)
+    E, M = ref.shape[:2]
+    d = ref[:, np.arange(M), np.arange(M)].real  # [E, M]
+    zero = d == 0
+    dead = zero[:, :, None] | zero[:, None, :]
+    assert (got[dead] == 0).all(), "an antenna of zeros has a nonzero row or column"
+    scale = np.sqrt(np.where(zero, 1.0, d))
+    err = np.abs(got - ref) / (scale[:, :, None] * scale[:, None, :])
+    err = np.where(dead, 0.0, err)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isnan(err).any(axis=(1, 2)), np.nan, np.nanmax(err, axis=(1, 2)))
+
+
+def covariance_f32(x, N, B, bpe, block_stride=None):
+    """covariance() by numpy's complex64 product x32 @ x32.conj().T of the same samples, block by block, the block sums added
+    in complex64: a float32 reference, whose own covariance_error against covariance() is what float32 summation costs on
+    these samples."""
+    return _block_products(np.asarray(x).astype(np.complex64), N, B, bpe, block_stride)
 
 
 def loaded(R, loading):

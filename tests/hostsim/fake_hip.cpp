@@ -30,6 +30,7 @@ struct hipGraphExec {
 namespace hostsim {
 Counters counters;
 TapCover tap_cover;
+CovCover cov_cover;
 void attach_worker(hipStream_t s, std::thread &&t)
 {
     if (s->worker.joinable()) s->worker.join(); // launches of one stream run in order

@@ -1,5 +1,5 @@
-// fake_kernels.cpp -- stand-ins for libgat's kernel launchers (the functions gat_kernels.hip, gat_dc_f*.hip, gat_mfma*.hip and
-// gat_resident_f*.hip define): nothing is computed.  Instead every launch of the vector kernel is checked against what the
+// fake_kernels.cpp -- stand-ins for libgat's kernel launchers (the functions gat_kernels.hip, gat_dc_f*.hip, gat_mfma*.hip,
+// gat_resident_f*.hip, gat_acq.hip and gat_array.hip define): nothing is computed.  Instead every launch of the vector kernel is checked against what the
 // kernel ASSUMES about its arguments (LDS carve-up, replica room, grid decode, descriptor spans, tap tables): the planner's
 // contract, over thousands of random shapes, under ASan / UBSan on the CPU.  A launch of the resident kernel starts a host
 // thread that plays the device's side of the doorbell protocol (gat_resident.h), so that gat_resident_*'s host side --
@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "gat_acq_kernels.h"
+#include "gat_array_kernels.h"
 #include "gat_ctx.h"
 #include "gat_internal.h"
 #include "hostsim.h"
@@ -308,6 +309,178 @@ hipError_t launch_acq_stats(const float *power, int P, int D, int J, const gat_a
         res[p].prn = prns[p];
     }
     (void)sink;
+    return hipSuccess;
+}
+
+// ---- the antenna-array path (gat_array.hip) -------------------------------------------------------------------------------
+// The covariance stand-ins check what cov_small_kernel / cov_tiled_kernel assume about CovArgs, walk the (estimate, workgroup,
+// unit) decomposition as CovArgs documents it, touch the first and last byte every unit reads of every antenna and plane, write
+// the whole slice of `partial` every workgroup owns, and count every (block, sample) in hostsim::cov_cover.
+static const float *cov_last_partial = nullptr; // the covariance launch's slices, for the finishing launch that follows
+static int cov_last_M = 0, cov_last_E = 0, cov_last_G = 0;
+
+static void cov_walk(const CovArgs &a, int fmt, const char *tag)
+{
+    const size_t sb = (size_t)layout_sample_bytes(fmt);
+    const bool planar = fmt == GAT_LAYOUT_PLANAR;
+    REQUIRE(fmt >= GAT_LAYOUT_PLANAR && fmt <= GAT_LAYOUT_INTERLEAVED_I8 && a.re && planar == (a.im != nullptr), "%s: layout %d", tag, fmt);
+    REQUIRE(a.M >= 1 && a.M <= GAT_MAX_ARRAY_ANTS && a.N >= 1 && a.B >= 1 && a.bpe >= 1 && a.E == (a.B + a.bpe - 1) / a.bpe, "%s: M %d N %lld B %d bpe %d E %d",
+            tag, a.M, a.N, a.B, a.bpe, a.E);
+    REQUIRE(a.splits >= 1 && a.seg_len >= 1 && (long long)a.splits * a.seg_len >= a.N && (long long)(a.splits - 1) * a.seg_len < a.N,
+            "%s: %d segments of %lld for N %lld (an empty segment would add the block's tail again)", tag, a.splits, a.seg_len, a.N);
+    REQUIRE(a.G >= 1 && (long long)a.G * a.E <= 0x7fffffffll, "%s: grid of %d x %d workgroups", tag, a.G, a.E);
+    REQUIRE((a.M == 1 || a.ant_stride >= 1) && (a.B == 1 || a.block_stride >= 1) && a.partial != nullptr, "%s: strides %lld / %lld", tag, a.ant_stride,
+            a.block_stride);
+    if (a.splits > 1) ++counters.cov_split_launches;
+    if ((long long)std::min(a.bpe, a.B) * a.splits > a.G) ++counters.cov_multi_unit_launches;
+    auto &cv = hostsim::cov_cover;
+    // block 0 of this launch within the call (the entry point offsets the planes by whole blocks from one batch to the next)
+    const long long byte_off = static_cast<const char *>(a.re) - static_cast<const char *>(cv.re);
+    const long long blk_bytes = cv.block_stride * (long long)sb;
+    const long long first_block = blk_bytes > 0 ? byte_off / blk_bytes : 0;
+    REQUIRE(byte_off >= 0 && (blk_bytes > 0 ? byte_off % blk_bytes == 0 : byte_off == 0) && a.N == cv.N && a.block_stride == cv.block_stride &&
+                first_block + a.B <= cv.B,
+            "%s: launch of %d blocks %lld bytes into a call of %d blocks", tag, a.B, byte_off, cv.B);
+    if (counters.violations) return; // (do not walk a decomposition that is already known to be wrong)
+    const size_t slice = (size_t)2 * a.M * a.M;
+    volatile long sink = 0;
+    for (int e = 0; e < a.E; ++e) {
+        const int b0 = e * a.bpe, nb = std::min(a.bpe, a.B - b0);
+        const long long units = (long long)nb * a.splits;
+        for (int g = 0; g < a.G; ++g) {
+            for (long long u = g; u < units; u += a.G) {
+                const int b = b0 + (int)(u / a.splits);
+                const long long n0 = (u % a.splits) * a.seg_len, n1 = std::min(n0 + a.seg_len, a.N);
+                for (int m = 0; m < a.M; ++m) {
+                    const size_t s0 = (size_t)b * (size_t)a.block_stride + (size_t)m * (size_t)a.ant_stride;
+                    const unsigned char *r = static_cast<const unsigned char *>(a.re) + s0 * sb;
+                    sink = sink + r[(size_t)n0 * sb] + r[(size_t)n1 * sb - 1];
+                    if (planar) {
+                        const unsigned char *q = static_cast<const unsigned char *>(a.im) + s0 * sb;
+                        sink = sink + q[(size_t)n0 * sb] + q[(size_t)n1 * sb - 1];
+                    }
+                }
+                unsigned char *row = cv.seen.data() + (size_t)(first_block + b) * (size_t)a.N;
+                for (long long n = n0; n < n1; ++n)
+                    if (row[n] < 255) ++row[n];
+            }
+            std::memset(a.partial + ((size_t)e * a.G + g) * slice, 0, slice * sizeof(float));
+        }
+    }
+    (void)sink;
+    cov_last_partial = a.partial;
+    cov_last_M = a.M, cov_last_E = a.E, cov_last_G = a.G;
+}
+
+hipError_t launch_cov_small(const CovArgs &a, int fmt, hipStream_t)
+{
+    ++counters.cov_small_launches;
+    const long long vs = layout_vec_samples(fmt);
+    const size_t sb = (size_t)layout_sample_bytes(fmt);
+    REQUIRE(a.M >= 1 && a.M <= kCovSmallMaxAnts, "streaming covariance: %d antennas", a.M);
+    REQUIRE(a.seg_len % vs == 0, "streaming covariance: segments of %lld samples, loads of %lld", a.seg_len, vs);
+    bool aligned = true; // every (block, antenna) start, in each plane
+    for (int b = 0; b < a.B && aligned; ++b)
+        for (int m = 0; m < a.M && aligned; ++m) {
+            const size_t off = ((size_t)b * (size_t)a.block_stride + (size_t)m * (size_t)a.ant_stride) * sb;
+            aligned = ((reinterpret_cast<uintptr_t>(a.re) + off) & 15u) == 0 && (!a.im || ((reinterpret_cast<uintptr_t>(a.im) + off) & 15u) == 0);
+        }
+    REQUIRE(aligned, "streaming covariance: a block of an antenna starts off a 16-byte boundary (strides %lld / %lld)", a.ant_stride, a.block_stride);
+    cov_walk(a, fmt, "streaming covariance");
+    return hipSuccess;
+}
+
+hipError_t launch_cov_tiled(const CovArgs &a, int fmt, hipStream_t)
+{
+    ++counters.cov_tiled_launches;
+    const CovTileGeom geo = cov_tile_geom(std::max(1, std::min(a.M, (int)GAT_MAX_ARRAY_ANTS)));
+    REQUIRE(geo.lds_bytes <= 64 * 1024 && (size_t)geo.chunk * geo.row * 8 <= geo.lds_bytes && (size_t)kCovTileThreads * 16 * sizeof(float) <= geo.lds_bytes,
+            "tiled covariance: %zu bytes of LDS for M %d", geo.lds_bytes, a.M);
+    REQUIRE(geo.phases >= 1 && geo.per_phase >= 1 && geo.tiles * geo.phases <= kCovTileThreads && geo.chunk == geo.phases * geo.per_phase &&
+                geo.row >= geo.nt * kCovTile && geo.nt * kCovTile >= a.M && geo.row % 2 == 0,
+            "tiled covariance: geometry %d tiles x %d phases, rows of %d for M %d", geo.tiles, geo.phases, geo.row, a.M);
+    cov_walk(a, fmt, "tiled covariance");
+    return hipSuccess;
+}
+
+hipError_t launch_cov_finish(const float *partial, int M, int E, int G, float *cov_re, float *cov_im, hipStream_t)
+{
+    ++counters.cov_finish_launches;
+    REQUIRE(partial && partial == cov_last_partial && M == cov_last_M && E == cov_last_E && G == cov_last_G && cov_re && cov_im,
+            "covariance finish: %d x %d slices of M %d after a launch of %d x %d of M %d", E, G, M, cov_last_E, cov_last_G, cov_last_M);
+    const size_t slice = (size_t)2 * M * M;
+    volatile float sink = 0.f;
+    for (size_t s = 0; s < (size_t)E * G; ++s) sink = sink + partial[s * slice] + partial[s * slice + slice - 1];
+    (void)sink;
+    std::memset(cov_re, 0, (size_t)E * M * M * sizeof(float));
+    std::memset(cov_im, 0, (size_t)E * M * M * sizeof(float));
+    return hipSuccess;
+}
+
+// The launcher's signature carries no LDS request (gat_array.hip derives it from M and the mode), so what can be checked here
+// is only that the entry point asked for the larger LDS limit before it launched, and that M is within what that limit holds.
+static bool weights_lds_allowed = false;
+hipError_t array_weights_allow_lds()
+{
+    weights_lds_allowed = true;
+    return hipSuccess;
+}
+
+hipError_t launch_array_weights(const float *cov_re, const float *cov_im, int M, const double *steer_re, const double *steer_im, int K, int mode,
+                                double loading, double *scratch, double *w_re, double *w_im, hipStream_t)
+{
+    ++counters.array_weight_launches;
+    const bool conv = mode == GAT_BF_CONVENTIONAL, pinv = mode == GAT_BF_POWER_INVERSION;
+    REQUIRE(M >= 1 && M <= GAT_MAX_ARRAY_ANTS && K >= 1 && K <= 65535 && (conv || pinv || mode == GAT_BF_MVDR) && w_re && w_im && loading >= 0.0,
+            "weights: M %d K %d mode %d", M, K, mode);
+    REQUIRE(conv || (cov_re && cov_im && scratch), "weights: mode %d without a covariance or scratch", mode);
+    REQUIRE(pinv || (steer_re && steer_im), "weights: mode %d without steering vectors", mode);
+    REQUIRE(weights_lds_allowed, "weights: launched before array_weights_allow_lds (64 antennas need more than 64 KB of LDS)");
+    if (counters.violations) return hipSuccess;
+    volatile double sink = 0.0;
+    if (!conv) {
+        sink = sink + cov_re[0] + cov_re[(size_t)M * M - 1] + cov_im[0] + cov_im[(size_t)M * M - 1];
+        std::memset(scratch, 0, (size_t)2 * M * M * sizeof(double) + sizeof(int)); // l_re | l_im | ok
+    }
+    if (!pinv) sink = sink + steer_re[0] + steer_re[(size_t)K * M - 1] + steer_im[0] + steer_im[(size_t)K * M - 1];
+    (void)sink;
+    std::memset(w_re, 0, (size_t)K * M * sizeof(double));
+    std::memset(w_im, 0, (size_t)K * M * sizeof(double));
+    return hipSuccess;
+}
+
+hipError_t launch_beamform(const float *acc_re, const float *acc_im, long long rows, int K, int L, int M, const double *w_re, const double *w_im,
+                           float *out_re, float *out_im, hipStream_t)
+{
+    ++counters.beamform_launches;
+    REQUIRE(acc_re && acc_im && w_re && w_im && out_re && out_im && K >= 1 && L >= 1 && M >= 1 && rows >= 1 && rows % ((long long)K * L) == 0 &&
+                (rows + 255) / 256 <= 0x7fffffffll,
+            "beamform: %lld rows for K %d L %d M %d", rows, K, L, M);
+    if (counters.violations) return hipSuccess;
+    volatile double sink = acc_re[0] + acc_re[(size_t)rows * M - 1] + acc_im[0] + acc_im[(size_t)rows * M - 1];
+    sink = sink + w_re[0] + w_re[(size_t)K * M - 1] + w_im[0] + w_im[(size_t)K * M - 1];
+    (void)sink;
+    std::memset(out_re, 0, (size_t)rows * sizeof(float));
+    std::memset(out_im, 0, (size_t)rows * sizeof(float));
+    return hipSuccess;
+}
+
+hipError_t launch_tracking_update_weighted(const float *acc_re, const float *acc_im, int K, int M, const gat_loop_config &cfg, gat_loop_state *state,
+                                           const gat_channel_params *cur, gat_channel_params *next, const double *w_re, const double *w_im,
+                                           hipStream_t)
+{
+    ++counters.weighted_update_launches;
+    const int L = cfg.num_taps;
+    REQUIRE(acc_re && acc_im && state && cur && next && cur != next && w_re && w_im && K >= 1 && M >= 1, "weighted update: K %d M %d", K, M);
+    REQUIRE(L >= 1 && L <= GAT_MAX_TAPS && cfg.early_index >= 0 && cfg.early_index < L && cfg.prompt_index >= 0 && cfg.prompt_index < L &&
+                cfg.late_index >= 0 && cfg.late_index < L,
+            "weighted update: taps %d / %d / %d of %d", cfg.early_index, cfg.prompt_index, cfg.late_index, L);
+    if (counters.violations) return hipSuccess;
+    const size_t n = (size_t)K * L * M;
+    volatile double sink = acc_re[0] + acc_re[n - 1] + acc_im[0] + acc_im[n - 1] + w_re[0] + w_re[(size_t)K * M - 1] + w_im[0] + w_im[(size_t)K * M - 1];
+    sink = sink + state[0].pll_acc1 + state[K - 1].pll_acc1 + cur[0].code_freq_hz + cur[K - 1].code_freq_hz;
+    (void)sink;
+    for (int k = 0; k < K; ++k) next[k] = cur[k];
     return hipSuccess;
 }
 

@@ -1,5 +1,5 @@
 // main.cpp -- drives libgat's C ABI (the real gat_api.cpp, gat_planner.cpp, gat_group.cpp, gat_resident_api.cpp, gat_acq_api.cpp,
-// gat_codes.cpp and gat_version.cpp; not gat_array_api.cpp, whose launchers have no stand-ins yet) on the host-only stand-ins of
+// gat_array_api.cpp, gat_codes.cpp and gat_version.cpp) on the host-only stand-ins of
 // this directory, under AddressSanitizer + UndefinedBehaviorSanitizer:
 //   1. thousands of random correlate calls on L1 / L5 and random caller's tables (formats, alignments, ragged lengths, strides, tap lists, flags, options) -- every
 //      launch the planner emits is checked against the kernel's contract by fake_kernels.cpp; error paths must return
@@ -11,6 +11,10 @@
 //      selection: every valid call launches, with the launches the sorted taps' grouping asks for, covering every tap once;
 //   1b. random acquisition searches (gat_acq_api.cpp): valid and invalid configs, L1 / L5 tables, caller's grid or none --
 //      every launch is checked by fake_kernels.cpp, which touches every byte the kernels would; the host statistics on grids with ties;
+//   1d. random antenna-array calls (gat_array_api.cpp): covariances of every layout, antenna count, alignment and work split on
+//      simulated devices of 64 .. 512 CUs -- every (block, sample) must be read exactly once, the outputs written whole and
+//      nothing else --, refusals with their documented status and no launch, the estimate batch loop; weights, beamforming,
+//      the weighted update and the weighted native run (eager and graph);
 //   3. the resident correlator's host side against a host thread that plays the device: rings at random distances around
 //      the kernel's idle limit and call budget, park, code-table change, free, close, destroy with correlators still open --
 //      every call must return exactly what the emulated workgroups posted, summed by the host's second stage.
@@ -25,6 +29,7 @@
 #include <vector>
 
 #include "gat.h"
+#include "gat_array_kernels.h"
 #include "gat_ctx.h"
 #include "gat_internal.h"
 #include "hostsim.h"
@@ -547,6 +552,286 @@ int main(int argc, char **argv)
     const long acq_split = hostsim::counters.acq_split_launches.load() - acq_split0;
     std::printf("acquisition sweep: %ld calls launched, %ld rejected, %ld with G > 1 (%ld host statistics)\n", acq_launched, acq_rejected, acq_split, acq_stats_ok);
     EXPECT(acq_launched > calls / 16 && acq_rejected > calls / 64 && acq_split > calls / 64, "the acquisition sweep launched, rejected and split");
+
+    // ---- 1d. the antenna-array entry points (gat_array_api.cpp) ------------------------------------------------------------
+    {
+        const auto &ct = hostsim::counters;
+        auto cov_launches = [&]() { return ct.cov_small_launches.load() + ct.cov_tiled_launches.load() + ct.cov_finish_launches.load(); };
+        long arr_ok = 0, arr_rejected = 0, arr_split = 0, arr_multi = 0, arr_stream = 0, arr_batched = 0;
+        gat_ctx *shared = nullptr;
+        EXPECT(gat_create(0, GAT_OWN_STREAM, &shared) == GAT_OK, "context for the array sweep");
+        // one covariance call on real memory of exactly the signal's extent; returns the status
+        auto cov_call = [&](gat_ctx *c, int fmt, int M, long long N, int B, int bpe, long long as, long long bs, size_t mis, int bad) {
+            const size_t sb = (size_t)layout_sample_bytes(fmt);
+            const size_t extent = ((size_t)(M - 1) * (size_t)as + (size_t)(B - 1) * (size_t)bs + (size_t)N) * sb;
+            unsigned char *p_re = static_cast<unsigned char *>(std::malloc(extent + mis)), *p_im = fmt == 0 ? static_cast<unsigned char *>(std::malloc(extent + mis)) : nullptr;
+            p_re[mis] = 1, p_re[mis + extent - 1] = 1;
+            if (p_im) p_im[mis] = 1, p_im[mis + extent - 1] = 1;
+            gat_signal_desc sig = {p_re + mis, p_im ? p_im + mis : nullptr, fmt, M, N, as, bs, 0};
+            const int E = (B + bpe - 1) / bpe;
+            const size_t outs = (size_t)E * M * M;
+            float *c_re = static_cast<float *>(std::malloc(outs * sizeof(float))), *c_im = static_cast<float *>(std::malloc(outs * sizeof(float)));
+            std::memset(c_re, 0xff, outs * sizeof(float));
+            std::memset(c_im, 0xff, outs * sizeof(float));
+            const gat_signal_desc *sigp = &sig;
+            float *o_re = c_re, *o_im = c_im;
+            gat_ctx *cc = c;
+            int calls_B = B, calls_bpe = bpe;
+            int32_t want = GAT_OK;
+            switch (bad) { // one way to be wrong, or (0) none
+            case 1: sigp = nullptr, want = GAT_ERR_ARG; break;
+            case 2: o_re = nullptr, want = GAT_ERR_ARG; break;
+            case 3: o_im = nullptr, want = GAT_ERR_ARG; break;
+            case 4: cc = nullptr, want = GAT_ERR_ARG; break;
+            case 5: calls_B = (int)uni(-2, 0), want = GAT_ERR_ARG; break;
+            case 6: calls_bpe = (int)uni(-2, 0), want = GAT_ERR_ARG; break;
+            case 7: sig.layout = (int)pick<long long>({-1, 4, 17}), want = GAT_ERR_ARG; break;
+            case 8: sig.im = fmt == 0 ? nullptr : (void *)p_re, want = GAT_ERR_ARG; break; // planar without im, interleaved with one
+            case 9: sig.num_ants = 65, want = GAT_ERR_RANGE; break;
+            case 10: sig.chan_stride = pick<long long>({1, -1, as}), want = GAT_ERR_UNSUPPORTED; break;
+            case 11: // zero (or negative) strides where the signal has several antennas or blocks
+                if (M > 1 && (B == 1 || uni(0, 1))) sig.ant_stride = -uni(0, 1);
+                else if (B > 1) sig.block_stride = -uni(0, 1);
+                else sig.num_samples = 0;
+                want = GAT_ERR_ARG;
+                break;
+            case 12: // an extent no double holds exactly
+                if (B > 1) sig.block_stride = 9100000000000000ll;
+                else if (M > 1) sig.ant_stride = 9100000000000000ll;
+                else sig.num_samples = 9100000000000000ll;
+                want = GAT_ERR_RANGE;
+                break;
+            case 13: sig.num_ants = (int)uni(-1, 0), want = GAT_ERR_ARG; break;
+            case 14: sig.re = nullptr, want = GAT_ERR_ARG; break;
+            default: break;
+            }
+            hostsim::cov_cover.reset(sig.re, B, N, bs);
+            const long l0 = cov_launches(), small0 = ct.cov_small_launches, split0 = ct.cov_split_launches, multi0 = ct.cov_multi_unit_launches, fin0 = ct.cov_finish_launches;
+            const long mallocs0 = ct.mallocs;
+            const int32_t rc = gat_spatial_covariance(cc, sigp, calls_B, calls_bpe, o_re, o_im);
+            EXPECT(rc == want, "covariance (case %d): status %d, want %d (%s): layout %d M %d N %lld B %d bpe %d strides %lld / %lld mis %zu", bad, rc, want,
+                   c ? gat_last_error(c) : "", fmt, M, N, B, bpe, as, bs, mis);
+            if (want != GAT_OK) {
+                EXPECT(cov_launches() == l0 && ct.mallocs == mallocs0, "covariance (case %d): a refused call launched or allocated", bad);
+                ++arr_rejected;
+            } else if (rc == GAT_OK) {
+                ++arr_ok;
+                const bool vec = ct.cov_small_launches > small0;
+                const long long vs = layout_vec_samples(fmt);
+                const bool aligned = M <= gat::kCovSmallMaxAnts && mis % 16 == 0 && (M == 1 || as % vs == 0) && (B == 1 || bs % vs == 0);
+                EXPECT(vec == aligned && (ct.cov_tiled_launches + ct.cov_small_launches - (l0 - fin0)) == ct.cov_finish_launches - fin0,
+                       "covariance: streaming kernel %d for aligned %d (layout %d M %d strides %lld / %lld mis %zu)", (int)vec, (int)aligned, fmt, M, as, bs, mis);
+                arr_stream += vec;
+                arr_split += ct.cov_split_launches > split0;
+                arr_multi += ct.cov_multi_unit_launches > multi0;
+                arr_batched += ct.cov_finish_launches - fin0 > 1;
+                const auto &seen = hostsim::cov_cover.seen;
+                const size_t once = (size_t)std::count(seen.begin(), seen.end(), (unsigned char)1);
+                EXPECT(once == seen.size(), "covariance: %zu of %zu (block, sample) pairs read exactly once: layout %d M %d N %lld B %d bpe %d CUs %d", once, seen.size(),
+                       fmt, M, N, B, bpe, c->num_cus);
+                bool whole = true;
+                for (size_t i = 0; i < outs && whole; ++i) whole = c_re[i] == 0.0f && c_im[i] == 0.0f;
+                EXPECT(whole, "covariance: the outputs are not written whole (E %d M %d)", E, M);
+                EXPECT(gat_sync(c) == GAT_OK, "sync");
+            }
+            std::free(p_re);
+            std::free(p_im);
+            std::free(c_re);
+            std::free(c_im);
+            return rc;
+        };
+        for (int it = 0; it < calls; ++it) {
+            // three calls of four on a new context: its scratch is then exactly what the call asked for, and ASan sees a slice
+            // beyond it (a reused, larger scratch would hide that)
+            gat_ctx *c = shared;
+            if (it % 4) EXPECT(gat_create(0, GAT_OWN_STREAM, &c) == GAT_OK, "context for one array call");
+            c->num_cus = (int)pick<long long>({64, 80, 104, 128, 228, 256, 256, 304, 512}); // the simulated device's size: only this sweep's contexts
+            const int fmt = (int)uni(0, 3);
+            const size_t sb = (size_t)layout_sample_bytes(fmt);
+            const long long vs = layout_vec_samples(fmt);
+            int M = (int)(uni(0, 1) ? uni(1, 8) : uni(1, 64));
+            long long N = (long long)std::llround(std::exp(unif(0.0, std::log(300000.0))));
+            int B = (int)std::llround(std::exp(unif(0.0, std::log(6000.0))));
+            if (uni(0, 9) == 0) B = (int)uni(4100, 6000), N = uni(1, 40); // more blocks than any device wants workgroups
+            if (uni(0, 9) == 0) B = (int)uni(1, 3), N = uni(20000, 300000); // long blocks: split
+            while ((double)B * (double)N > 1.5e6 || (double)M * (double)B * (double)N * (double)sb > 24e6) { // bounded: table and signal
+                if (B > 1 && uni(0, 1)) B = (B + 1) / 2;
+                else if (N > 1) N = (N + 1) / 2;
+                else M = (M + 1) / 2;
+            }
+            const int bpe = (int)pick<long long>({1, 1, uni(1, B), uni(1, B), B, B + uni(1, 5)});
+            const bool tidy = uni(0, 2) != 0; // aligned base and strides of whole 16-byte loads: the streaming kernel where M <= 8
+            const size_t mis = tidy ? 0 : (size_t)pick<long long>({0, 1, 1, 3}) * sb;
+            long long bs = tidy ? (N + vs - 1) / vs * vs + vs * pick<long long>({0, 0, 1, 4}) : N + pick<long long>({0, 1, 3, 7});
+            if (B == 1 && uni(0, 3) == 0) bs = 0;
+            long long as = (B - 1) * bs + N;
+            as = tidy ? (as + vs - 1) / vs * vs + vs * pick<long long>({0, 0, 2}) : as + pick<long long>({0, 1, 5});
+            if (M == 1 && uni(0, 3) == 0) as = 0;
+            const int bad = uni(0, 7) == 0 ? (int)uni(1, 14) : 0;
+            cov_call(c, fmt, M, N, B, bpe, as, bs, mis, bad);
+            if (c != shared) EXPECT(gat_destroy(c) == GAT_OK, "destroy");
+        }
+        // The estimate batch loop: M = 64, one block of N = 1 per estimate, E = 8192 + 5 > e_max = 256 MB / 32 KB: two launches, the
+        // second with planes and outputs offset.  256 MB of scratch and 2 x 134 MB of outputs: fits comfortably here under ASan.
+        {
+            gat_ctx *c = nullptr;
+            EXPECT(gat_create(0, GAT_OWN_STREAM, &c) == GAT_OK, "context for the batch loop");
+            const long b0 = arr_batched;
+            EXPECT(cov_call(c, GAT_LAYOUT_INTERLEAVED_I8, 64, 1, 8192 + 5, 1, 8192 + 5 + 3, 1, 0, 0) == GAT_OK && arr_batched == b0 + 1, "covariance: the estimate batch loop");
+            EXPECT(gat_destroy(c) == GAT_OK, "destroy");
+        }
+
+        // weights, beamforming and the weighted update on real buffers of exactly the documented sizes
+        long w_ok = 0, w_rej = 0, bf_ok = 0, bf_rej = 0, up_ok = 0, up_rej = 0, run_ok = 0, run_rej = 0, run_replayed = 0;
+        const int n_other = std::max(40, calls / 8);
+        for (int it = 0; it < n_other; ++it) {
+            gat_ctx *c = shared;
+            if (it % 2) EXPECT(gat_create(0, GAT_OWN_STREAM, &c) == GAT_OK, "context for one weights call");
+            const int M = (int)pick<long long>({1, 2, 3, 5, 8, 9, 33, 63, 64, uni(1, 64)}), K = (int)pick<long long>({1, 1, 3, 64, 65, 1000, 65535, uni(1, 300)});
+            const int mode = (int)uni(0, 2);
+            std::vector<float> cre((size_t)M * M, 1.f), cim((size_t)M * M, 0.f);
+            std::vector<double> sre((size_t)K * M, 1.0), sim((size_t)K * M, 0.0), wre((size_t)K * M, -1.0), wim((size_t)K * M, -1.0);
+            const float *pcre = mode == GAT_BF_CONVENTIONAL && uni(0, 1) ? nullptr : cre.data(), *pcim = pcre ? cim.data() : nullptr;
+            const double *psre = mode == GAT_BF_POWER_INVERSION && uni(0, 1) ? nullptr : sre.data(), *psim = psre ? sim.data() : nullptr;
+            double *pwre = wre.data();
+            int cM = M, cK = K, cmode = mode;
+            double loading = pick<double>({0.0, 1e-3, 0.5});
+            int32_t want = GAT_OK;
+            switch (uni(0, 24)) {
+            case 0: cmode = (int)pick<long long>({-1, 3, 9}), want = GAT_ERR_ARG; break;
+            case 1: if (mode != GAT_BF_POWER_INVERSION) psim = nullptr, want = GAT_ERR_ARG; break;
+            case 2: if (mode != GAT_BF_CONVENTIONAL) pcre = nullptr, want = GAT_ERR_ARG; break;
+            case 3: loading = pick<double>({-1e-3, (double)NAN, (double)INFINITY}), want = GAT_ERR_ARG; break;
+            case 4: pwre = nullptr, want = GAT_ERR_ARG; break;
+            case 5: cK = (int)pick<long long>({0, -1}), want = GAT_ERR_ARG; break;
+            case 6: cM = 65, want = GAT_ERR_RANGE; break;
+            case 7: cK = 65536, want = GAT_ERR_RANGE; break;
+            default: break;
+            }
+            const long l0 = ct.array_weight_launches;
+            const int32_t rc = gat_array_weights(c, pcre, pcim, cM, psre, psim, cK, cmode, loading, pwre, wim.data());
+            EXPECT(rc == want, "weights: status %d, want %d (%s): M %d K %d mode %d", rc, want, gat_last_error(c), cM, cK, cmode);
+            if (want == GAT_OK && rc == GAT_OK) {
+                EXPECT(ct.array_weight_launches == l0 + 1 && std::all_of(wre.begin(), wre.end(), [](double v) { return v == 0.0; }) &&
+                           std::all_of(wim.begin(), wim.end(), [](double v) { return v == 0.0; }), "weights: launched once, the outputs written whole");
+                ++w_ok;
+            } else {
+                EXPECT(ct.array_weight_launches == l0, "weights: a refused call launched");
+                ++w_rej;
+            }
+            // beamform
+            const int B = (int)pick<long long>({1, 2, 5, 64}), L = (int)pick<long long>({1, 3, 5, 32}), Kb = std::min(K, 300);
+            const size_t rows = (size_t)B * Kb * L;
+            std::vector<float> are(rows * M, 1.f), aim(rows * M, 1.f), yre(rows, -1.f), yim(rows, -1.f);
+            int bB = B, bL = L;
+            const float *pare = are.data();
+            want = GAT_OK;
+            switch (uni(0, 14)) {
+            case 0: pare = nullptr, want = GAT_ERR_ARG; break;
+            case 1: bB = 0, want = GAT_ERR_ARG; break;
+            case 2: bL = -1, want = GAT_ERR_ARG; break;
+            default: break;
+            }
+            const long bl0 = ct.beamform_launches;
+            const int32_t rb = gat_beamform(c, pare, aim.data(), bB, Kb, bL, M, sre.data(), sim.data(), yre.data(), yim.data());
+            EXPECT(rb == want, "beamform: status %d, want %d", rb, want);
+            if (want == GAT_OK && rb == GAT_OK) {
+                EXPECT(ct.beamform_launches == bl0 + 1 && std::all_of(yre.begin(), yre.end(), [](float v) { return v == 0.f; }) &&
+                           std::all_of(yim.begin(), yim.end(), [](float v) { return v == 0.f; }), "beamform: launched once, the outputs written whole");
+                ++bf_ok;
+            } else {
+                EXPECT(ct.beamform_launches == bl0, "beamform: a refused call launched");
+                ++bf_rej;
+            }
+            // the weighted update: null weights are the unweighted launch
+            gat_loop_config cfg = {1e-3, 18.0, 1.0, fc, 1575.42e6, 0.0, 1.0, lc, L, 0, L / 2, L - 1};
+            std::vector<gat_loop_state> st((size_t)Kb);
+            std::vector<gat_channel_params> cur((size_t)Kb, gat_channel_params{1, 0, fc, 1000.0, 10.0, 0.0}), nxt((size_t)Kb);
+            std::vector<float> ure((size_t)Kb * L * M, 2.f), uim((size_t)Kb * L * M, 3.f);
+            const double *uw_re = sre.data(), *uw_im = sim.data();
+            int uK = Kb;
+            want = GAT_OK;
+            bool plain = false;
+            switch (uni(0, 14)) {
+            case 0: uw_im = nullptr, want = GAT_ERR_ARG; break;
+            case 1: uw_re = nullptr, want = GAT_ERR_ARG; break;
+            case 2: cfg.late_index = L, want = GAT_ERR_RANGE; break;
+            case 3: uK = 0, want = GAT_ERR_ARG; break;
+            case 4: uw_re = uw_im = nullptr, plain = true; break;
+            default: break;
+            }
+            const long ul0 = ct.weighted_update_launches, ol0 = ct.other_launches;
+            const int32_t ru = gat_tracking_update_weighted(c, ure.data(), uim.data(), uK, M, &cfg, st.data(), cur.data(), nxt.data(), uw_re, uw_im);
+            EXPECT(ru == want, "weighted update: status %d, want %d (%s)", ru, want, gat_last_error(c));
+            if (want == GAT_OK && ru == GAT_OK) {
+                EXPECT(plain ? (ct.other_launches == ol0 + 1 && ct.weighted_update_launches == ul0) : ct.weighted_update_launches == ul0 + 1, "weighted update: the launch");
+                ++up_ok;
+            } else {
+                EXPECT(ct.weighted_update_launches == ul0 && ct.other_launches == ol0, "weighted update: a refused call launched");
+                ++up_rej;
+            }
+            EXPECT(gat_sync(c) == GAT_OK, "sync");
+            if (c != shared) EXPECT(gat_destroy(c) == GAT_OK, "destroy");
+        }
+        // the weighted native run, eager and as a graph (the same arguments again: replayed), on the context that has the codes
+        {
+            const int K = 6, M = 4, L = 3, N = 20000, NB = 5;
+            int32_t sh[3];
+            EXPECT(gat_sample_shifts(L, N / 1e-3, fc, 0.5, sh) == GAT_OK, "sample shifts");
+            gat_signal_desc sig = {(void *)0x10000000, (void *)0x50000000, GAT_LAYOUT_PLANAR, M, N, (long long)N * NB, N, 0};
+            gat_loop_config cfg = {1e-3, 18.0, 1.0, fc, 1575.42e6, 0.0, 1.0, lc, L, 0, 1, 2};
+            void *state, *pa, *pb, *are, *aim, *wre, *wim;
+            gat_malloc(ctx, sizeof(gat_loop_state) * K, &state);
+            gat_memset(ctx, state, 0, sizeof(gat_loop_state) * K);
+            gat_malloc(ctx, sizeof(gat_channel_params) * K, &pa);
+            gat_malloc(ctx, sizeof(gat_channel_params) * K, &pb);
+            std::vector<gat_channel_params> p0(K, gat_channel_params{1, 0, fc, 1000.0, 10.0, 0.0});
+            gat_memcpy_h2d(ctx, pa, p0.data(), sizeof(gat_channel_params) * K);
+            gat_memcpy_h2d(ctx, pb, p0.data(), sizeof(gat_channel_params) * K);
+            gat_malloc(ctx, sizeof(float) * NB * K * L * M, &are);
+            gat_malloc(ctx, sizeof(float) * NB * K * L * M, &aim);
+            gat_memset(ctx, are, 0, sizeof(float) * NB * K * L * M);
+            gat_memset(ctx, aim, 0, sizeof(float) * NB * K * L * M);
+            gat_malloc(ctx, sizeof(double) * K * M, &wre);
+            gat_malloc(ctx, sizeof(double) * K * M, &wim);
+            gat_memset(ctx, wre, 0, sizeof(double) * K * M);
+            gat_memset(ctx, wim, 0, sizeof(double) * K * M);
+            int32_t is_b = 0;
+            const int reps = std::max(20, calls / 8);
+            for (int rep = 0; rep < reps; ++rep) {
+                const int nb = 1 + rep % 2 * (NB - 1); // (two block counts: their graphs stay in the LRU and are replayed)
+                const uint32_t flags = rep % 3 == 0 ? 0u : GAT_FLAG_GRAPH;
+                const bool bad = rep % 10 == 9, plain = rep % 10 == 4;
+                const long ul0 = ct.weighted_update_launches, g0 = ct.graph_launches, gi0 = ct.graphs;
+                const int32_t rr = gat_tracking_run_weighted(ctx, &sig, nb, K, L, sh, N / 1e-3, &cfg, (gat_loop_state *)state, (gat_channel_params *)pa,
+                                                             (gat_channel_params *)pb, (float *)are, (float *)aim, (long long)K * L * M, flags, &is_b,
+                                                             plain ? nullptr : (double *)wre, plain || bad ? nullptr : (double *)wim);
+                if (bad) {
+                    EXPECT(rr == GAT_ERR_ARG && ct.weighted_update_launches == ul0, "weighted run: one null weight plane returned %d", rr);
+                    ++run_rej;
+                    continue;
+                }
+                EXPECT(rr == GAT_OK && is_b == (nb & 1), "weighted run %d: %d (%s)", rep, rr, gat_last_error(ctx));
+                const long ul = ct.weighted_update_launches - ul0;
+                if (plain) EXPECT(ul == 0, "weighted run without weights launched %ld weighted updates", ul);
+                else if (!flags) EXPECT(ul == nb, "weighted run: %ld weighted updates for %d blocks", ul, nb);
+                else EXPECT((ul == 2 * nb && ct.graphs == gi0 + 1) || (ul == 0 && ct.graph_launches == g0 + 1), // recorded (one eager pass, one captured) or replayed
+                            "weighted graph run: %ld updates, %ld replays", ul, ct.graph_launches - g0);
+                run_replayed += !plain && flags && ul == 0;
+                ++run_ok;
+            }
+            EXPECT(run_replayed >= 3, "the weighted run's graphs were replayed (%ld times)", run_replayed);
+            EXPECT(gat_sync(ctx) == GAT_OK, "sync");
+            for (void *p : {state, pa, pb, are, aim, wre, wim}) gat_free(ctx, p);
+        }
+        EXPECT(gat_destroy(shared) == GAT_OK, "destroy");
+        std::printf("array sweep: %ld covariance calls launched, %ld rejected, %ld with splits > 1, %ld with more units than workgroups, %ld through the streaming kernel\n",
+                    arr_ok, arr_rejected, arr_split, arr_multi, arr_stream);
+        std::printf("array entry points: %ld / %ld weights, %ld / %ld beamform, %ld / %ld weighted updates, %ld / %ld weighted runs launched / rejected; %ld covariance calls in batches\n",
+                    w_ok, w_rej, bf_ok, bf_rej, up_ok, up_rej, run_ok, run_rej, arr_batched);
+        EXPECT(arr_ok > calls / 2 && arr_rejected > calls / 20 && arr_split > calls / 40 && arr_multi > calls / 40 && arr_stream > calls / 10 && arr_batched >= 1,
+               "the array sweep launched, rejected, split, looped over units and batched");
+    }
 
     // ---- 2. closed loop, stand-alone operators, groups ---------------------------------------------------------------------
     {

@@ -42,10 +42,11 @@ def make_samples(rng, M, ld, layout):
     return q(x.real) + 1j * q(x.imag)
 
 
-def run_covariance(g, x, layout, N, B, bpe, block_stride, offset=0, ant_pad=0):
+def run_covariance(g, x, layout, N, B, bpe, block_stride, offset=0, ant_pad=0, nan_ok=False):
     """x complex128 [M, ld] holding B blocks block_stride samples apart.  The device buffer puts antenna rows ld + ant_pad
     samples apart and starts `offset` samples into its allocation.  Two calls: returns the first result (complex128 [E, M, M])
-    after asserting that the second one has the same bits and that the matrix is exactly Hermitian."""
+    after asserting that the second one has the same bits and that the matrix is exactly Hermitian.  nan_ok: the samples
+    hold a NaN on purpose, and NaN elements count as equal to their NaN mirror."""
     import torch
     ctx = g.get_context()
     dev = ctx.device
@@ -76,7 +77,8 @@ def run_covariance(g, x, layout, N, B, bpe, block_stride, offset=0, ant_pad=0):
         outs.append((c_re.cpu().numpy(), c_im.cpu().numpy()))
     (re0, im0), (re1, im1) = outs
     assert re0.tobytes() == re1.tobytes() and im0.tobytes() == im1.tobytes(), "a repeat call gave other bits"
-    assert np.array_equal(re0, re0.transpose(0, 2, 1)) and np.array_equal(im0, -im0.transpose(0, 2, 1)), "not exactly Hermitian"
+    assert np.array_equal(re0, re0.transpose(0, 2, 1), equal_nan=nan_ok) and np.array_equal(im0, -im0.transpose(0, 2, 1), equal_nan=nan_ok), \
+        "not exactly Hermitian"
     diag = im0[:, np.arange(M), np.arange(M)]
     assert (diag == 0).all() and not np.signbit(diag).any(), "the diagonal's imaginary part is not +0"
     return re0.astype(np.float64) + 1j * im0.astype(np.float64)

@@ -45,7 +45,7 @@ def f32_cov(R):
     return R.real.astype(np.float32).astype(np.float64) + 1j * R.imag.astype(np.float32).astype(np.float64)
 
 
-CASES = [(M, jnr, sample) for M in (2, 4, 16, 64) for jnr, sample in ((0.0, False), (30.0, False), (50.0, False), (40.0, True))]
+CASES = [(M, jnr, sample) for M in (1, 2, 3, 4, 5, 8, 9, 16, 33, 63, 64) for jnr, sample in ((0.0, False), (30.0, False), (50.0, False), (40.0, True))]
 
 
 @pytest.mark.parametrize("M,jnr,sample", CASES)
@@ -70,6 +70,25 @@ def test_weights_match_numpy_solve(g, M, jnr, sample):
             if mode == g.GAT_BF_POWER_INVERSION:
                 assert (w[:, 0] == 1.0).all()
                 assert (w == w[0]).all()  # no steering vector: every channel gets the same weights
+
+
+@pytest.mark.parametrize("K", (1, 65, 1000))
+def test_weights_for_many_channels(g, K):
+    """K steering vectors on one factor: every row against numpy.linalg.solve at the tolerance and condition cap above"""
+    M = 8
+    rng = np.random.default_rng(2000 + K)
+    R = f32_cov(array_ref.jammer_covariance(M, 50.0, rng)[0])
+    assert np.linalg.cond(R) <= 1e7
+    a = np.exp(2j * np.pi * rng.uniform(0, 1, (K, M)))
+    for mode in (g.GAT_BF_MVDR, g.GAT_BF_POWER_INVERSION, g.GAT_BF_CONVENTIONAL):
+        for loading in (0.0, 1e-3):
+            rc, w = host_weights(g, R, a, mode, loading)
+            assert rc == 0 and w.shape == (K, M), (mode, rc)
+            ref = array_ref.weights(R, a, mode, loading)
+            err = np.linalg.norm(w - ref, axis=1) / np.linalg.norm(ref, axis=1)
+            assert err.max() <= 1e-8, (mode, loading, err.max())
+            if mode == g.GAT_BF_MVDR:
+                assert np.abs(np.sum(np.conj(w) * a, axis=1) - 1.0).max() <= 1e-12
 
 
 def test_power_inversion_needs_no_steering_and_conventional_no_covariance(g):
@@ -114,13 +133,13 @@ def test_weights_error_codes(g):
     assert lib.gat_array_weights_host(_vp(c_re), _vp(c_im), M, _vp(a_re), _vp(a_im), 1, 1, 0.0, None, _vp(w)) == 1  # null output
 
 
-def _loop_case(g, seed=4):
+def _loop_case(g, seed=4, K=5, M=3, L=3, taps=(0, 1, 2)):
+    """taps: (early, prompt, late) indices into the L taps"""
     L_ = g._lib
-    K, M, L = 5, 3, 3
     rng = np.random.default_rng(seed)
-    cfg = L_.LoopConfig(1e-3, 18.0, 2.0, 1.023e6, 1575.42e6, 1.0e5, 1.0, 1023, L, 0, 1, 2)
+    cfg = L_.LoopConfig(1e-3, 18.0, 2.0, 1.023e6, 1575.42e6, 1.0e5, 1.0, 1023, L, *taps)
     dop = rng.uniform(-3e3, 3e3, K)
-    cur = g.make_params(np.arange(K), 1.023e6 + dop * 1.023e6 / 1575.42e6, 1.0e5 + dop, rng.uniform(0, 1023, K), rng.uniform(0, 1, K), shape=(K,))
+    cur = g.make_params(np.arange(K) % 32, 1.023e6 + dop * 1.023e6 / 1575.42e6, 1.0e5 + dop, rng.uniform(0, 1023, K), rng.uniform(0, 1, K), shape=(K,))
     st = np.zeros(K, dtype=L_.LOOP_STATE_DTYPE)
     st["init_carrier_doppler_hz"] = dop
     st["carrier_doppler_hz"] = dop
@@ -139,6 +158,33 @@ def test_host_weighted_update_with_null_weights_is_the_unweighted_update(g):
         assert lib.gat_tracking_update_host_weighted(_vp(re), _vp(im), K, M, C.byref(cfg), _vp(st2), _vp(cur2), _vp(nxt2), None, None) == 0
         cur, nxt, cur2, nxt2 = nxt, cur, nxt2, cur2
         assert cur.tobytes() == cur2.tobytes() and st.tobytes() == st2.tobytes(), it
+
+
+LOOP_SHAPES = ((5, 3, 5, (4, 1, 0)), (200, 3, 3, (0, 1, 2)), (200, 16, 5, (3, 0, 2)), (1, 1, 5, (2, 4, 1)))
+
+
+@pytest.mark.parametrize("K,M,L,taps", LOOP_SHAPES)
+def test_host_weighted_update_tap_orders_and_channel_counts(g, K, M, L, taps):
+    """five taps with early, prompt and late out of order, 200 channels, one antenna: against the numpy restatement over
+    five updates, at the tolerances of the test below"""
+    lib = g.load_library()
+    _, _, _, rng, cfg, cur, st = _loop_case(g, seed=40 + K + L, K=K, M=M, L=L, taps=taps)
+    cfgd = {n: getattr(cfg, n) for n, _ in cfg._fields_}
+    nxt = cur.copy()
+    ostate = {n: st[n].copy() for n in st.dtype.names}
+    ocur = oracle.make_params(cur["prn"], cur["code_freq_hz"], cur["carrier_freq_hz"], cur["code_phase_chips"], cur["carrier_phase_cycles"])
+    w = (rng.standard_normal((K, M)) + 1j * rng.standard_normal((K, M))) / M
+    w_re, w_im = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
+    for it in range(5):
+        acc = (rng.standard_normal((K, L, M)) + 1j * rng.standard_normal((K, L, M))).astype(np.complex64) * 1000
+        re, im = np.ascontiguousarray(acc.real), np.ascontiguousarray(acc.imag)
+        assert lib.gat_tracking_update_host_weighted(_vp(re), _vp(im), K, M, C.byref(cfg), _vp(st), _vp(cur), _vp(nxt), _vp(w_re), _vp(w_im)) == 0
+        cur, nxt = nxt, cur
+        ocur, ostate = array_ref.tracking_update_weighted(acc, w, cfgd, ostate, ocur)
+        for f in ("code_freq_hz", "carrier_freq_hz", "code_phase_chips", "carrier_phase_cycles"):
+            assert np.allclose(cur[f], ocur[f], rtol=1e-12, atol=1e-9), (it, f)
+        for name in ostate:
+            assert np.allclose(st[name], ostate[name], rtol=1e-10, atol=1e-9), (it, name)
 
 
 def test_host_weighted_update_matches_numpy_restatement(g):

@@ -6,7 +6,8 @@ chip edges, carrier phases that round to a whole cycle, GPS L5 lengths).  Any re
 
 `make -C tests/hostsim run` does the same for the REST of the library's host code -- csrc/gat_api.cpp (validation, launch
 planning, scratch management, graph cache, device groups) and csrc/gat_resident_api.cpp (the resident correlator's host side) and csrc/gat_acq_api.cpp (the acquisition search's validation,
-work split and scratch carve-up) -- by linking it against a
+work split and scratch carve-up) and csrc/gat_array_api.cpp (the antenna-array entry points: validation, the covariance's work split and
+estimate batches) -- by linking it against a
 host-only stand-in of the HIP runtime ("device" memory = host memory: every copy size is checked) and of the kernel
 launchers, which check each planned launch against what the kernel assumes about its arguments (LDS carve-up, replica
 room, grid decode, tap tables) and play the device's side of the resident correlator's doorbell protocol in a thread."""
@@ -51,3 +52,13 @@ def test_library_host_code_on_a_simulated_device_under_asan_ubsan():
     # ... and through the acquisition search's host side (csrc/gat_acq_api.cpp): launches, rejections and split grids
     m = re.search(r"acquisition sweep: (\d+) calls launched, (\d+) rejected, (\d+) with G > 1", out)
     assert m and int(m.group(1)) > 150 and int(m.group(2)) > 150 and int(m.group(3)) > 50, out[-2000:]
+    # ... and through the antenna-array entry points (csrc/gat_array_api.cpp): every (block, sample) of every launched covariance
+    # read exactly once and its outputs written whole (checked per call), refusals without a launch, and the work split's regimes
+    # as shares of the launched calls.  Observed at CALLS=2500: 2168 / 333 / 665 / 292 / 832 on the default seed, 2215 / 286 /
+    # 745 / 311 / 847 on seed 7; the shares asked for are about half the smaller of the two (0.31, 0.13 and 0.38 of the launched).
+    m = re.search(r"array sweep: (\d+) covariance calls launched, (\d+) rejected, (\d+) with splits > 1, (\d+) with more units than workgroups, "
+                  r"(\d+) through the streaming kernel", out)
+    assert m, out[-2000:]
+    launched, refused, split, multi_unit, streaming = (int(v) for v in m.groups())
+    assert launched > 1500 and refused > 150, out[-2000:]
+    assert split >= 0.15 * launched and multi_unit >= 0.065 * launched and streaming >= 0.19 * launched, out[-2000:]
