@@ -13,8 +13,8 @@ from ._lib import (GAT_FLAG_ATOMIC, GAT_LAYOUT_INTERLEAVED, GAT_LAYOUT_INTERLEAV
 from .acquisition import AcquisitionResult, acquire, acquisition_stats_host, tracking_init  # noqa: F401
 from .algorithms import (ALGODICT, ALGODICTINV, MEMDICT, REDDICT, KernelAlgorithm, ReductionAlgorithm,  # noqa: F401
                          ReplicaAlgorithm, cpu_reduce_partial_sum, cuda_reduce_partial_sum, kernel_algorithm)
-from .array import (GAT_BF_CONVENTIONAL, GAT_BF_MVDR, GAT_BF_POWER_INVERSION, beamform, beamformer_weights,  # noqa: F401
-                    spatial_covariance)
+from .array import (GAT_BF_CONVENTIONAL, GAT_BF_MVDR, GAT_BF_POWER_INVERSION, beamform, beamform_samples,  # noqa: F401
+                    beamformer_weights, spatial_covariance)
 from .benchmarks import (add_metadata, add_results, algorithmic_bytes, build_stream,  # noqa: F401
                          run_kernel_benchmark, run_reduction_benchmark, run_replica_benchmark, stream_scenario)
 from .context import Context, ResidentCorrelator, get_context  # noqa: F401

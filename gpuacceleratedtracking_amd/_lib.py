@@ -48,7 +48,7 @@ EXPORTS = [
     "gat_acquire", "gat_acq_stats_host",
     # antenna-array processing: spatial covariance, beamformer weights, beamformed accumulators and loop
     "gat_spatial_covariance", "gat_array_weights", "gat_array_weights_host", "gat_beamform", "gat_tracking_update_weighted",
-    "gat_tracking_update_host_weighted", "gat_tracking_run_weighted",
+    "gat_tracking_update_host_weighted", "gat_tracking_run_weighted", "gat_beamform_samples",
 ]
 
 
@@ -225,6 +225,7 @@ def load(build_if_missing: bool = True):
         "gat_array_weights": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, dbl, vp, vp]),
         "gat_array_weights_host": (i32, [vp, vp, i32, vp, vp, i32, i32, dbl, vp, vp]),
         "gat_beamform": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "gat_beamform_samples": (i32, [vp, sp, i32, vp, vp, i32, sp]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

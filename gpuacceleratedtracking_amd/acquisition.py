@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .array import beamform_desc
 from .context import Context, get_context
 from .gen_signal import make_params
 from .signals import GNSSSystem, get_code_frequency
@@ -64,13 +65,21 @@ def acquire(system: GNSSSystem, signal, sampling_frequency: float, prns=range(32
             interm_freq: float = 0.0, max_doppler: float = 7000.0, doppler_step: float | None = None, dopplers=None,
             code_step_chips: float = 0.5, first_shift: int = 0, num_code_bins: int | None = None, num_blocks: int = 1,
             block_stride: int | None = None, min_peak_ratio: float = 2.0, keep_power: bool = False,
-            ctx: Context | None = None, device=None) -> list[AcquisitionResult]:
+            ctx: Context | None = None, device=None, weights=None) -> list[AcquisitionResult]:
     """Search ``prns`` (code-table columns, 0-based) in ``num_blocks`` blocks of ``num_samples`` samples (default: one
     code period) starting at sample 0 of ``signal``, ``block_stride`` apart (default ``num_samples``).
 
     Grid defaults: code step s = max(1, round(code_step_chips * fs / fc)) samples, J = ceil(Lc * fs / (fc * s)) bins (one
     code period) from ``first_shift``; Doppler -max_doppler .. +max_doppler in steps of 1 / (2 N / fs), or the evenly
-    spaced ``dopplers`` given (Hz, relative to ``interm_freq``).  Returns one AcquisitionResult per PRN, in order."""
+    spaced ``dopplers`` given (Hz, relative to ``interm_freq``).  Returns one AcquisitionResult per PRN, in order.
+
+    ``weights`` (complex ``[J, M]`` or ``[M]``, e.g. ``beamformer_weights(R, mode="power_inversion")``): the blocks searched
+    are first beamformed (``array.beamform_samples``'s ``beamform_desc``, into a buffer that lives for this call) and the search runs on the J
+    beams, non-coherently over them as it is over antennas.  The search adds antennas as |R|^2, so a jammer that is coherent
+    across them enters at full strength; a beam with a null towards it does not.  With power-inversion weights the result's
+    ``CN0``, ``noise_power`` and ``signal_power`` are those of the beam's output (its noise is sum |w_m|^2 times one
+    antenna's, and the satellite's gain is whatever the null leaves), not of an antenna.  ``weights=None``: the search on
+    the antennas as they are."""
     ctx = ctx if ctx is not None else get_context(device)
     ctx.set_codes(system.codes)
     fs = float(sampling_frequency)
@@ -95,6 +104,10 @@ def acquire(system: GNSSSystem, signal, sampling_frequency: float, prns=range(32
     prn_arr = np.ascontiguousarray(np.asarray(list(prns) if not isinstance(prns, np.ndarray) else prns, dtype=np.int32).reshape(-1))
     P = int(prn_arr.size)
     desc = _as_desc(signal, N, int(num_blocks), bstride)
+    if weights is not None:
+        if desc.chan_stride != 0:
+            raise ValueError("weights need one signal for all channels (chan_stride 0)")
+        beams, desc = beamform_desc(ctx, desc, weights, int(num_blocks), zero=False)  # `beams` lives until gat_acquire has returned
 
     cfg = _lib.AcqConfig()
     cfg.struct_size = C.sizeof(_lib.AcqConfig)

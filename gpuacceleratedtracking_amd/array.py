@@ -1,10 +1,11 @@
 """Antenna-array processing on device tensors (include/gat.h, "antenna-array processing"): the spatial covariance of the raw
-samples, beamformer weights from it, and the weights applied to correlator accumulators.
+samples, beamformer weights from it, and the weights applied to correlator accumulators or to the raw samples.
 
 Correlation is linear, so a beam or a null is applied to the accumulators the correlators already return:
 ``w^H (sum_n x_n c_n) = sum_n (w^H x_n) c_n``.  A receiver estimates ``R = spatial_covariance(signal, N, B)``, turns it into
 ``w = beamformer_weights(R, steering)`` and hands ``w`` to ``TrackingLoop(weights=w)`` (or to ``beamform`` for accumulators
-it already has).  Everything runs in libgat's HIP kernels; there is no CPU fallback."""
+it already has).  ``beamform_samples`` applies the weights before correlation instead, ``y[n] = w^H x[n]``: the beam is a
+signal of its own, which is what the acquisition search needs under a jammer (``acquire(..., weights=w)``).  Everything runs in libgat's HIP kernels; there is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
@@ -107,3 +108,51 @@ def beamform(acc_re: torch.Tensor, acc_im: torch.Tensor, weights: torch.Tensor, 
     y_im = torch.empty_like(y_re)
     ctx.check(ctx.lib.gat_beamform(ctx._h, _vp(a_re), _vp(a_im), B, K, L, M, _vp(w_re), _vp(w_im), _vp(y_re), _vp(y_im)), "gat_beamform")
     return y_re, y_im
+
+
+def beamform_desc(ctx: Context, desc: _lib.SignalDesc, weights: torch.Tensor, num_blocks: int, out_block_stride: int | None = None,
+                  interleaved: bool = False, zero: bool = True):
+    """``gat_beamform_samples`` of the ``num_blocks`` blocks a signal descriptor covers.  Returns ``(out, out_desc)``: the
+    tensors ``beamform_samples`` returns, and the descriptor of them as a J-antenna signal (it points into ``out``: keep both).
+    ``zero=False`` leaves what the kernel does not write uninitialised (no gaps to fill when blocks are back to back)."""
+    N, M, nb = int(desc.num_samples), int(desc.num_ants), int(num_blocks)
+    w = weights.reshape(1, -1) if weights.dim() == 1 else weights
+    if w.dim() != 2 or int(w.shape[1]) != M:
+        raise ValueError("weights must be [J, M] or [M]")
+    J = int(w.shape[0])
+    ostride = N if out_block_stride is None else int(out_block_stride)
+    if ostride < N:
+        raise ValueError("out_block_stride shorter than num_samples")
+    w_re, w_im = _planes(w.to(ctx.device), torch.float64)
+    ld = nb * ostride
+    alloc = torch.zeros if zero else torch.empty
+    if interleaved:
+        out = alloc((J, ld, 2), dtype=torch.float32, device=ctx.device)
+        odesc = _lib.SignalDesc(out.data_ptr(), None, _lib.GAT_LAYOUT_INTERLEAVED, J, N, ld, ostride, 0)
+    else:
+        out = (alloc((J, ld), dtype=torch.float32, device=ctx.device), alloc((J, ld), dtype=torch.float32, device=ctx.device))
+        odesc = _lib.SignalDesc(out[0].data_ptr(), out[1].data_ptr(), _lib.GAT_LAYOUT_PLANAR, J, N, ld, ostride, 0)
+    ctx.check(ctx.lib.gat_beamform_samples(ctx._h, C.byref(desc), nb, _vp(w_re), _vp(w_im), J, C.byref(odesc)), "gat_beamform_samples")
+    return out, odesc
+
+
+def beamform_samples(signal, weights: torch.Tensor, num_samples: int, num_blocks: int = 1, start: int = 0, block_stride: int | None = None,
+                     out_block_stride: int | None = None, interleaved: bool = False, ctx: Context | None = None):
+    """Beams of the raw samples, ``y[j, n] = sum_m conj(w[j, m]) x[m, n]`` for every sample of ``num_blocks`` blocks.
+    ``signal`` as ``spatial_covariance`` takes it; ``weights`` complex (or real) ``[J, M]`` or ``[M]`` of any float dtype,
+    moved to the float64 planes ``beamformer_weights`` returns.  Returns ``(re, im)`` float32 ``[J, num_blocks *
+    out_block_stride]``, or with ``interleaved=True`` one tensor ``[J, num_blocks * out_block_stride, 2]``; block b starts
+    ``b * out_block_stride`` samples in (default: ``num_samples``; what a larger stride leaves between blocks is zero: the
+    allocation's, the kernel does not write there).  The result is a J-antenna signal for ``acquire``, ``spatial_covariance``
+    and the correlators.  float32 sums in antenna order: ``|y - y64| <= (4 M + 4) 2^-24 sum_m |w_m| |x_m|``."""
+    re, im = signal if isinstance(signal, (tuple, list)) else (signal, None)
+    nb, N = int(num_blocks), int(num_samples)
+    if nb < 1 or N < 1:
+        raise ValueError("num_blocks and num_samples must be positive")
+    stride = N if block_stride is None else int(block_stride)
+    ntot = re.shape[-2] if im is None else re.shape[-1]
+    if stride < 0 or start + (nb - 1) * stride + N > ntot:
+        raise ValueError("signal shorter than start + (num_blocks - 1) * block_stride + num_samples")
+    ctx = ctx if ctx is not None else get_context(re.device)
+    desc = _signal_desc(re, im, N, start=int(start), block_stride=stride)
+    return beamform_desc(ctx, desc, weights, nb, out_block_stride, interleaved)[0]

@@ -16,12 +16,14 @@ LIB = os.path.join(HERE, "libgat.so")
 SOURCES = ["gat_dc_f0.hip", "gat_dc_f1.hip", "gat_dc_f2.hip", "gat_dc_f3.hip", "gat_resident_f0.hip", "gat_resident_f1.hip",
            "gat_resident_f2.hip", "gat_resident_f3.hip",
            "gat_kernels.hip", "gat_mfma.hip", "gat_mfma_bf16.hip", "gat_api.cpp", "gat_planner.cpp", "gat_group.cpp",
-           "gat_resident_api.cpp", "gat_codes.cpp", "gat_acq.hip", "gat_acq_api.cpp", "gat_array.hip", "gat_array_api.cpp"]
+           "gat_resident_api.cpp", "gat_codes.cpp", "gat_acq.hip", "gat_acq_api.cpp", "gat_array.hip", "gat_array_api.cpp",
+           "gat_beam.hip", "gat_beam_api.cpp"]
 # gat_version.cpp is not in SOURCES: it is compiled at every link with the build's identity (git commit, flags)
 HEADERS = [os.path.join(CSRC, "gat_internal.h"), os.path.join(CSRC, "gat_phase.h"), os.path.join(CSRC, "gat_dc.h"),
            os.path.join(CSRC, "gat_dc_body.inc"), os.path.join(CSRC, "gat_resident.h"), os.path.join(CSRC, "gat_ctx.h"),
            os.path.join(CSRC, "gat_acq.h"), os.path.join(CSRC, "gat_acq_kernels.h"), os.path.join(CSRC, "gat_loop.h"),
-           os.path.join(CSRC, "gat_array.h"), os.path.join(CSRC, "gat_array_kernels.h"), os.path.join(ROOT, "include", "gat.h")]
+           os.path.join(CSRC, "gat_array.h"), os.path.join(CSRC, "gat_array_kernels.h"), os.path.join(CSRC, "gat_beam_kernels.h"),
+           os.path.join(ROOT, "include", "gat.h")]
 
 
 def hipcc_path() -> str:
@@ -122,7 +124,9 @@ def build_libgat(force: bool = False, verbose: bool = False, extra_flags: tuple[
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(sp), hdr_t):
             # the fused vector kernel is written with scalar FMAs on purpose (gat_dc.h): keep the SLP vectoriser from
             # re-packing them into v_pk_fma_f32 + operand-pairing moves
-            per_file = ("-fno-slp-vectorize",) if vector_tu else ()
+            # (the sample beamformer too: packed FMAs want operand pairs in vector registers -- with the vectoriser on,
+            # beam_stream_kernel<planar, 4, 4> takes 156 VGPRs instead of 124 and <int8, 8, 4> 256 with 8 spilled instead of 246)
+            per_file = ("-fno-slp-vectorize",) if vector_tu or src == "gat_beam.hip" else ()
             jobs.append([hipcc_path(), *_flags(tuple(extra_here) + per_file), "-c", sp, "-o", obj])
 
     def run(cmd):

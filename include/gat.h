@@ -404,7 +404,7 @@ GAT_API int32_t gat_set_vector_tiling(gat_ctx *ctx, int32_t max_antenna_tiles, i
  * GAT_ERR_ARG: unknown name; GAT_ERR_RANGE: value outside the option's range. */
 GAT_API int32_t gat_set_option(gat_ctx *ctx, const char *name, int64_t value);
 
-/* Launch geometry chosen for the last correlate call (diagnostics / DESIGN.md tables). */
+/* Launch geometry chosen for the last correlate call, or the last gat_beamform_samples call (diagnostics / DESIGN.md tables). */
 typedef struct gat_launch_info {
     int32_t workgroups, threads, splits, ant_tile, vec, lds_bytes, finalize_launched;
     int32_t matrix_core; /* 0: the vector kernel ran, 1: the f32-MFMA kernel, 2: the split-bf16 MFMA kernel */
@@ -605,7 +605,7 @@ GAT_API int32_t gat_acq_stats_host(const float *power_host, int32_t num_prns, in
                                    const gat_acq_config *config, double sampling_freq_hz, int64_t num_samples,
                                    gat_acq_result *results_host);
 
-/* ---- antenna-array processing: spatial covariance, beamformer weights, beamformed accumulators and loop -------------
+/* ---- antenna-array processing: spatial covariance, beamformer weights, beamformed samples, accumulators and loop ----
  * The correlators return accumulators per antenna; what an array receiver does with its antennas happens here.
  * Correlation is linear -- w^H (sum_n x_n c_n) = sum_n (w^H x_n) c_n -- so a beam or a null is applied to the
  * accumulators the correlators already produce: one pass over the raw samples estimates the spatial covariance, a small
@@ -651,6 +651,32 @@ GAT_API int32_t gat_array_weights_host(const float *cov_re_host, const float *co
 GAT_API int32_t gat_beamform(gat_ctx *ctx, const float *acc_re_dev, const float *acc_im_dev, int32_t num_blocks,
                              int32_t num_channels, int32_t num_taps, int32_t num_ants, const double *w_re_dev,
                              const double *w_im_dev, float *out_re_dev, float *out_im_dev);
+
+/* Beams of the raw samples: y[n, j, b] = sum_m conj(w[j][m]) * x[n, m, b], 0 <= j < num_beams.
+ * signal: any layout, 1 <= M <= GAT_MAX_ARRAY_ANTS, any N, base alignment and strides; chan_stride must be 0.
+ * w: dev double [num_beams][M] planar, as gat_array_weights writes it; 1 <= num_beams <= GAT_MAX_ARRAY_ANTS.
+ * out: describes device memory the call WRITES: layout GAT_LAYOUT_PLANAR or GAT_LAYOUT_INTERLEAVED (float32),
+ *      num_ants == num_beams, num_samples == signal->num_samples, its own ant_stride and block_stride, chan_stride 0;
+ *      beam j, block b, sample n goes to n + j*ant_stride + b*block_stride.  Nothing outside those elements is written.
+ * The output descriptor can be handed unchanged to gat_acquire, gat_spatial_covariance and the correlators: as given it is
+ * a num_beams-antenna signal; with num_ants = 1 and chan_stride = ant_stride it is one signal per channel (per-satellite
+ * beams, each channel correlated on ONE stream instead of M).  This is how a null reaches the acquisition search, which
+ * adds its antennas non-coherently and so takes a jammer at full strength.
+ * Arithmetic: the weights are narrowed to float32 once; the sum runs in antenna order 0 .. M-1 with one FMA per real
+ * product, in float32: |y - y64| <= (4M + 4) * 2^-24 * sum_m |w_m| |x_m| per sample.  The bits depend neither on the
+ * kernel nor on the work split; integer samples convert exactly; NaN weights (what gat_array_weights writes for a
+ * covariance that is not positive definite) give NaN samples and no error.  M <= 8 with every block of every antenna and of
+ * every beam starting on a 16-byte boundary streams the samples once with 16-byte loads and stores for up to 4 beams (a
+ * further pass per 4 more); everything else runs the scalar-load kernel (8 beams a pass).  gat_last_launch_info afterwards
+ * describes this call: vec = 4 (streaming) or 1, workgroups, threads, splits (chunks of a block), ant_tile = M.
+ * Enqueues on the context's stream and does not synchronise.  Refusals, all before any launch: GAT_ERR_ARG for null
+ * pointers, num_blocks or num_beams < 1, negative strides, out->num_ants != num_beams, out->num_samples !=
+ * signal->num_samples, a planar output without im or an interleaved one with im, and an output whose byte extent (either
+ * plane, computed from the descriptor) overlaps the input's; GAT_ERR_RANGE for M or num_beams above 64;
+ * GAT_ERR_UNSUPPORTED for an integer output layout or chan_stride != 0 on either side. */
+GAT_API int32_t gat_beamform_samples(gat_ctx *ctx, const gat_signal_desc *signal, int32_t num_blocks,
+                                     const double *w_re_dev, const double *w_im_dev, int32_t num_beams,
+                                     const gat_signal_desc *out);
 
 /* gat_tracking_update / gat_tracking_update_host / gat_tracking_run with the antenna sum of prompt, early and late
  * replaced by sum_m conj(w[k][m]) * R[m, tap]; w: double [K][M] planar (device memory for the device entry points, host

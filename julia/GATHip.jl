@@ -748,6 +748,23 @@ function beamform!(ctx::Context, acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, num_b
                      (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Cfloat}, Ptr{Cfloat}),
                      ctx.handle, acc_re, acc_im, Int32(num_blocks), Int32(K), Int32(L), Int32(M), w_re, w_im, out_re, out_im))
 end
+# beams of the raw samples, y[n, j, b] = sum_m conj(w[m, j]) x[n, m, b]: `out` describes the device memory the call writes
+# (GAT_LAYOUT_PLANAR or GAT_LAYOUT_INTERLEAVED, num_ants = num_beams, num_samples = desc.num_samples, chan_stride 0) and is
+# afterwards a signal for acquire!, spatial_covariance! and the correlators.  w [M x num_beams] Float64 planes on the device.
+function beamform_samples!(ctx::Context, desc::SignalDesc, num_blocks::Integer, w_re::Ptr{Float64}, w_im::Ptr{Float64}, num_beams::Integer,
+                           out::SignalDesc)
+    check(ctx, ccall((:gat_beamform_samples, libgat), Int32,
+                     (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ref{SignalDesc}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), w_re, w_im, Int32(num_beams), Ref(out)))
+    out
+end
+# the same with the planar output described here: out_re / out_im device Float32, beam j at j * out_ant_stride, block b at
+# b * out_block_stride (default: blocks back to back)
+function beamform_samples(ctx::Context, desc::SignalDesc, num_blocks::Integer, w_re::Ptr{Float64}, w_im::Ptr{Float64}, num_beams::Integer,
+                          out_re::Ptr{Cvoid}, out_im::Ptr{Cvoid}, out_ant_stride::Integer, out_block_stride::Integer = desc.num_samples)
+    out = SignalDesc(out_re, out_im, Int32(0), Int32(num_beams), desc.num_samples, Int64(out_ant_stride), Int64(out_block_stride), Int64(0))
+    beamform_samples!(ctx, desc, num_blocks, w_re, w_im, num_beams, out)
+end
 # tracking_update! / tracking_update_host! / tracking_run! with weights [M x K] (C_NULL planes: the unweighted calls)
 function tracking_update_weighted!(ctx::Context, acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, K::Integer, M::Integer, cfg::LoopConfig,
                                    state_dev::Ptr{Cvoid}, cur_dev::Ptr{Cvoid}, next_dev::Ptr{Cvoid}, w_re::Ptr{Float64}, w_im::Ptr{Float64})

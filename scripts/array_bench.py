@@ -1,5 +1,5 @@
-"""Timings of the spatial covariance kernels (include/gat.h gat_spatial_covariance) on the device, next to their yardsticks
-in the same run:
+"""Timings of the spatial covariance kernels (include/gat.h gat_spatial_covariance) and of the sample beamformer
+(gat_beamform_samples) on the device, next to their yardsticks in the same run:
 
   small arrays -- the headline stream (M = 4, B = 4096 x N = 20000; planar float 2.62 GB, then int16 and int8 pairs): the
       covariance, the headline correlator and the read-only kernel (gat_debug_read_stream, best variant) over the same
@@ -10,7 +10,11 @@ in the same run:
       and its share of the FP32 vector roof (8 M (M + 1) / 2 flop per sample over 157.3 TFLOP/s), and, reported only,
       torch.view_as_complex(x) @ x.mH on the interleaved layout.
 
-  python scripts/array_bench.py [--out profiles/array/array_bench.json] [--only small|large|trace] [--settle 64] [--steps 30]
+  beams -- the headline stream in the three ingest formats into 1 and 4 planar beams (the streaming kernel), and the M = 16
+      and M = 64 signals into 1 and 4 beams (the general kernel): ms, GB/s over the algorithmic bytes in_bytes * M + 8 * beams
+      per sample, and that rate over the reader's of the same run.  Reported, not required.
+
+  python scripts/array_bench.py [--out profiles/array/array_bench.json] [--only small|large|beams|trace] [--settle 64] [--steps 30]
 --only trace: a few launches of every measured covariance shape and nothing else, for a rocprofv3 --kernel-trace --stats (or
 --pmc) run of its own.  Exit status 1 when the small-array requirement is missed."""
 from __future__ import annotations
@@ -74,6 +78,55 @@ def small(g, settle, steps):
     return rows
 
 
+def beams_call(g, ctx, desc, B, M, J, N):
+    """gat_beamform_samples of `desc` into J planar beams, blocks back to back; random weights"""
+    import torch
+    gen = torch.Generator().manual_seed(J * 100 + M)
+    w_re = torch.randn((J, M), generator=gen, dtype=torch.float64).to(ctx.device)
+    w_im = torch.randn((J, M), generator=gen, dtype=torch.float64).to(ctx.device)
+    ld = B * N
+    o_re = torch.empty((J, ld), dtype=torch.float32, device=ctx.device)
+    o_im = torch.empty_like(o_re)
+    out = g._lib.SignalDesc(o_re.data_ptr(), o_im.data_ptr(), 0, J, N, ld, N, 0)
+    fn, args = ctx.lib.gat_beamform_samples, (ctx._h, C.byref(desc), B, C.c_void_p(w_re.data_ptr()), C.c_void_p(w_im.data_ptr()), J, C.byref(out))
+
+    def launch(_keep=(w_re, w_im, o_re, o_im, out, desc)):
+        rc = fn(*args)
+        if rc != 0:
+            ctx.check(rc, "gat_beamform_samples")
+    return launch
+
+
+BEAMS = (("planar float", ("GPSL1", 20000, 4, 3, 1, 4096), 0, {}), ("int16 pairs", ("GPSL1", 20000, 4, 3, 1, 4096), 2, {}),
+         ("int8 pairs", ("GPSL1", 20000, 4, 3, 1, 4096), 3, {}), ("ComplexF32 pairs", ("GPSL1", 50000, 16, 3, 32, 128), 1, {}),
+         ("ComplexF32 pairs", ("GPSL1", 2000000, 64, 3, 64, 1), 1, dict(block_seconds=20e-3)))
+
+
+def beams(g, settle, steps):
+    import torch
+    rows = []
+    for name, args, layout, kw in BEAMS:
+        _, N, M, L, K, B = args
+        op, desc, sig, prm = g.build_stream(*args, layout=layout, **kw)
+        ctx = op.ctx
+        rbytes = sig[0].numel() * sig[0].element_size()
+        t_read = min(float(np.median(ctx.read_stream_ms(sig[0], rbytes, variant=v, launches=7)[1:])) for v in (0, 1, 2, 4, 8))
+        read_rate = rbytes / t_read / 1e6
+        t_cov = median_ms(ctx, covariance_call(g, ctx, desc, B, M), settle, steps)
+        for J in (1, 4):
+            t = median_ms(ctx, beams_call(g, ctx, desc, B, M, J, N), settle, steps)
+            info = ctx.last_launch_info()
+            nbytes = B * N * (M * g.SAMPLE_BYTES[layout] + 8 * J)
+            rows.append(dict(shape=f"M={M} B={B} N={N} {name}", beams=J, kernel="streaming" if info["vec"] == 4 else "general", bytes=nbytes,
+                             beams_ms=t, beams_GBps=nbytes / t / 1e6, reader_GBps=read_rate, beams_fraction_of_read_ceiling=nbytes / t / 1e6 / read_rate,
+                             covariance_ms=t_cov, beams_over_covariance_time=t / t_cov,
+                             byte_ratio_to_covariance=nbytes / (B * N * M * g.SAMPLE_BYTES[layout])))
+            print(json.dumps(rows[-1]), flush=True)
+        del op, desc, sig
+        torch.cuda.empty_cache()
+    return rows
+
+
 LARGE = (("configs[3] signal", ("GPSL1", 50000, 16, 3, 32, 128), {}), ("configs[4] signal", ("GPSL1", 2000000, 64, 3, 64, 1), dict(block_seconds=20e-3)))
 
 
@@ -124,7 +177,7 @@ def trace(g):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "array", "array_bench.json"))
-    ap.add_argument("--only", choices=("small", "large", "trace"))
+    ap.add_argument("--only", choices=("small", "large", "beams", "trace"))
     ap.add_argument("--settle", type=int, default=64)
     ap.add_argument("--steps", type=int, default=30)
     a = ap.parse_args()
@@ -142,6 +195,8 @@ def main():
         res["small_arrays"] = small(g, a.settle, a.steps)
     if a.only in (None, "large"):
         res["large_arrays"] = large(g, a.settle, a.steps)
+    if a.only in (None, "beams"):
+        res["sample_beams"] = beams(g, a.settle, a.steps)
     ok = True
     if "small_arrays" in res:
         ok = res["small_arrays"][0]["covariance_GBps"] * 1.12 >= res["small_arrays"][0]["reader_GBps"]
