@@ -20,6 +20,8 @@ from .benchmarks import (add_metadata, add_results, algorithmic_bytes, build_str
 from .context import Context, ResidentCorrelator, get_context  # noqa: F401
 from .correlator import (EarlyPromptLateCorrelator, NumAccumulators, NumAnts, get_accumulators,  # noqa: F401
                          get_correlator_sample_shifts, get_num_accumulators, get_num_ants)
+from .frontend import (GAT_COND_BLANK_ALL_ANTS, SampleStats, agc_params, agc_params_host, condition_samples,  # noqa: F401
+                       condition_samples_host, requantize, sample_stats)
 from .gen_signal import StructSignal, gen_blank_signal, gen_signal, gen_signal_stream, make_params  # noqa: F401
 from .loop import ResidentTrackingLoop, TrackingLoop  # noqa: F401
 from .sharding import DeviceGroup, ShardPlan, gather_outputs, shard_channels, shard_params  # noqa: F401

@@ -26,6 +26,8 @@ GAT_MC_VECTOR, GAT_MC_AUTO, GAT_MC_F32, GAT_MC_BF16_SPLIT = 0, 1, 2, 3
 # antenna-array processing (gat_array_weights modes; the array functions' antenna limit)
 GAT_BF_CONVENTIONAL, GAT_BF_MVDR, GAT_BF_POWER_INVERSION = 0, 1, 2
 GAT_MAX_ARRAY_ANTS = 64
+# sample conditioning (gat_condition_samples / gat_sample_stats flags)
+GAT_COND_BLANK_ALL_ANTS = 1
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -49,6 +51,8 @@ EXPORTS = [
     # antenna-array processing: spatial covariance, beamformer weights, beamformed accumulators and loop
     "gat_spatial_covariance", "gat_array_weights", "gat_array_weights_host", "gat_beamform", "gat_tracking_update_weighted",
     "gat_tracking_update_host_weighted", "gat_tracking_run_weighted", "gat_beamform_samples",
+    # sample conditioning: level statistics, pulse blanking, AGC, requantisation
+    "gat_condition_samples", "gat_condition_samples_host", "gat_sample_stats", "gat_agc_update", "gat_agc_update_host",
 ]
 
 
@@ -131,6 +135,19 @@ ACQ_RESULT_DTYPE = np.dtype([("prn", "<i4"), ("detected", "<i4"), ("doppler_bin"
                              ("peak_to_second", "<f8"), ("cn0_dbhz", "<f8"), ("carrier_doppler_hz", "<f8"),
                              ("code_phase_chips", "<f8"), ("num_noise_bins", "<i8")])
 assert C.sizeof(AcqConfig) == 72 and ACQ_RESULT_DTYPE.itemsize == 80
+
+
+class AgcConfig(C.Structure):
+    """gat_agc_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("target_rms", C.c_double), ("blank_factor", C.c_double), ("remove_dc", C.c_int32)]
+
+
+# gat_cond_params and gat_sample_stats_t (include/gat.h)
+COND_PARAMS_DTYPE = np.dtype([("scale", "<f4"), ("dc_re", "<f4"), ("dc_im", "<f4"), ("threshold", "<f4")])
+SAMPLE_STATS_DTYPE = np.dtype([("kept", "<i8"), ("blanked", "<i8"), ("sum_re", "<f8"), ("sum_im", "<f8"), ("sum_pow", "<f8"),
+                               ("max_abs", "<f4"), ("pad_", "<f4")])
+assert C.sizeof(AgcConfig) == 32 and COND_PARAMS_DTYPE.itemsize == 16 and SAMPLE_STATS_DTYPE.itemsize == 48
 
 
 _LIB = None
@@ -226,6 +243,11 @@ def load(build_if_missing: bool = True):
         "gat_array_weights_host": (i32, [vp, vp, i32, vp, vp, i32, i32, dbl, vp, vp]),
         "gat_beamform": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
         "gat_beamform_samples": (i32, [vp, sp, i32, vp, vp, i32, sp]),
+        "gat_condition_samples": (i32, [vp, sp, i32, vp, u32, sp, vp]),
+        "gat_condition_samples_host": (i32, [sp, i32, vp, u32, sp, vp]),
+        "gat_sample_stats": (i32, [vp, sp, i32, i32, vp, u32, vp]),
+        "gat_agc_update": (i32, [vp, vp, i32, C.POINTER(AgcConfig), vp]),
+        "gat_agc_update_host": (i32, [vp, i32, C.POINTER(AgcConfig), vp]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

@@ -1,0 +1,224 @@
+"""Sample conditioning on device tensors (include/gat.h, "sample conditioning"): level statistics per antenna with pulses
+excluded, the AGC's records from them, and the conditioned stream -- blanked, scaled, requantised -- that ``acquire``,
+``spatial_covariance``, ``beamform_samples`` and the correlators take as a signal.
+
+The fastest kernels read int8 pairs; ``requantize`` is what makes them from a float front end::
+
+    sig8, desc, counts, params = requantize((re, im), N, num_blocks=B, blank_factor=4.0)
+    results = acquire(sig8, system, fs, N, prns, ...)
+
+Everything runs in libgat's HIP kernels; there is no CPU fallback (``condition_samples_host`` and ``agc_params_host`` are the
+library's host twins, the bit-exact reference of the device calls, for tests and for machines without a GPU)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import COND_PARAMS_DTYPE, GAT_COND_BLANK_ALL_ANTS, SAMPLE_STATS_DTYPE  # noqa: F401
+from .context import Context, get_context
+from .tracking import _signal_desc
+
+_OUT_LAYOUT = {torch.int8: _lib.GAT_LAYOUT_INTERLEAVED_I8, torch.int16: _lib.GAT_LAYOUT_INTERLEAVED_I16,
+               torch.float32: _lib.GAT_LAYOUT_INTERLEAVED}
+
+
+def _vp(t: torch.Tensor | None):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class SampleStats:
+    """``gat_sample_stats_t`` records ``[E, M]`` on the device: ``raw`` is the uint8 tensor ``[E, M, 48]`` the kernel wrote;
+    ``numpy()`` copies it to the host as a structured array (kept, blanked, sum_re, sum_im, sum_pow, max_abs); ``stats[e]`` is
+    one estimate (a view)."""
+
+    def __init__(self, raw: torch.Tensor):
+        self.raw = raw
+
+    @property
+    def shape(self):
+        return tuple(self.raw.shape[:2])
+
+    def __getitem__(self, e: int) -> "SampleStats":
+        E = self.raw.shape[0]
+        if not -E <= e < E:
+            raise IndexError(f"estimate {e} of {E}")
+        e %= E
+        return SampleStats(self.raw[e:e + 1])
+
+    def numpy(self) -> np.ndarray:
+        return self.raw.cpu().numpy().view(SAMPLE_STATS_DTYPE).reshape(self.shape)
+
+
+def _records(params, M: int, device) -> torch.Tensor:
+    """``gat_cond_params`` records as a float32 tensor ``[M, 4]`` (scale, dc_re, dc_im, threshold) on ``device``."""
+    if isinstance(params, np.ndarray):
+        params = torch.from_numpy(np.ascontiguousarray(params).view(np.float32).reshape(-1, 4).copy())
+    t = params.to(device=device, dtype=torch.float32).contiguous()
+    if tuple(t.shape) != (M, 4):
+        raise ValueError(f"params must be [M, 4] = (scale, dc_re, dc_im, threshold) for {M} antennas")
+    return t
+
+
+def _input_desc(signal, num_samples: int, num_blocks: int, start: int, block_stride: int | None):
+    re, im = signal if isinstance(signal, (tuple, list)) else (signal, None)
+    nb, N = int(num_blocks), int(num_samples)
+    if nb < 1 or N < 1:
+        raise ValueError("num_blocks and num_samples must be positive")
+    stride = N if block_stride is None else int(block_stride)
+    ntot = re.shape[-2] if im is None else re.shape[-1]
+    if stride < 0 or start + (nb - 1) * stride + N > ntot:
+        raise ValueError("signal shorter than start + (num_blocks - 1) * block_stride + num_samples")
+    return re, _signal_desc(re, im, N, start=int(start), block_stride=stride)
+
+
+def sample_stats(signal, num_samples: int, num_blocks: int = 1, blocks_per_estimate: int | None = None, params=None,
+                 blank_all: bool = False, ctx: Context | None = None, start: int = 0, block_stride: int | None = None,
+                 out: SampleStats | None = None) -> SampleStats:
+    """Level statistics per (estimate, antenna) over the samples the blanking rule keeps: counts, ``sum x``, ``sum |x|^2`` and
+    the largest component, ``E = ceil(num_blocks / blocks_per_estimate)`` estimates (default: one over all blocks).  ``signal``
+    as ``spatial_covariance`` takes it.  ``params``: records ``[M, 4]`` of which only the threshold is read, or None (keep every
+    sample).  The same bits on every call; FP64 sums.  ``out``: an earlier result to write into (no allocation)."""
+    re, desc = _input_desc(signal, num_samples, num_blocks, start, block_stride)
+    nb = int(num_blocks)
+    bpe = nb if blocks_per_estimate is None else int(blocks_per_estimate)
+    if bpe < 1:
+        raise ValueError("blocks_per_estimate must be positive")
+    ctx = ctx if ctx is not None else get_context(re.device)
+    E, M = (nb + bpe - 1) // bpe, int(desc.num_ants)
+    prm = _records(params, M, re.device) if params is not None else None
+    if out is None:
+        out = SampleStats(torch.empty((E, M, SAMPLE_STATS_DTYPE.itemsize), dtype=torch.uint8, device=re.device))
+    elif out.shape != (E, M):
+        raise ValueError("out has another shape")
+    flags = GAT_COND_BLANK_ALL_ANTS if blank_all else 0
+    ctx.check(ctx.lib.gat_sample_stats(ctx._h, C.byref(desc), nb, bpe, _vp(prm), flags, _vp(out.raw)), "gat_sample_stats")
+    out._keep = prm  # the kernel reads it after this call returns
+    return out
+
+
+def _agc_config(target_rms: float, blank_factor: float, remove_dc: bool) -> _lib.AgcConfig:
+    return _lib.AgcConfig(C.sizeof(_lib.AgcConfig), float(target_rms), float(blank_factor), int(bool(remove_dc)))
+
+
+def agc_params(stats: SampleStats, target_rms: float, blank_factor: float = 0.0, remove_dc: bool = False, ctx: Context | None = None,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """The next records ``[M, 4]`` (scale, dc_re, dc_im, threshold; float32, on the device) from ONE estimate's statistics,
+    without a host round trip: ``sigma = sqrt(sum_pow / (2 kept))``, ``scale = target_rms / sigma``, ``dc = sum / kept`` if
+    ``remove_dc``, ``threshold = blank_factor * sigma`` (``blank_factor <= 0``: no blanking).  An antenna without kept samples
+    or power gets scale 0 and no blanking."""
+    E, M = stats.shape
+    if E != 1:
+        raise ValueError("pick one estimate: stats[e]")
+    ctx = ctx if ctx is not None else get_context(stats.raw.device)
+    if out is None:
+        out = torch.empty((M, 4), dtype=torch.float32, device=stats.raw.device)
+    elif tuple(out.shape) != (M, 4) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 [M, 4]")
+    cfg = _agc_config(target_rms, blank_factor, remove_dc)
+    ctx.check(ctx.lib.gat_agc_update(ctx._h, _vp(stats.raw), M, C.byref(cfg), _vp(out)), "gat_agc_update")
+    return out
+
+
+def agc_params_host(stats: np.ndarray, target_rms: float, blank_factor: float = 0.0, remove_dc: bool = False) -> np.ndarray:
+    """``gat_agc_update_host``: the same arithmetic on a host structured array ``[M]`` of ``SAMPLE_STATS_DTYPE``."""
+    st = np.ascontiguousarray(stats, dtype=SAMPLE_STATS_DTYPE).reshape(-1)
+    out = np.zeros(st.size, dtype=COND_PARAMS_DTYPE)
+    cfg = _agc_config(target_rms, blank_factor, remove_dc)
+    rc = _lib.load().gat_agc_update_host(st.ctypes.data, st.size, C.byref(cfg), out.ctypes.data)
+    if rc != _lib.GAT_OK:
+        raise _lib.GatError(rc, "gat_agc_update_host")
+    return out
+
+
+def _alloc_out(M: int, N: int, nb: int, out_dtype, planar: bool, device):
+    """Zeroed output with every block start padded to 16 bytes; returns (tensor(s), descriptor)."""
+    if planar:
+        if out_dtype != torch.float32:
+            raise ValueError("a planar output is float32")
+        layout = _lib.GAT_LAYOUT_PLANAR
+    elif out_dtype in _OUT_LAYOUT:
+        layout = _OUT_LAYOUT[out_dtype]
+    else:
+        raise ValueError("out_dtype must be torch.int8, torch.int16 or torch.float32")
+    vs = 16 // (4 if planar else _lib.SAMPLE_BYTES[layout])
+    ostride = (N + vs - 1) // vs * vs
+    ld = nb * ostride
+    if planar:
+        out = (torch.zeros((M, ld), dtype=torch.float32, device=device), torch.zeros((M, ld), dtype=torch.float32, device=device))
+        return out, _lib.SignalDesc(out[0].data_ptr(), out[1].data_ptr(), layout, M, N, ld, ostride, 0)
+    out = torch.zeros((M, ld, 2), dtype=out_dtype, device=device)
+    return out, _lib.SignalDesc(out.data_ptr(), None, layout, M, N, ld, ostride, 0)
+
+
+def condition_samples(signal, params, num_samples: int, num_blocks: int = 1, out_dtype=torch.int8, blank_all: bool = False, out=None,
+                      ctx: Context | None = None, start: int = 0, block_stride: int | None = None, planar: bool = False,
+                      out_block_stride: int | None = None, counts: torch.Tensor | None = None):
+    """The conditioned stream: a sample of antenna m is blanked unless ``|re| <= T_m and |im| <= T_m`` (``blank_all``: on every
+    antenna if on any), a kept component becomes ``(x - dc) * scale`` in float32 and, for an integer ``out_dtype``, is rounded
+    to nearest-even and clamped to +-127 / +-32767.  Returns ``(tensor, desc, counts)``: the output as ``acquire`` and the
+    correlators take it -- ``[M, Ntot, 2]`` of ``out_dtype``, or with ``planar=True`` a float32 ``(re, im)`` pair ``[M, Ntot]`` --,
+    its descriptor (it points into the tensor: keep both) and int64 ``[M, 2]`` = (blanked samples, clipped components), added
+    to ``counts`` when one is passed.  Allocated here, block b starts ``b * stride`` samples in with ``stride`` = ``num_samples``
+    rounded up to 16 bytes (what lies between blocks is zero); a caller's ``out`` (with ``out_block_stride``, default
+    ``num_samples``) is described as it is -- the input itself for in-place work."""
+    re, desc = _input_desc(signal, num_samples, num_blocks, start, block_stride)
+    nb, N, M = int(num_blocks), int(num_samples), int(desc.num_ants)
+    ctx = ctx if ctx is not None else get_context(re.device)
+    prm = _records(params, M, re.device)
+    if out is None:
+        out, odesc = _alloc_out(M, N, nb, out_dtype, planar, re.device)
+    else:
+        o_re, o_im = out if isinstance(out, (tuple, list)) else (out, None)
+        odesc = _signal_desc(o_re, o_im, N, block_stride=N if out_block_stride is None else int(out_block_stride))
+    if counts is None:
+        counts = torch.zeros((M, 2), dtype=torch.int64, device=re.device)
+    flags = GAT_COND_BLANK_ALL_ANTS if blank_all else 0
+    ctx.check(ctx.lib.gat_condition_samples(ctx._h, C.byref(desc), nb, _vp(prm), flags, C.byref(odesc), _vp(counts)), "gat_condition_samples")
+    odesc._keep = prm  # the kernel reads the records after this call returns
+    return out, odesc, counts
+
+
+def _host_desc(arr, im, layout: int, M: int, N: int, ant_stride: int, block_stride: int, offset: int = 0) -> _lib.SignalDesc:
+    step = 4 if layout == _lib.GAT_LAYOUT_PLANAR else _lib.SAMPLE_BYTES.get(layout, 1)  # (an unknown layout is the callee's to refuse)
+    return _lib.SignalDesc(arr.ctypes.data + offset * step, None if im is None else im.ctypes.data + offset * step, layout, M, N,
+                           ant_stride, block_stride, 0)
+
+
+def condition_samples_host(desc: _lib.SignalDesc, num_blocks: int, params: np.ndarray, out_desc: _lib.SignalDesc, blank_all: bool = False,
+                           counts: np.ndarray | None = None) -> int:
+    """``gat_condition_samples_host`` on descriptors of HOST memory (``host_desc`` builds one over numpy arrays).  Returns the
+    status instead of raising: the refusals are part of what the twin is a reference of."""
+    prm = np.ascontiguousarray(params, dtype=COND_PARAMS_DTYPE) if params is not None else None
+    if counts is not None and (counts.dtype != np.uint64 or not counts.flags.c_contiguous):
+        raise ValueError("counts must be a contiguous uint64 [M, 2]")
+    flags = GAT_COND_BLANK_ALL_ANTS if blank_all is True else int(blank_all)
+    return int(_lib.load().gat_condition_samples_host(C.byref(desc) if desc is not None else None, int(num_blocks),
+                                                      prm.ctypes.data if prm is not None else None, flags,
+                                                      C.byref(out_desc) if out_desc is not None else None,
+                                                      counts.ctypes.data if counts is not None else None))
+
+
+host_desc = _host_desc
+
+
+def requantize(signal, num_samples: int, num_blocks: int = 1, out_dtype=torch.int8, target_rms: float = 16.0, blank_factor: float = 0.0,
+               iterations: int = 2, remove_dc: bool = False, blank_all: bool = False, ctx: Context | None = None, start: int = 0,
+               block_stride: int | None = None, planar: bool = False):
+    """Measure, set the gain, convert: ``iterations`` rounds of ``sample_stats`` (one estimate over all blocks, blanking with
+    the previous round's threshold) and ``agc_params``, then ``condition_samples``.  Two rounds are the robust iteration: a
+    pulse inflates the first sigma, the second measurement excludes it.  Returns ``(tensor, desc, counts, params)``.
+
+    The default ``target_rms = 16`` counts per component for int8: the clip at 127 is 127 / 16 = 7.9 sigma away (a Gaussian
+    component passes it with probability 2e-15), and the quantisation step is sigma / 16, which adds 1 / (12 * 256) = 0.03 % to
+    the noise power (0.0014 dB).  For int16 a larger target costs nothing."""
+    if int(iterations) < 1:
+        raise ValueError("iterations must be at least 1")
+    params = None
+    for _ in range(int(iterations)):
+        st = sample_stats(signal, num_samples, num_blocks, None, params, blank_all, ctx, start, block_stride)
+        params = agc_params(st, target_rms, blank_factor, remove_dc, ctx)
+    out, desc, counts = condition_samples(signal, params, num_samples, num_blocks, out_dtype, blank_all, None, ctx, start, block_stride, planar)
+    return out, desc, counts, params

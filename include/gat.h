@@ -698,6 +698,85 @@ GAT_API int32_t gat_tracking_run_weighted(gat_ctx *ctx, const gat_signal_desc *s
                                           float *acc_re_dev, float *acc_im_dev, int64_t acc_block_stride, uint32_t flags,
                                           int32_t *current_is_b, const double *w_re_dev, const double *w_im_dev);
 
+/* ---- sample conditioning: level statistics, pulse blanking, AGC, requantisation ----------------------------------------
+ * A stream-in, stream-out stage in front of everything else: measure the level of each antenna with pulses excluded
+ * (gat_sample_stats), turn the measurement into a scale, a DC estimate and a blanking threshold on the device
+ * (gat_agc_update), and write a conditioned stream, blanked and requantised (gat_condition_samples), that the search, the
+ * covariance, the beamformer and the correlators take as a signal.  The fastest kernels read int8 pairs; this is what
+ * produces them from a float front end.  The rule below is written so that the device, the host twin and a float32
+ * restatement give the same bits.
+ *   Blanking: a sample of antenna m is KEPT iff fabsf(re) <= T_m && fabsf(im) <= T_m on the raw sample (integer samples
+ *     convert exactly).  A NaN component blanks its sample at any threshold, +inf included; a component equal to T is kept.
+ *     With GAT_COND_BLANK_ALL_ANTS sample n is blanked on every antenna if it is blanked on any.
+ *   A kept component: t = x - dc, then y = t * scale: one float32 subtraction, one float32 multiplication, never fused.
+ *   Float outputs (planar, ComplexF32): y as is; a blanked sample is +0.0, +0.0.
+ *   Integer outputs (int16 / int8 pairs): y rounded to nearest, ties to even, then clamped to +-32767 / +-127 (the most
+ *     negative code is never written); a component whose rounded value was outside that range counts as clipped; a NaN y
+ *     (NaN parameters only) writes 0 and counts as clipped; a blanked sample is 0, 0. */
+typedef struct gat_cond_params { /* one per antenna, device- or host-resident */
+    float scale;                 /* y = (x - dc) * scale */
+    float dc_re, dc_im;
+    float threshold;             /* on the RAW sample: blanked unless |re| <= T and |im| <= T; +inf: no blanking */
+} gat_cond_params;
+#define GAT_COND_BLANK_ALL_ANTS 1u /* a sample blanked on one antenna is blanked on all of them */
+
+/* The conditioned stream.  signal: any layout, 1 <= M <= GAT_MAX_ARRAY_ANTS, any N, base alignment and strides,
+ * chan_stride 0.  out: describes device memory the call WRITES, as in gat_beamform_samples: the same num_ants and
+ * num_samples, its own layout (any of the four, the input's included) and strides; nothing outside the described elements
+ * is written.  params_dev: M records.  counts_dev: uint64 [M][2] = {blanked samples, clipped components} of this call,
+ * ADDED to what is there (the caller zeroes it; integer atomics, so the order does not matter), or NULL.
+ * M <= 8 with every block of every antenna starting on a 16-byte boundary on both sides streams with 16-byte non-temporal
+ * loads and 16-byte stores (a lane owns 4, or with an int8 side 8, consecutive samples of all antennas); everything else
+ * runs one sample per lane with scalar loads and stores.  The bits are the same.  gat_last_launch_info afterwards: vec = 4
+ * (streaming) or 1, workgroups, threads, splits (chunks of a block), ant_tile = M.  Enqueues on the context's stream and
+ * does not synchronise; it allocates nothing.  Refusals, all before any launch: GAT_ERR_ARG for null pointers, num_blocks <
+ * 1, sizes < 1, negative (or, where more than one antenna / block is described, zero) strides, unknown flags, out->num_ants
+ * or out->num_samples different from the signal's, a planar side without im or an interleaved one with im, and an output
+ * whose byte extent overlaps the input's unless the two descriptors are identical element for element (in place: the same
+ * layout, planes and strides); GAT_ERR_RANGE for M above 64 or an extent beyond 9e15 samples; GAT_ERR_UNSUPPORTED for
+ * chan_stride != 0 on either side. */
+GAT_API int32_t gat_condition_samples(gat_ctx *ctx, const gat_signal_desc *signal, int32_t num_blocks,
+                                      const gat_cond_params *params_dev, uint32_t flags, const gat_signal_desc *out,
+                                      uint64_t *counts_dev);
+/* The same rule in a plain loop on the HOST (csrc/gat_cond.h, shared with the device): every pointer is host memory; needs
+ * no context and no device.  The bit-exact reference of the device call, with the same refusals. */
+GAT_API int32_t gat_condition_samples_host(const gat_signal_desc *signal, int32_t num_blocks, const gat_cond_params *params_host,
+                                           uint32_t flags, const gat_signal_desc *out, uint64_t *counts_host);
+
+/* Level statistics, one record per (estimate, antenna): E = ceil(num_blocks / blocks_per_estimate) as in
+ * gat_spatial_covariance, stats_dev [E][M].  The blanking rule is the one above; only `threshold` of the records is read,
+ * params_dev == NULL keeps every sample without a NaN component.  The samples cross HBM once (M <= 8; more antennas run in
+ * tiles of 8, and with GAT_COND_BLANK_ALL_ANTS a tile reads the other tiles' samples again for the verdict).  Every lane
+ * sums in FP64; workgroups write their sums to slices of the context's scratch and a second kernel adds them in a fixed
+ * order: no float atomics, the same bits on every call.  Counts and max_abs are exact; |sum - exact| <= 1e-5 * sum |x| per
+ * component and sum_pow to a relative 1e-5 hold with a wide margin (integer samples: exact below 2^53). */
+typedef struct gat_sample_stats_t {
+    int64_t kept, blanked;
+    double sum_re, sum_im, sum_pow; /* over kept samples: sum x, sum |x|^2 */
+    float max_abs;                  /* largest |component| among kept samples; 0 if none */
+    float pad_;
+} gat_sample_stats_t;
+GAT_API int32_t gat_sample_stats(gat_ctx *ctx, const gat_signal_desc *signal, int32_t num_blocks, int32_t blocks_per_estimate,
+                                 const gat_cond_params *params_dev, uint32_t flags, gat_sample_stats_t *stats_dev);
+
+/* One estimate's statistics [num_ants] into the next records [num_ants], on the device: sigma = sqrt(sum_pow / (2 kept))
+ * (the RMS per component), scale = target_rms / sigma, dc = sum / kept if remove_dc else 0, threshold = blank_factor *
+ * sigma (blank_factor <= 0: +inf).  FP64 throughout, narrowed once.  kept == 0 or sigma == 0 (or not finite): scale = 0,
+ * dc = 0, threshold = +inf.  gat_sample_stats, gat_agc_update, gat_sample_stats again is the robust iteration: a pulse
+ * inflates the first sigma, the second pass excludes it.  After a first call has sized the scratch, the three calls and
+ * gat_condition_samples neither allocate nor read on the host: they can be captured in a stream graph. */
+typedef struct gat_agc_config {
+    uint32_t struct_size; /* sizeof(gat_agc_config) */
+    double target_rms;    /* finite, >= 0 */
+    double blank_factor;
+    int32_t remove_dc;
+} gat_agc_config;
+GAT_API int32_t gat_agc_update(gat_ctx *ctx, const gat_sample_stats_t *stats_dev, int32_t num_ants, const gat_agc_config *cfg,
+                               gat_cond_params *params_dev);
+/* The same arithmetic on the HOST (csrc/gat_cond.h, shared with the device), to the last bit. */
+GAT_API int32_t gat_agc_update_host(const gat_sample_stats_t *stats_host, int32_t num_ants, const gat_agc_config *cfg,
+                                    gat_cond_params *params_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -765,6 +765,71 @@ function beamform_samples(ctx::Context, desc::SignalDesc, num_blocks::Integer, w
     out = SignalDesc(out_re, out_im, Int32(0), Int32(num_beams), desc.num_samples, Int64(out_ant_stride), Int64(out_block_stride), Int64(0))
     beamform_samples!(ctx, desc, num_blocks, w_re, w_im, num_beams, out)
 end
+# ---- sample conditioning: level statistics, pulse blanking, AGC, requantisation (include/gat.h) --------------------------------
+const GAT_COND_BLANK_ALL_ANTS = UInt32(1)
+struct CondParams    # gat_cond_params: y = (x - dc) * scale; blanked unless |re| <= threshold and |im| <= threshold
+    scale::Float32
+    dc_re::Float32
+    dc_im::Float32
+    threshold::Float32
+end
+struct SampleStats   # gat_sample_stats_t, one per (estimate, antenna)
+    kept::Int64
+    blanked::Int64
+    sum_re::Float64
+    sum_im::Float64
+    sum_pow::Float64
+    max_abs::Float32
+    pad_::Float32
+end
+struct AgcConfig     # gat_agc_config
+    struct_size::UInt32
+    target_rms::Float64
+    blank_factor::Float64
+    remove_dc::Int32
+end
+AgcConfig(target_rms::Real, blank_factor::Real = 0.0, remove_dc::Bool = false) =
+    AgcConfig(UInt32(sizeof(AgcConfig)), Float64(target_rms), Float64(blank_factor), Int32(remove_dc))
+# the conditioned stream: `out` describes the device memory the call writes (any layout, the signal's num_ants and num_samples) and
+# is afterwards a signal for acquire!, spatial_covariance! and the correlators; params_dev: M CondParams; counts_dev: UInt64
+# [2 x M] = (blanked samples, clipped components), added to, or C_NULL
+function condition_samples!(ctx::Context, desc::SignalDesc, num_blocks::Integer, params_dev::Ptr{Cvoid}, out::SignalDesc;
+                            blank_all::Bool = false, counts_dev::Ptr{Cvoid} = C_NULL)
+    check(ctx, ccall((:gat_condition_samples, libgat), Int32,
+                     (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Ptr{Cvoid}, UInt32, Ref{SignalDesc}, Ptr{Cvoid}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), params_dev, blank_all ? GAT_COND_BLANK_ALL_ANTS : UInt32(0), Ref(out), counts_dev))
+    out
+end
+# the same rule on host memory (both descriptors point into host arrays): the bit-exact reference of the device call
+function condition_samples_host!(desc::SignalDesc, num_blocks::Integer, params::Vector{CondParams}, out::SignalDesc;
+                                 blank_all::Bool = false, counts::Union{Nothing,Matrix{UInt64}} = nothing)
+    rc = ccall((:gat_condition_samples_host, libgat), Int32,
+               (Ref{SignalDesc}, Int32, Ptr{CondParams}, UInt32, Ref{SignalDesc}, Ptr{UInt64}),
+               Ref(desc), Int32(num_blocks), params, blank_all ? GAT_COND_BLANK_ALL_ANTS : UInt32(0), Ref(out),
+               counts === nothing ? Ptr{UInt64}(C_NULL) : pointer(counts))
+    rc == GAT_OK || error("gat_condition_samples_host: status $rc")
+    out
+end
+# level statistics [M x E] SampleStats on the device, E = cld(num_blocks, blocks_per_estimate); params_dev: C_NULL keeps every sample
+function sample_stats!(ctx::Context, desc::SignalDesc, num_blocks::Integer, blocks_per_estimate::Integer, stats_dev::Ptr{Cvoid};
+                       params_dev::Ptr{Cvoid} = C_NULL, blank_all::Bool = false)
+    check(ctx, ccall((:gat_sample_stats, libgat), Int32,
+                     (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Int32, Ptr{Cvoid}, UInt32, Ptr{Cvoid}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), Int32(blocks_per_estimate), params_dev,
+                     blank_all ? GAT_COND_BLANK_ALL_ANTS : UInt32(0), stats_dev))
+end
+# one estimate's statistics into the next records, on the device
+function agc_update!(ctx::Context, stats_dev::Ptr{Cvoid}, num_ants::Integer, cfg::AgcConfig, params_dev::Ptr{Cvoid})
+    check(ctx, ccall((:gat_agc_update, libgat), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ref{AgcConfig}, Ptr{Cvoid}),
+                     ctx.handle, stats_dev, Int32(num_ants), Ref(cfg), params_dev))
+end
+function agc_update_host(stats::Vector{SampleStats}, cfg::AgcConfig)
+    params = Vector{CondParams}(undef, length(stats))
+    rc = ccall((:gat_agc_update_host, libgat), Int32, (Ptr{SampleStats}, Int32, Ref{AgcConfig}, Ptr{CondParams}),
+               stats, Int32(length(stats)), Ref(cfg), params)
+    rc == GAT_OK || error("gat_agc_update_host: status $rc")
+    params
+end
 # tracking_update! / tracking_update_host! / tracking_run! with weights [M x K] (C_NULL planes: the unweighted calls)
 function tracking_update_weighted!(ctx::Context, acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, K::Integer, M::Integer, cfg::LoopConfig,
                                    state_dev::Ptr{Cvoid}, cur_dev::Ptr{Cvoid}, next_dev::Ptr{Cvoid}, w_re::Ptr{Float64}, w_im::Ptr{Float64})
