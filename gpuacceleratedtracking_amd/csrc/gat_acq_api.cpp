@@ -101,14 +101,9 @@ GAT_API int32_t gat_acquire(gat_ctx *c, const gat_signal_desc *sig, int32_t B, c
     if (B < 1) return fail(c, GAT_ERR_ARG, "num_blocks must be positive");
     for (int p = 0; p < P; ++p)
         if (prns[p] < 0 || prns[p] >= c->P) return fail(c, GAT_ERR_RANGE, "prn outside the code table");
+    const Refusal r = check_desc(sig, B, 0, signal_refusals({GAT_ERR_ARG, "chan_stride must be 0 (one signal for every PRN)"}));
+    if (r.code != GAT_OK) return fail(c, r.code, r.msg);
     const int layout = sig->layout;
-    if (layout < GAT_LAYOUT_PLANAR || layout > GAT_LAYOUT_INTERLEAVED_I8) return fail(c, GAT_ERR_ARG, "bad layout");
-    if (!sig->re || (layout == GAT_LAYOUT_PLANAR) != (sig->im != nullptr)) return fail(c, GAT_ERR_ARG, "bad signal planes");
-    if (sig->num_ants < 1 || sig->num_samples < 1 || sig->ant_stride < 0 || sig->block_stride < 0)
-        return fail(c, GAT_ERR_ARG, "bad signal sizes");
-    if (sig->num_ants > 1 && sig->ant_stride < 1) return fail(c, GAT_ERR_ARG, "ant_stride must be positive");
-    if (B > 1 && sig->block_stride < 1) return fail(c, GAT_ERR_ARG, "block_stride must be positive");
-    if (sig->chan_stride != 0) return fail(c, GAT_ERR_ARG, "chan_stride must be 0 (one signal for every PRN)");
     const int D = cfg.num_doppler_bins, J = cfg.num_code_bins, s = cfg.code_step_samples;
     const long long N = sig->num_samples;
     const int jtiles = (J + kAcqCodeTile - 1) / kAcqCodeTile, dtiles = (D + kAcqDopTile - 1) / kAcqDopTile;
@@ -117,8 +112,6 @@ GAT_API int32_t gat_acquire(gat_ctx *c, const gat_signal_desc *sig, int32_t B, c
     if (!(reach < 1073741824.0)) return fail(c, GAT_ERR_RANGE, "N + |first_shift| + s * J must stay below 2^30 samples");
     const double ratio = cfg.code_freq_hz / fs;
     if (!code_span_ok(ratio, (double)cfg.code_length, reach, c->Lc)) return fail(c, GAT_ERR_RANGE, "code phase span too large");
-    if ((double)(B - 1) * (double)sig->block_stride + (double)(sig->num_ants - 1) * (double)sig->ant_stride + (double)N > 9.0e15)
-        return fail(c, GAT_ERR_RANGE, "signal extent too large");
 
     // groups of (antenna, block) units: enough workgroups for two per compute unit, within the scratch bound
     const long long cells = (long long)P * D * J;

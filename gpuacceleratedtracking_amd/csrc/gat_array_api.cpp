@@ -26,15 +26,8 @@ int32_t covariance_launches(gat_ctx *c, const gat_signal_desc *sig, const void *
     const long long round_to = vec ? vs * kCovSmallThreads : geo.chunk;
     const long long min_seg = vec ? 4 * round_to : 8ll * geo.chunk;
     const long long want = (long long)c->num_cus * (vec ? 8 : 4); // workgroups of the launch
-    const long long per_est = std::max<long long>(1, want / E);
-    const int blocks = std::min(bpe, B);
-    long long splits = 1;
-    if (blocks < per_est) splits = std::min<long long>((per_est + blocks - 1) / blocks, std::max<long long>(1, N / min_seg));
-    long long seg_len = ((N + splits - 1) / splits + round_to - 1) / round_to * round_to;
-    splits = (N + seg_len - 1) / seg_len;
-    const long long G = std::min<long long>((long long)blocks * splits, per_est);
-
-    const size_t bytes = (size_t)E * (size_t)G * 2 * M * M * sizeof(float);
+    const EstimateSplit sp = split_estimate(std::min(bpe, B), N, round_to, min_seg, std::max<long long>(1, want / E));
+    const size_t bytes = (size_t)E * (size_t)sp.G * 2 * M * M * sizeof(float);
     const int32_t rc = ensure_partial(c, bytes);
     if (rc != GAT_OK) return rc;
     CovArgs a{};
@@ -44,15 +37,15 @@ int32_t covariance_launches(gat_ctx *c, const gat_signal_desc *sig, const void *
     a.B = B;
     a.bpe = bpe;
     a.E = E;
-    a.G = (int)G;
-    a.splits = (int)splits;
+    a.G = (int)sp.G;
+    a.splits = (int)sp.splits;
     a.N = N;
     a.ant_stride = sig->ant_stride;
     a.block_stride = sig->block_stride;
-    a.seg_len = seg_len;
+    a.seg_len = sp.seg_len;
     a.partial = c->d_partial;
     GAT_HIP(c, vec ? launch_cov_small(a, layout, c->stream) : launch_cov_tiled(a, layout, c->stream));
-    GAT_HIP(c, launch_cov_finish(c->d_partial, M, E, (int)G, cov_re, cov_im, c->stream));
+    GAT_HIP(c, launch_cov_finish(c->d_partial, M, E, (int)sp.G, cov_re, cov_im, c->stream));
     return GAT_OK;
 }
 
@@ -63,33 +56,19 @@ GAT_API int32_t gat_spatial_covariance(gat_ctx *c, const gat_signal_desc *sig, i
     if (!c) return GAT_ERR_ARG;
     if (!sig || !cov_re || !cov_im) return fail(c, GAT_ERR_ARG, "null argument");
     if (B < 1 || bpe < 1) return fail(c, GAT_ERR_ARG, "num_blocks and blocks_per_estimate must be positive");
-    const int layout = sig->layout;
-    if (layout < GAT_LAYOUT_PLANAR || layout > GAT_LAYOUT_INTERLEAVED_I8) return fail(c, GAT_ERR_ARG, "bad layout");
-    if (!sig->re || (layout == GAT_LAYOUT_PLANAR) != (sig->im != nullptr)) return fail(c, GAT_ERR_ARG, "bad signal planes");
-    if (sig->num_ants < 1 || sig->num_samples < 1 || sig->ant_stride < 0 || sig->block_stride < 0) return fail(c, GAT_ERR_ARG, "bad signal sizes");
+    // (the antenna limit ahead of the shared check's strides, as this entry point always answered)
     if (sig->num_ants > GAT_MAX_ARRAY_ANTS) return fail(c, GAT_ERR_RANGE, "more than 64 antennas");
-    if (sig->num_ants > 1 && sig->ant_stride < 1) return fail(c, GAT_ERR_ARG, "ant_stride must be positive");
-    if (B > 1 && sig->block_stride < 1) return fail(c, GAT_ERR_ARG, "block_stride must be positive");
-    if (sig->chan_stride != 0) return fail(c, GAT_ERR_UNSUPPORTED, "chan_stride must be 0 (one signal, one covariance)");
-    if ((double)(B - 1) * (double)sig->block_stride + (double)(sig->num_ants - 1) * (double)sig->ant_stride + (double)sig->num_samples > 9.0e15)
-        return fail(c, GAT_ERR_RANGE, "signal extent too large");
+    const Refusal r = check_desc(sig, B, GAT_MAX_ARRAY_ANTS, signal_refusals({GAT_ERR_UNSUPPORTED, "chan_stride must be 0 (one signal, one covariance)"}));
+    if (r.code != GAT_OK) return fail(c, r.code, r.msg);
     const int M = sig->num_ants;
-    // the streaming kernel's rule is the correlator's fast-path rule: every block of every antenna starts on a 16-byte boundary
-    const long long vs = layout_vec_samples(layout);
-    const bool vec = M <= kCovSmallMaxAnts && aligned16(sig->re) && (layout != GAT_LAYOUT_PLANAR || aligned16(sig->im)) &&
-                     (M == 1 || sig->ant_stride % vs == 0) && (B == 1 || sig->block_stride % vs == 0);
+    const bool vec = M <= kCovSmallMaxAnts && blocks_aligned(sig, B); // the streaming kernel's rule is the correlator's fast-path rule
     GAT_ENTER(c, "gat_spatial_covariance");
     // estimates per launch: one workgroup each at least, within the scratch bound
-    const int E = (B + bpe - 1) / bpe;
-    const size_t slice = (size_t)2 * M * M * sizeof(float);
-    const int e_max = (int)std::max<size_t>(1, std::min<size_t>((size_t)1 << 20, kMaxCovScratch / slice));
-    for (int e0 = 0; e0 < E; e0 += e_max) {
-        const int en = std::min(e_max, E - e0);
-        const int b0 = e0 * bpe, bn = std::min(B - b0, en * bpe);
-        const size_t off = (size_t)b0 * (size_t)sig->block_stride * (size_t)layout_sample_bytes(layout);
+    for (EstimateBatches t(B, bpe, (size_t)2 * M * M * sizeof(float), kMaxCovScratch); t.next();) {
+        const size_t off = block_offset_bytes(sig, t.b0);
         const void *re = static_cast<const char *>(sig->re) + off;
         const void *im = sig->im ? static_cast<const char *>(sig->im) + off : nullptr;
-        const int32_t rc = covariance_launches(c, sig, re, im, bn, bpe, en, vec, cov_re + (size_t)e0 * M * M, cov_im + (size_t)e0 * M * M);
+        const int32_t rc = covariance_launches(c, sig, re, im, t.bn, bpe, t.en, vec, cov_re + (size_t)t.e0 * M * M, cov_im + (size_t)t.e0 * M * M);
         if (rc != GAT_OK) return rc;
     }
     return GAT_OK;

@@ -1,5 +1,5 @@
 // gat_beam_kernels.h -- what the sample beamformer's kernels (gat_beam.hip) and their host side (gat_beam_api.cpp) share: the
-// kernels' geometry, their arguments and the launchers.
+// kernels' geometry, their arguments and the launchers.  The streaming rule and the work split are gat_beam_plan.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,19 +7,14 @@
 #include <stdint.h>
 
 #include "gat.h"
+#include "gat_beam_plan.h"
 
 namespace gat {
 
-constexpr int kBeamStreamMaxAnts = 8; // the streaming kernel holds one 16-byte load per antenna (and plane) up to here
 constexpr int kBeamStreamTile = 4;    // beams whose sums the streaming kernel keeps in registers: one pass over the samples
 constexpr int kBeamGeneralTile = 8;   // the same for the general kernel (one sample per lane)
-constexpr int kBeamThreads = 256;
 // the general kernel's instances: the smallest tile of 1, 2, 4, 8 beams that holds J (or 8)
 constexpr int beam_general_tile(int J) { return J == 1 ? 1 : J == 2 ? 2 : J <= 4 ? 4 : kBeamGeneralTile; }
-
-// samples a lane of the streaming kernel takes per step: whole 16-byte loads (4 / 2 / 4 / 8 samples by layout) AND whole 16-byte
-// stores of either output layout (4 samples a plane, 2 interleaved) -- two loads per antenna for ComplexF32 pairs
-constexpr int beam_group_samples(int fmt) { return fmt == GAT_LAYOUT_INTERLEAVED_I8 ? 8 : 4; }
 
 // One call.  Work units are (block, chunk of `chunk` samples), `chunks` to a block, B * chunks < 2^31; workgroup g of the grid takes units g,
 // g + gridDim.x, ...  Output element (n, j, b) is float n + j * out_ant_stride + b * out_block_stride of out_re / out_im

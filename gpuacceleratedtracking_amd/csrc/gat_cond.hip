@@ -54,13 +54,13 @@ __device__ __forceinline__ void cond_load_scalar(const void *re, const void *im,
 // one 16-byte load per plane: VS samples
 template <int FMT>
 struct CondVec {
-    static constexpr int VS = cond_vec_samples(FMT);
+    static constexpr int VS = layout_vec_samples(FMT);
     u4 a, b; // b: the imaginary plane's 16 bytes (planar only)
 
     // vector v (VS samples) of the antenna stream that starts `base` samples into the planes
     __device__ __forceinline__ void load(const void *re, const void *im, size_t base, long long v)
     {
-        constexpr size_t sample_bytes = cond_sample_bytes(FMT);
+        constexpr size_t sample_bytes = layout_sample_bytes(FMT);
         a = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(static_cast<const char *>(re) + base * sample_bytes) + v);
         if constexpr (FMT == GAT_LAYOUT_PLANAR) b = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(static_cast<const char *>(im) + base * sample_bytes) + v);
     }
@@ -195,7 +195,7 @@ __global__ void __launch_bounds__(kCondThreads) cond_stream_kernel(const CondArg
 {
     using Vec = CondVec<FI>;
     constexpr int VS = Vec::VS, G = cond_group_samples(FI, FO), NV = G / VS;
-    static_assert(G % VS == 0 && G % cond_vec_samples(FO) == 0, "whole loads and whole stores");
+    static_assert(G % VS == 0 && G % layout_vec_samples(FO) == 0, "whole loads and whole stores");
     const int tid = threadIdx.x;
     // The antenna strides live in vector registers: as scalars, the 2 M (planar: 4 M) block-and-antenna base addresses of the two
     // sides are hoisted out of the sample loop into register pairs, and with the records' 4 M values the scalar file overflows.

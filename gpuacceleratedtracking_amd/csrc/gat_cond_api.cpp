@@ -1,5 +1,5 @@
 // gat_cond_api.cpp -- host side of the sample conditioner (include/gat.h gat_condition_samples, gat_sample_stats,
-// gat_agc_update): the launches behind the pure plan of gat_cond_plan.h, the statistics' work split, and the host twins
+// gat_agc_update): the launches behind the pure plan of gat_cond_plan.h and the shared splits of gat_sig_plan.h, and the host twins
 // (gat_condition_samples_host, gat_agc_update_host), which run the arithmetic of gat_cond.h in plain loops.
 #include <algorithm>
 #include <cmath>
@@ -61,7 +61,7 @@ GAT_API int32_t gat_condition_samples(gat_ctx *c, const gat_signal_desc *sig, in
 {
     if (!c) return GAT_ERR_ARG;
     CondPlan plan{};
-    const CondRefusal r = cond_plan(sig, B, params, flags, out, (long long)c->num_cus * 8, &plan);
+    const Refusal r = cond_plan(sig, B, params, flags, out, (long long)c->num_cus * 8, &plan);
     if (r.code != GAT_OK) return fail(c, r.code, r.msg);
     GAT_ENTER(c, "gat_condition_samples");
     CondArgs a{};
@@ -97,7 +97,7 @@ GAT_API int32_t gat_condition_samples_host(const gat_signal_desc *sig, int32_t B
                                            const gat_signal_desc *out, uint64_t *counts)
 {
     CondPlan plan{};
-    const CondRefusal r = cond_plan(sig, B, params, flags, out, 1, &plan);
+    const Refusal r = cond_plan(sig, B, params, flags, out, 1, &plan);
     if (r.code != GAT_OK) return r.code;
     const int M = sig->num_ants;
     const bool blank_all = (flags & GAT_COND_BLANK_ALL_ANTS) != 0;
@@ -126,51 +126,42 @@ GAT_API int32_t gat_sample_stats(gat_ctx *c, const gat_signal_desc *sig, int32_t
     if (!stats) return fail(c, GAT_ERR_ARG, "null argument");
     if (bpe < 1) return fail(c, GAT_ERR_ARG, "blocks_per_estimate must be positive");
     if (flags & ~(uint32_t)GAT_COND_BLANK_ALL_ANTS) return fail(c, GAT_ERR_ARG, "unknown flags");
-    const CondRefusal r = cond_check_signal(sig, B);
+    const Refusal r = cond_check_signal(sig, B);
     if (r.code != GAT_OK) return fail(c, r.code, r.msg);
     const int M = sig->num_ants, layout = sig->layout;
     const long long N = sig->num_samples;
-    const bool vec = M <= kStatsTile && cond_detail::blocks_aligned(sig, B);
+    const bool vec = M <= kStatsTile && blocks_aligned(sig, B);
     GAT_ENTER(c, "gat_sample_stats");
-    const int E = (B + bpe - 1) / bpe;
-    const int e_max = (int)std::max<size_t>(1, std::min<size_t>((size_t)1 << 20, kMaxStatsScratch / (M * sizeof(gat_sample_stats_t))));
     // the work split of one batch of estimates, as the covariance's: (block, segment) units, G workgroups an estimate
-    const long long round_to = (long long)kStatsThreads * (vec ? cond_vec_samples(layout) : 1);
+    const long long round_to = (long long)kStatsThreads * (vec ? layout_vec_samples(layout) : 1);
     const long long want = (long long)c->num_cus * 8;
     long long grid_all = 0, splits_all = 1;
-    for (int e0 = 0; e0 < E; e0 += e_max) {
-        const int en = std::min(e_max, E - e0);
-        const int b0 = e0 * bpe, bn = std::min(B - b0, en * bpe);
-        const long long per_est = std::max<long long>(1, want / en);
-        const int blocks = std::min(bpe, bn);
-        long long splits = 1;
-        if (blocks < per_est) splits = std::min<long long>((per_est + blocks - 1) / blocks, std::max<long long>(1, N / (4 * round_to)));
-        const long long seg_len = ((N + splits - 1) / splits + round_to - 1) / round_to * round_to;
-        splits = (N + seg_len - 1) / seg_len;
-        const long long G = std::min<long long>((long long)blocks * splits, per_est);
-        const int32_t rc = ensure_partial(c, (size_t)en * (size_t)G * M * sizeof(gat_sample_stats_t));
+    for (EstimateBatches t(B, bpe, M * sizeof(gat_sample_stats_t), kMaxStatsScratch); t.next();) {
+        const EstimateSplit sp = split_estimate(std::min(bpe, t.bn), N, round_to, 4 * round_to, std::max<long long>(1, want / t.en));
+        const long long G = sp.G, splits = sp.splits;
+        const int32_t rc = ensure_partial(c, (size_t)t.en * (size_t)G * M * sizeof(gat_sample_stats_t));
         if (rc != GAT_OK) return rc;
-        const size_t off = (size_t)b0 * (size_t)sig->block_stride * (size_t)cond_sample_bytes(layout);
+        const size_t off = block_offset_bytes(sig, t.b0);
         StatsArgs a{};
         a.re = static_cast<const char *>(sig->re) + off;
         a.im = sig->im ? static_cast<const char *>(sig->im) + off : nullptr;
         a.M = M;
-        a.B = bn;
+        a.B = t.bn;
         a.bpe = bpe;
-        a.E = en;
+        a.E = t.en;
         a.G = (int)G;
         a.splits = (int)splits;
         a.blank_all = (flags & GAT_COND_BLANK_ALL_ANTS) ? 1 : 0;
         a.N = N;
         a.ant_stride = sig->ant_stride;
         a.block_stride = sig->block_stride;
-        a.seg_len = seg_len;
+        a.seg_len = sp.seg_len;
         a.prm = params;
         a.partial = reinterpret_cast<gat_sample_stats_t *>(c->d_partial);
         GAT_HIP(c, launch_stats(a, layout, vec, c->stream));
-        GAT_HIP(c, launch_stats_finish(a.partial, M, en, (int)G, stats + (size_t)e0 * M, c->stream));
+        GAT_HIP(c, launch_stats_finish(a.partial, M, t.en, (int)G, stats + (size_t)t.e0 * M, c->stream));
         // gat_last_launch_info describes the whole call: the workgroups of every batch, the largest split
-        grid_all += (long long)en * G * (M <= kStatsTile ? 1 : (M + kStatsTile - 1) / kStatsTile);
+        grid_all += (long long)t.en * G * (M <= kStatsTile ? 1 : (M + kStatsTile - 1) / kStatsTile);
         splits_all = std::max(splits_all, splits);
     }
     c->last = gat_launch_info{};

@@ -1,7 +1,8 @@
 // gat_ctx.h -- what the translation units of the C-ABI layer share: the context, error helpers, the entry preamble, scratch and
 // graph housekeeping, the planner's entry points.  The layer: gat_api.cpp (contexts, operators, options, the closed loop),
 // gat_planner.cpp (the correlator call's launch planning), gat_group.cpp (device groups), gat_resident_api.cpp (the resident
-// correlator's host side), gat_acq_api.cpp (acquisition), gat_array_api.cpp (antenna arrays).
+// correlator's host side), gat_acq_api.cpp (acquisition), gat_array_api.cpp (antenna arrays), gat_beam_api.cpp (beams of the raw
+// samples), gat_cond_api.cpp (sample conditioning).  What the operators over raw samples share is gat_sig_plan.h (through gat_internal.h).
 #pragma once
 
 #include <cmath>
@@ -123,8 +124,6 @@ inline int32_t hipfail(gat_ctx *c, hipError_t e, const char *where)
         if (e_ != hipSuccess) return hipfail((c), e_, #call); \
     } while (0)
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // host mirror of the kernels' code_span_bad (gat_phase.h): what passes here is not poisoned there
 inline bool code_span_ok(double ratio, double tau, double reach, int Lc)
 {
@@ -171,12 +170,6 @@ int32_t tracking_run_shared(gat_ctx *c, const gat_signal_desc *sig, int32_t num_
                             double fs, const gat_loop_config *cfg, gat_loop_state *state, gat_channel_params *params_a,
                             gat_channel_params *params_b, float *acc_re, float *acc_im, int64_t acc_block_stride, uint32_t flags,
                             int32_t *current_is_b, const double *w_re, const double *w_im, const LoopUpdateFn &update);
-
-// What planning returns: GAT_OK, or a refusal's code and message (the caller reports it with fail()).
-struct Refusal {
-    int32_t code;
-    const char *msg;
-};
 
 // params_dev: [B*K] records on the device -- or null with params_inline: B*K <= kInlineParams validated HOST records that
 // travel inside the vector kernel's arguments (uploaded after all if a matrix-core kernel takes the call)

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "gat.h"
+#include "gat_sig_plan.h" // the layout arithmetic (layout_sample_bytes, layout_vec_samples): HIP-free, shared with the pure plans
 
 // The reduced instance set (-DGAT_DC_DEV) and the environment knobs of gat_create exist in development builds only
 // (-DGAT_DEV); gat_version() names every flag of a build.
@@ -22,14 +23,6 @@ constexpr int kFinalizeFewSplits = 32; // second stage: up to this many splits a
 constexpr int kMaxReplicaSpan = 512;  // tap span the LDS replica segment of a launch is sized for by default
 constexpr int kMaxLaunchSpan = 2048;  // largest tap span one launch serves (the replica's LDS grows with the span beyond
                                       // kMaxReplicaSpan; wider tap lists are cut into several launches)
-
-// Layout arithmetic, stated here once.  Bytes of one sample in one plane: planar f32 4, interleaved ComplexF32 8,
-// interleaved int16 4, interleaved int8 2 -- and the samples one 16-byte load holds: 4, 2, 4, 8.
-constexpr int layout_sample_bytes(int fmt)
-{
-    return fmt == GAT_LAYOUT_PLANAR ? 4 : fmt == GAT_LAYOUT_INTERLEAVED ? 8 : fmt == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 2;
-}
-constexpr int layout_vec_samples(int fmt) { return 16 / layout_sample_bytes(fmt); }
 
 // Sample ownership of one lane per step in dc_kernel: G groups of S consecutive samples, one
 // 16-byte load per plane and group (vec == 4: S = layout_vec_samples) or scalar loads (vec == 1: S = 1).

@@ -116,9 +116,7 @@ Refusal plan_correlate(const gat_ctx &c, const Call &call, long long resident_wg
     // bounds each thread by num_samples, src/algorithms.jl:170): lanes beyond the last whole group read zeros through
     // the buffer range check and the N % spv samples behind it are taken one per lane after the step loop.
     // (a stride that is never applied -- one antenna, one block -- does not matter)
-    if (aligned16(sig->re) && (fmt != GAT_LAYOUT_PLANAR || aligned16(sig->im)) && (M == 1 || sig->ant_stride % spv == 0) &&
-        (B == 1 || sig->block_stride % spv == 0) && sig->chan_stride % spv == 0 && N * plane_bytes < (1ll << 31))
-        vec = 4;
+    if (blocks_aligned(sig, B) && sig->chan_stride % spv == 0 && N * plane_bytes < (1ll << 31)) vec = 4;
     if (vec != 4) MT = 1; // unaligned input (scalar loads) is served one antenna per wave
     // the vector kernel reaches a wave's MT antennas through ONE descriptor per plane (antenna = scalar offset): the
     // tile's span of bytes must stay below 2^31 (a lane offset of 2^31 then means "beyond every record")

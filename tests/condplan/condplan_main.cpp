@@ -1,14 +1,16 @@
-// Stand-alone check of the sample conditioner's pure plan (csrc/gat_cond_plan.h): a few thousand random descriptor pairs.
-// Every planned call must cover each (block, sample) exactly once through the units the kernels walk, dealt to the grid
-// exactly once, with the streaming kernel chosen exactly under its rule; every documented refusal must return its code with
-// nothing planned.  Built with -fsanitize=address,undefined by tests/test_condition_plan_host.py.  No memory behind the
-// descriptors is ever touched: the plan reads addresses, not data.
+// Stand-alone check of the pure plans of the operators over raw samples: the sample conditioner's (csrc/gat_cond_plan.h), the
+// sample beamformer's (csrc/gat_beam_plan.h) and the pieces they share with the covariance and the statistics
+// (csrc/gat_sig_plan.h), over a few thousand random cases each.  Every planned call must cover each (block, sample) exactly once
+// through the units the kernels walk, dealt to the grid exactly once, with the streaming kernel chosen exactly under its rule;
+// every documented refusal must return its code with nothing planned; the estimate batches must tile the estimates and every
+// estimate's workgroups its (block, sample) pairs.  Built with -fsanitize=address,undefined by
+// tests/test_condition_plan_host.py.  No memory behind the descriptors is ever touched: the plans read addresses, not data.
 #include <cstdint>
 #include <cstdio>
-#include <cstring>
 #include <random>
 #include <vector>
 
+#include "gat_beam_plan.h"
 #include "gat_cond_plan.h"
 
 using namespace gat;
@@ -28,7 +30,9 @@ int failures = 0;
     } while (0)
 
 const CondPlan kUntouched = {true, true, -7, -7, -7, -7, -7};
-bool untouched(const CondPlan &p) { return std::memcmp(&p, &kUntouched, sizeof p) == 0; }
+template <class Plan> // (field by field: the structs have padding)
+bool split_untouched(const Plan &p) { return p.stream && p.group == -7 && p.chunk == -7 && p.chunks == -7 && p.units == -7 && p.grid == -7; }
+bool untouched(const CondPlan &p) { return split_untouched(p) && p.in_place; }
 
 gat_signal_desc desc(uintptr_t re, uintptr_t im, int layout, int M, long long N, long long as, long long bs)
 {
@@ -47,20 +51,22 @@ gat_signal_desc desc(uintptr_t re, uintptr_t im, int layout, int M, long long N,
 void expect_refusal(const gat_signal_desc *s, int B, const void *prm, uint32_t flags, const gat_signal_desc *o, int code, const char *what)
 {
     CondPlan p = kUntouched;
-    const CondRefusal r = cond_plan(s, B, prm, flags, o, 2048, &p);
+    const Refusal r = cond_plan(s, B, prm, flags, o, 2048, &p);
     CHECK(r.code == code, "%s: got %d, want %d", what, r.code, code);
     CHECK(r.code == GAT_OK || r.msg != nullptr, "%s: a refusal without a message", what);
     CHECK(untouched(p), "%s: a refused call planned something", what);
 }
 
-// walks the plan as the kernels do and counts every (block, sample)
-void check_cover(const CondPlan &p, int B, long long N, int li, int lo)
+// walks a (block, chunk) plan -- the conditioner's or the beamformer's: their kernels decode a unit alike -- as the kernels do
+// and counts every (block, sample); group: what a lane of the streaming kernel owns per step
+template <class Plan>
+void check_cover(const Plan &p, int B, long long N, int group)
 {
     std::vector<unsigned char> hits((size_t)B * (size_t)N, 0);
     std::vector<unsigned char> dealt((size_t)p.units, 0);
     CHECK(p.grid >= 1 && p.grid <= p.units, "grid %lld of %lld units", p.grid, p.units);
     CHECK(p.units == (long long)B * p.chunks && p.units < (1ll << 31), "units");
-    CHECK(p.group == (p.stream ? cond_group_samples(li, lo) : 1), "group %d", p.group);
+    CHECK(p.group == (p.stream ? group : 1), "group %d", p.group);
     CHECK(p.chunk % ((long long)kCondThreads * p.group) == 0 && p.chunk > 0, "chunk %lld", p.chunk);
     for (long long g = 0; g < p.grid; ++g)
         for (long long u = g; u < p.units; u += p.grid) {
@@ -90,6 +96,207 @@ void check_cover(const CondPlan &p, int B, long long N, int li, int lo)
         }
 }
 
+static_assert(kBeamThreads == kCondThreads, "check_cover's lane count is both kernels'");
+const BeamPlan kBeamUntouched = {true, -7, -7, -7, -7, -7};
+bool untouched(const BeamPlan &p) { return split_untouched(p); }
+const double *const kWeights = reinterpret_cast<const double *>(uintptr_t(0x8000));
+
+void expect_beam_refusal(const gat_signal_desc *s, int B, const double *w_re, const double *w_im, int J, const gat_signal_desc *o, int code,
+                         const char *what)
+{
+    BeamPlan p = kBeamUntouched;
+    const Refusal r = beam_plan(s, B, w_re, w_im, J, o, 2048, &p);
+    CHECK(r.code == code, "beam, %s: got %d, want %d", what, r.code, code);
+    CHECK(r.code == GAT_OK || r.msg != nullptr, "beam, %s: a refusal without a message", what);
+    CHECK(untouched(p), "beam, %s: a refused call planned something", what);
+}
+
+// gat_beamform_samples: random (signal, output) pairs; returns the calls that streamed
+int sweep_beam_plans(std::mt19937_64 &rng)
+{
+    auto pick = [&](long long lo, long long hi) { return (long long)(rng() % (uint64_t)(hi - lo + 1)) + lo; };
+    int planned = 0, streamed = 0;
+    for (int it = 0; it < 3000; ++it) {
+        const int li = (int)pick(0, 3), lo = (int)pick(0, 1);
+        const int M = (int)(it % 5 == 0 ? pick(1, 64) : pick(1, 9)), J = (int)(it % 6 == 0 ? pick(1, 64) : pick(1, 5));
+        const int B = (int)(it % 7 == 0 ? pick(1, 300) : pick(1, 4));
+        const long long N = it % 11 == 0 ? pick(1, 300000) / B + 1 : pick(1, 3000);
+        const bool tidy = it % 2 == 0;
+        const long long vi = layout_vec_samples(li), vo = layout_vec_samples(lo);
+        const long long ibs = tidy ? (N + vi - 1) / vi * vi : N + pick(0, 9), obs = tidy ? (N + vo - 1) / vo * vo : N + pick(0, 9);
+        const long long ias = ibs * B + (tidy ? vi * pick(0, 3) : pick(0, 5)), oas = obs * B + (tidy ? vo * pick(0, 3) : pick(0, 5));
+        const uintptr_t ioff = tidy ? 0 : (uintptr_t)pick(0, 3) * layout_sample_bytes(li), ooff = tidy ? 0 : (uintptr_t)pick(0, 3) * layout_sample_bytes(lo);
+        const gat_signal_desc s = desc(0x100000000ull + ioff, 0x200000000ull + ioff, li, M, N, ias, ibs);
+        const gat_signal_desc o = desc(0x300000000ull + ooff, 0x400000000ull + ooff, lo, J, N, oas, obs);
+        const long long want = pick(1, 3) == 1 ? pick(1, 64) : 2048;
+        BeamPlan p = kBeamUntouched;
+        const Refusal r = beam_plan(&s, B, kWeights, kWeights, J, &o, want, &p);
+        CHECK(r.code == GAT_OK, "beam: a valid call was refused: %d %s", r.code, r.msg ? r.msg : "");
+        if (r.code != GAT_OK) continue;
+        ++planned;
+        const bool rule = M <= kBeamStreamMaxAnts && blocks_aligned(&s, B) && blocks_aligned(&o, B);
+        CHECK(p.stream == rule, "beam: stream %d, the rule says %d", (int)p.stream, (int)rule);
+        CHECK(!tidy || M > kBeamStreamMaxAnts || p.stream, "beam: an aligned call did not stream");
+        streamed += p.stream;
+        if ((long long)B * N <= 400000) check_cover(p, B, N, beam_group_samples(li));
+
+        // the refusals, each from this valid pair
+        gat_signal_desc t = s, v = o;
+        expect_beam_refusal(nullptr, B, kWeights, kWeights, J, &o, GAT_ERR_ARG, "null signal");
+        expect_beam_refusal(&s, B, kWeights, kWeights, J, nullptr, GAT_ERR_ARG, "null output");
+        expect_beam_refusal(&s, B, nullptr, kWeights, J, &o, GAT_ERR_ARG, "null w_re");
+        expect_beam_refusal(&s, B, kWeights, nullptr, J, &o, GAT_ERR_ARG, "null w_im");
+        expect_beam_refusal(&s, 0, kWeights, kWeights, J, &o, GAT_ERR_ARG, "no blocks");
+        v = o, v.num_ants = 0;
+        expect_beam_refusal(&s, B, kWeights, kWeights, 0, &v, GAT_ERR_ARG, "no beams");
+        t = s, t.layout = 4;
+        expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_ARG, "bad layout");
+        t = s;
+        t.im = li == GAT_LAYOUT_PLANAR ? nullptr : t.re;
+        expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_ARG, "signal planes");
+        t = s, t.re = nullptr;
+        expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_ARG, "no signal plane");
+        t = s, t.num_samples = 0;
+        expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_ARG, "no samples");
+        t = s, t.num_ants = 0;
+        expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_ARG, "no antennas");
+        t = s, t.ant_stride = -1;
+        expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_ARG, "negative ant_stride");
+        t = s, t.block_stride = -1;
+        expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_ARG, "negative block_stride");
+        v = o, v.ant_stride = -1;
+        expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "negative output ant_stride");
+        v = o, v.block_stride = -1;
+        expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "negative output block_stride");
+        t = s, t.num_ants = GAT_MAX_ARRAY_ANTS + 1;
+        expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_RANGE, "too many antennas");
+        v = o, v.num_ants = GAT_MAX_ARRAY_ANTS + 1;
+        expect_beam_refusal(&s, B, kWeights, kWeights, GAT_MAX_ARRAY_ANTS + 1, &v, GAT_ERR_RANGE, "too many beams");
+        v = o, v.num_ants = J + 1;
+        expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "num_ants is not num_beams");
+        v = o, v.num_samples = N + 1;
+        expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "num_samples mismatch");
+        for (int l : {GAT_LAYOUT_INTERLEAVED_I16, GAT_LAYOUT_INTERLEAVED_I8}) {
+            v = o, v.layout = l, v.im = nullptr;
+            expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_UNSUPPORTED, "an integer output");
+        }
+        v = o, v.layout = -1;
+        expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "bad output layout");
+        t = s, t.chan_stride = 8;
+        expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_UNSUPPORTED, "signal chan_stride");
+        v = o, v.chan_stride = 8;
+        expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_UNSUPPORTED, "output chan_stride");
+        v = o;
+        v.im = lo == GAT_LAYOUT_PLANAR ? nullptr : v.re;
+        expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "output planes");
+        v = o, v.re = nullptr;
+        expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "no output plane");
+        if (M > 1) {
+            t = s, t.ant_stride = 0;
+            expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_ARG, "zero ant_stride");
+            t = s, t.ant_stride = 1ll << 60;
+            expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_RANGE, "signal extent");
+        }
+        if (B > 1) {
+            t = s, t.block_stride = 0;
+            expect_beam_refusal(&t, B, kWeights, kWeights, J, &o, GAT_ERR_ARG, "zero block_stride");
+            v = o, v.block_stride = 0;
+            expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "zero output block_stride");
+        }
+        if (J > 1) {
+            v = o, v.ant_stride = 0;
+            expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "zero output ant_stride");
+            v = o, v.ant_stride = 1ll << 60;
+            expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_RANGE, "output extent");
+        }
+        // overlap: the output starts on the last byte of either input plane, or either output plane is an input plane
+        const uintptr_t in_bytes = (uintptr_t)((B - 1) * ibs + (M - 1) * ias + N) * layout_sample_bytes(li);
+        v = o, v.re = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(s.re) + in_bytes - 1);
+        expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "the output starts on the input's last byte");
+        if (li == GAT_LAYOUT_PLANAR) {
+            v = o, v.re = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(s.im) + in_bytes - 1);
+            expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "the output starts on the last byte of the input's im plane");
+        }
+        if (lo == GAT_LAYOUT_PLANAR) {
+            v = o, v.im = s.re;
+            expect_beam_refusal(&s, B, kWeights, kWeights, J, &v, GAT_ERR_ARG, "the output's im plane is the input's re plane");
+        }
+        // an output that ends where the input begins is no overlap
+        const uintptr_t out_bytes = (uintptr_t)((B - 1) * obs + (J - 1) * oas + N) * layout_sample_bytes(lo);
+        if (lo != GAT_LAYOUT_PLANAR) {
+            v = o, v.re = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(s.re) - out_bytes);
+            BeamPlan z = kBeamUntouched;
+            CHECK(beam_plan(&s, B, kWeights, kWeights, J, &v, want, &z).code == GAT_OK, "beam: an adjacent output was refused");
+        }
+    }
+    std::printf("planned %d beam calls (%d streaming)\n", planned, streamed);
+    CHECK(planned == 3000 && streamed > 700 && streamed < 2300, "the beam sweep lost its balance");
+    return streamed;
+}
+
+// The estimating operators' split (gat_spatial_covariance, gat_sample_stats): the batches must tile the estimates, and inside a
+// batch the kernels' walk -- estimate e owns blocks [e * bpe, min(B, (e + 1) * bpe)) of its launch and G workgroups; its unit u
+// is (block u / splits, segment u % splits); workgroup g takes units g, g + G, ... -- must cover every (block, sample) once.
+void sweep_estimate_splits(std::mt19937_64 &rng)
+{
+    auto pick = [&](long long lo, long long hi) { return (long long)(rng() % (uint64_t)(hi - lo + 1)) + lo; };
+    long batches = 0, batched_calls = 0, split_calls = 0;
+    for (int it = 0; it < 3000; ++it) {
+        const int B = (int)(it % 3 == 0 ? pick(1, 400) : pick(1, 12));
+        const int bpe = (int)(it % 4 == 0 ? B + pick(1, 5) : it % 4 == 1 ? 1 : pick(1, B)); // beyond B; one block; a last estimate that may be short
+        const long long round_to = pick(0, 2) == 0 ? pick(1, 9) : 64 * pick(1, 32);
+        const long long N = it % 5 == 0 ? pick(1, round_to) : pick(1, 3000); // N < round_to among them
+        const long long min_seg = round_to * pick(1, 8);
+        const long long want = pick(0, 3) == 0 ? pick(1, 16) : 64 * pick(1, 64);
+        const size_t slice = (size_t)pick(1, 40000);
+        const int E = (B + bpe - 1) / bpe;
+        // a cap that holds every estimate, some of them (E above e_max), or not even one slice
+        const size_t cap = it % 3 == 0 ? slice * (size_t)pick(1, E) + (size_t)pick(0, (long long)slice - 1) : it % 3 == 1 ? slice * (size_t)E * 4 : (size_t)pick(1, (long long)slice);
+        std::vector<unsigned char> hits((size_t)B * (size_t)N, 0);
+        int next_e = 0;
+        long here = 0;
+        bool split = false;
+        for (EstimateBatches t(B, bpe, slice, cap); t.next(); ++here) {
+            CHECK(t.e0 == next_e && t.en >= 1 && t.e0 + t.en <= E, "batch [%d, +%d) after %d of %d estimates", t.e0, t.en, next_e, E);
+            CHECK((size_t)t.en * slice <= cap || t.en == 1, "a batch of %d estimates beyond the cap", t.en);
+            CHECK(t.b0 == t.e0 * bpe && t.bn >= 1 && t.b0 + t.bn <= B && (t.e0 + t.en == E ? t.b0 + t.bn == B : t.bn == t.en * bpe), "batch blocks [%d, +%d)", t.b0, t.bn);
+            if (!(t.e0 == next_e && t.en >= 1 && t.b0 >= 0 && t.bn >= 1 && t.b0 + t.bn <= B)) break;
+            next_e = t.e0 + t.en;
+            const long long per_est = want / t.en < 1 ? 1 : want / t.en;
+            const EstimateSplit sp = split_estimate(bpe < t.bn ? bpe : t.bn, N, round_to, min_seg, per_est);
+            CHECK(sp.seg_len > 0 && sp.seg_len % round_to == 0, "seg_len %lld for round_to %lld", sp.seg_len, round_to);
+            CHECK(sp.splits >= 1 && (sp.splits - 1) * sp.seg_len < N && sp.splits * sp.seg_len >= N, "splits %lld of %lld samples for N %lld", sp.splits, sp.seg_len, N);
+            CHECK(sp.splits == 1 || sp.splits <= N / min_seg, "segments below min_seg: %lld splits of N %lld, min_seg %lld", sp.splits, N, min_seg);
+            const long long blocks = bpe < t.bn ? bpe : t.bn; // of every estimate but a short last one, whose spare workgroups find no unit
+            CHECK(sp.G >= 1 && sp.G <= per_est && sp.G <= blocks * sp.splits, "G %lld for per_est %lld, %lld blocks", sp.G, per_est, blocks);
+            if (!(sp.seg_len > 0 && sp.splits >= 1 && sp.G >= 1)) break;
+            split |= sp.splits > 1;
+            for (int e = 0; e < t.en; ++e) { // the launch sees blocks [0, bn) from the batch's offset
+                const int b0 = e * bpe, nb = t.bn - b0 < bpe ? t.bn - b0 : bpe;
+                CHECK(nb >= 1, "an estimate without blocks");
+                const long long units = (long long)nb * sp.splits;
+                for (long long g = 0; g < sp.G; ++g)
+                    for (long long u = g; u < units; u += sp.G) {
+                        const int b = t.b0 + b0 + (int)(u / sp.splits);
+                        const long long n0 = (u % sp.splits) * sp.seg_len, n1 = n0 + sp.seg_len < N ? n0 + sp.seg_len : N;
+                        CHECK(b < B && n0 < n1, "unit %lld: block %d samples [%lld, %lld)", u, b, n0, n1);
+                        if (!(b < B && n0 < n1)) continue;
+                        for (long long n = n0; n < n1; ++n) ++hits[(size_t)b * (size_t)N + (size_t)n];
+                    }
+            }
+        }
+        CHECK(next_e == E, "the batches end at estimate %d of %d", next_e, E);
+        for (size_t i = 0; i < hits.size(); ++i)
+            if (hits[i] != 1) {
+                CHECK(false, "estimates: block %zu sample %zu covered %d times", i / (size_t)N, i % (size_t)N, (int)hits[i]);
+                break;
+            }
+        batches += here, batched_calls += here > 1, split_calls += split;
+    }
+    std::printf("split 3000 estimating calls (%ld in several batches, %ld with split blocks)\n", batched_calls, split_calls);
+    CHECK(batches >= 3000 && batched_calls > 300 && split_calls > 300, "the estimate sweep lost its balance");
+}
+
 } // namespace
 
 int main()
@@ -104,29 +311,29 @@ int main()
         const int M = (int)(it % 5 == 0 ? pick(1, 64) : pick(1, 9)), B = (int)(it % 7 == 0 ? pick(1, 300) : pick(1, 4));
         const long long N = it % 11 == 0 ? pick(1, 300000) / B + 1 : pick(1, 3000);
         const bool tidy = it % 2 == 0; // aligned bases and strides: the streaming kernel's candidates
-        const long long vi = cond_vec_samples(li), vo = cond_vec_samples(lo);
+        const long long vi = layout_vec_samples(li), vo = layout_vec_samples(lo);
         const long long ibs = tidy ? (N + vi - 1) / vi * vi : N + pick(0, 9), obs = tidy ? (N + vo - 1) / vo * vo : N + pick(0, 9);
         const long long ias = ibs * B + (tidy ? vi * pick(0, 3) : pick(0, 5)), oas = obs * B + (tidy ? vo * pick(0, 3) : pick(0, 5));
-        const uintptr_t ioff = tidy ? 0 : (uintptr_t)pick(0, 3) * cond_sample_bytes(li), ooff = tidy ? 0 : (uintptr_t)pick(0, 3) * cond_sample_bytes(lo);
+        const uintptr_t ioff = tidy ? 0 : (uintptr_t)pick(0, 3) * layout_sample_bytes(li), ooff = tidy ? 0 : (uintptr_t)pick(0, 3) * layout_sample_bytes(lo);
         // four regions far apart: input planes, output planes
         const gat_signal_desc s = desc(0x100000000ull + ioff, 0x200000000ull + ioff, li, M, N, ias, ibs);
         const gat_signal_desc o = desc(0x300000000ull + ooff, 0x400000000ull + ooff, lo, M, N, oas, obs);
         const long long want = pick(1, 3) == 1 ? pick(1, 64) : 2048;
         CondPlan p = kUntouched;
-        const CondRefusal r = cond_plan(&s, B, prm, (uint32_t)pick(0, 1), &o, want, &p);
+        const Refusal r = cond_plan(&s, B, prm, (uint32_t)pick(0, 1), &o, want, &p);
         CHECK(r.code == GAT_OK, "a valid call was refused: %d %s", r.code, r.msg ? r.msg : "");
         if (r.code != GAT_OK) continue;
         ++planned;
-        const bool rule = M <= kCondStreamMaxAnts && cond_detail::blocks_aligned(&s, B) && cond_detail::blocks_aligned(&o, B);
+        const bool rule = M <= kCondStreamMaxAnts && blocks_aligned(&s, B) && blocks_aligned(&o, B);
         CHECK(p.stream == rule, "stream %d, the rule says %d", (int)p.stream, (int)rule);
         CHECK(!tidy || M > kCondStreamMaxAnts || p.stream, "an aligned call did not stream");
         CHECK(!p.in_place, "in_place without identical descriptors");
         streamed += p.stream;
-        if ((long long)B * N <= 400000) check_cover(p, B, N, li, lo);
+        if ((long long)B * N <= 400000) check_cover(p, B, N, cond_group_samples(li, lo));
 
         // in place: the same descriptor on both sides
         CondPlan q = kUntouched;
-        const CondRefusal r2 = cond_plan(&s, B, prm, 0, &s, want, &q);
+        const Refusal r2 = cond_plan(&s, B, prm, 0, &s, want, &q);
         CHECK(r2.code == GAT_OK && q.in_place, "in place refused: %d", r2.code);
         in_place += r2.code == GAT_OK;
 
@@ -176,7 +383,7 @@ int main()
         t = s, t.ant_stride = 1ll << 60;
         if (M > 1) expect_refusal(&t, B, prm, 0, &o, GAT_ERR_RANGE, "extent");
         // overlap: the output starts inside the input's extent (its last byte, or one sample in), in every plane pairing
-        const uintptr_t in_bytes = (uintptr_t)((B - 1) * ibs + (M - 1) * ias + N) * cond_sample_bytes(li);
+        const uintptr_t in_bytes = (uintptr_t)((B - 1) * ibs + (M - 1) * ias + N) * layout_sample_bytes(li);
         v = o, v.re = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(s.re) + in_bytes - 1);
         expect_refusal(&s, B, prm, 0, &v, GAT_ERR_ARG, "the output starts on the input's last byte");
         if (lo == GAT_LAYOUT_PLANAR) {
@@ -184,26 +391,28 @@ int main()
             expect_refusal(&s, B, prm, 0, &v, GAT_ERR_ARG, "the output's im plane is the input's re plane");
         }
         if (li == GAT_LAYOUT_PLANAR) {
-            v = o, v.re = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(s.im) + cond_sample_bytes(li));
+            v = o, v.re = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(s.im) + layout_sample_bytes(li));
             expect_refusal(&s, B, prm, 0, &v, GAT_ERR_ARG, "the output starts inside the input's im plane");
         }
         // the same memory, not the same elements
         t = s;
-        t.re = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(s.re) + cond_sample_bytes(li));
+        t.re = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(s.re) + layout_sample_bytes(li));
         expect_refusal(&s, B, prm, 0, &t, GAT_ERR_ARG, "in place, one sample on");
         if (B > 1) {
             t = s, t.block_stride = ibs + 1;
             expect_refusal(&s, B, prm, 0, &t, GAT_ERR_ARG, "in place with another block_stride");
         }
         // an output that ends where the input begins is no overlap
-        const uintptr_t out_bytes = (uintptr_t)((B - 1) * obs + (M - 1) * oas + N) * cond_sample_bytes(lo);
+        const uintptr_t out_bytes = (uintptr_t)((B - 1) * obs + (M - 1) * oas + N) * layout_sample_bytes(lo);
         if (lo != GAT_LAYOUT_PLANAR) {
             v = o, v.re = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(s.re) - out_bytes);
             CondPlan z = kUntouched;
             CHECK(cond_plan(&s, B, prm, 0, &v, want, &z).code == GAT_OK, "an adjacent output was refused");
         }
     }
-    std::printf("planned %d calls (%d streaming, %d in place), %d failures\n", planned, streamed, in_place, failures);
     CHECK(planned == 4000 && streamed > 1000 && streamed < 3000, "the sweep lost its balance");
+    sweep_beam_plans(rng);
+    sweep_estimate_splits(rng);
+    std::printf("planned %d calls (%d streaming, %d in place), %d failures\n", planned, streamed, in_place, failures);
     return failures ? 1 : 0;
 }

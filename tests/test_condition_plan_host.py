@@ -1,7 +1,8 @@
-"""The pure plan of gat_condition_samples (csrc/gat_cond_plan.h: refusals, kernel choice, work split) compiled stand-alone
-with its own main (tests/condplan/condplan_main.cpp) under AddressSanitizer and UBSan, and run: a few thousand random
-descriptor pairs, every (block, sample) covered exactly once, every documented refusal with nothing planned.  The program
-stands alone; nothing is loaded into Python."""
+"""The pure plans of the operators over raw samples -- gat_condition_samples (csrc/gat_cond_plan.h), gat_beamform_samples
+(csrc/gat_beam_plan.h) and what they share with the covariance and the statistics (csrc/gat_sig_plan.h: descriptor check, fast-path
+rule, overlap test, work splits, estimate batches) -- compiled stand-alone with their own main (tests/condplan/condplan_main.cpp)
+under AddressSanitizer and UBSan, and run: a few thousand random cases each, every (block, sample) covered exactly once, every
+documented refusal with nothing planned.  The program stands alone; nothing is loaded into Python."""
 import os
 import shutil
 import subprocess
