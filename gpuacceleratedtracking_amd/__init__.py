@@ -22,6 +22,8 @@ from .correlator import (EarlyPromptLateCorrelator, NumAccumulators, NumAnts, ge
                          get_correlator_sample_shifts, get_num_accumulators, get_num_ants)
 from .frontend import (GAT_COND_BLANK_ALL_ANTS, SampleStats, agc_params, agc_params_host, condition_samples,  # noqa: F401
                        condition_samples_host, requantize, sample_stats)
+from .filtering import (channelize, filter_samples, filter_samples_host, filter_stream, lowpass_taps, notch_taps,  # noqa: F401
+                        shift_taps)
 from .gen_signal import StructSignal, gen_blank_signal, gen_signal, gen_signal_stream, make_params  # noqa: F401
 from .loop import ResidentTrackingLoop, TrackingLoop  # noqa: F401
 from .sharding import DeviceGroup, ShardPlan, gather_outputs, shard_channels, shard_params  # noqa: F401

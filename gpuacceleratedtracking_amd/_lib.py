@@ -28,6 +28,8 @@ GAT_BF_CONVENTIONAL, GAT_BF_MVDR, GAT_BF_POWER_INVERSION = 0, 1, 2
 GAT_MAX_ARRAY_ANTS = 64
 # sample conditioning (gat_condition_samples / gat_sample_stats flags)
 GAT_COND_BLANK_ALL_ANTS = 1
+# sample filtering (gat_filter_samples limits)
+GAT_MAX_FIR_TAPS, GAT_MAX_FIR_DECIMATION = 256, 64
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -53,6 +55,8 @@ EXPORTS = [
     "gat_tracking_update_host_weighted", "gat_tracking_run_weighted", "gat_beamform_samples",
     # sample conditioning: level statistics, pulse blanking, AGC, requantisation
     "gat_condition_samples", "gat_condition_samples_host", "gat_sample_stats", "gat_agc_update", "gat_agc_update_host",
+    # sample filtering: complex FIR, decimation and an oscillator over the raw samples
+    "gat_filter_samples", "gat_filter_samples_host",
 ]
 
 
@@ -148,6 +152,16 @@ COND_PARAMS_DTYPE = np.dtype([("scale", "<f4"), ("dc_re", "<f4"), ("dc_im", "<f4
 SAMPLE_STATS_DTYPE = np.dtype([("kept", "<i8"), ("blanked", "<i8"), ("sum_re", "<f8"), ("sum_im", "<f8"), ("sum_pow", "<f8"),
                                ("max_abs", "<f4"), ("pad_", "<f4")])
 assert C.sizeof(AgcConfig) == 32 and COND_PARAMS_DTYPE.itemsize == 16 and SAMPLE_STATS_DTYPE.itemsize == 48
+
+
+class FirConfig(C.Structure):
+    """gat_fir_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("num_taps", C.c_int32), ("decimation", C.c_int32), ("nco_step", C.c_double),
+                ("nco_phase", C.c_double)]
+
+
+assert C.sizeof(FirConfig) == 32
 
 
 _LIB = None
@@ -248,6 +262,8 @@ def load(build_if_missing: bool = True):
         "gat_sample_stats": (i32, [vp, sp, i32, i32, vp, u32, vp]),
         "gat_agc_update": (i32, [vp, vp, i32, C.POINTER(AgcConfig), vp]),
         "gat_agc_update_host": (i32, [vp, i32, C.POINTER(AgcConfig), vp]),
+        "gat_filter_samples": (i32, [vp, sp, i32, vp, vp, C.POINTER(FirConfig), sp]),
+        "gat_filter_samples_host": (i32, [sp, i32, vp, vp, C.POINTER(FirConfig), sp]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

@@ -777,6 +777,57 @@ GAT_API int32_t gat_agc_update(gat_ctx *ctx, const gat_sample_stats_t *stats_dev
 GAT_API int32_t gat_agc_update_host(const gat_sample_stats_t *stats_host, int32_t num_ants, const gat_agc_config *cfg,
                                     gat_cond_params *params_host);
 
+/* ---- sample filtering: complex FIR, decimation and an oscillator over the raw samples ------------------------------------
+ * A stream-in, stream-out stage that changes a stream's band and rate: a notch against a CW tone, a channeliser from a
+ * wideband front end down to the rate the search and the correlators are fast at.  For block b, antenna m and output
+ * sample q (0 <= q < Q), with T complex float32 taps g, decimation D and blocks of N input samples:
+ *     Q     = (N - T) / D + 1                    (integer division; N >= T)
+ *     p     = q*D + (T-1)                        newest input sample of output q
+ *     z     = sum_{t=0}^{T-1} g[t] * x[p - t]    "valid" convolution: nothing outside the block is read
+ *     P     = b*block_stride(signal) + p         position in the antenna's stream
+ *     theta = fma((double)P, step, phase)        cycles; step - rint(step) and phase - floor(phase) first (exact, but for
+ *                                                a negative phase above -2^-53, which becomes 1.0)
+ *     y     = (c - j s) * z                      (c, s): the library's float polynomial of exp(j 2 pi theta)
+ * The sum runs in float32 in tap order from +0, per tap zr = fma(g_re, x_re, zr), zr = fma(-g_im, x_im, zr), zi =
+ * fma(g_re, x_im, zi), zi = fma(g_im, x_re, zi); y_re = fma(s, z_im, c*z_re), y_im = fma(-s, z_re, c*z_im).  nco_step == 0
+ * && nco_phase == 0 is the plain filter: y = z bit for bit.  Integer samples convert exactly; NaN and inf propagate by the
+ * IEEE rules.  The bits depend neither on the kernel nor on the work split, and the host twin gives the same ones:
+ *     |y - y64| <= [(2T + 8) * 2^-24 + 2 pi * 2^-53 * (P/2 + 2)] * sum_t (|g_re| + |g_im|)(|x_re| + |x_im|)  per component.
+ * There is no state between calls: a continuous stream is described by overlapping blocks (overlap-save by descriptor:
+ * input num_samples = Q*D + T - 1 and block_stride = Q*D, output block_stride = Q), and because the oscillator runs on the
+ * stream position P every partition of one stream into blocks gives the same bits.  "Mix down by nu cycles/sample, then
+ * low-pass with h" is this rule with g[t] = h[t] * exp(+j 2 pi nu t) and nco_step = nu: one sincos per output.
+ * signal: any layout, 1 <= M <= GAT_MAX_ARRAY_ANTS, any base alignment and strides, overlapping blocks included,
+ * chan_stride 0.  taps: T floats each, device memory (the host twin: host memory).  out: describes device memory the call
+ * WRITES: GAT_LAYOUT_PLANAR or GAT_LAYOUT_INTERLEAVED float32, num_ants == M, num_samples == Q, its own strides; nothing
+ * outside the described elements is written.  gat_acquire, gat_spatial_covariance, gat_beamform_samples, gat_sample_stats,
+ * gat_condition_samples and the correlators take it unchanged.
+ * With every block of every antenna starting on a 16-byte boundary on both sides a workgroup stages its samples through
+ * LDS with 16-byte loads (the tiled kernel); everything else runs one output per lane with scalar loads.
+ * gat_last_launch_info afterwards: vec = 1 (general) or the samples of a 16-byte load (tiled), workgroups, threads, splits
+ * (chunks of a (block, antenna) pair's outputs), ant_tile = 1.  Enqueues on the context's stream, does not synchronise and
+ * allocates nothing.  Refusals, all before any launch: GAT_ERR_ARG for null pointers, a wrong struct_size, num_blocks < 1,
+ * bad sizes or strides, N < T, out->num_samples != Q, out->num_ants != M, a non-finite nco_step or nco_phase and an output
+ * whose byte extent overlaps the input's (there is no in-place form: an output reads T inputs); GAT_ERR_RANGE for
+ * num_taps or decimation outside their limits, M above 64 and (num_blocks - 1) * block_stride + N above 2^31 (theta is one
+ * double rounding of a value below P/2; longer streams advance nco_phase per call); GAT_ERR_UNSUPPORTED for an integer
+ * output layout or chan_stride != 0 on either side. */
+#define GAT_MAX_FIR_TAPS 256
+#define GAT_MAX_FIR_DECIMATION 64
+typedef struct gat_fir_config {
+    uint32_t struct_size; /* sizeof(gat_fir_config) */
+    int32_t num_taps;     /* 1 .. GAT_MAX_FIR_TAPS */
+    int32_t decimation;   /* 1 .. GAT_MAX_FIR_DECIMATION */
+    double nco_step;      /* cycles per INPUT sample, finite */
+    double nco_phase;     /* cycles, finite */
+} gat_fir_config;
+GAT_API int32_t gat_filter_samples(gat_ctx *ctx, const gat_signal_desc *signal, int32_t num_blocks, const float *taps_re_dev,
+                                   const float *taps_im_dev, const gat_fir_config *cfg, const gat_signal_desc *out);
+/* The same rule in a plain loop on the HOST (csrc/gat_fir.h, shared with the device): every pointer is host memory; needs
+ * no context and no device.  The bit-exact reference of the device call, with the same refusals. */
+GAT_API int32_t gat_filter_samples_host(const gat_signal_desc *signal, int32_t num_blocks, const float *taps_re_host,
+                                        const float *taps_im_host, const gat_fir_config *cfg, const gat_signal_desc *out);
+
 #ifdef __cplusplus
 }
 #endif

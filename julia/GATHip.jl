@@ -830,6 +830,39 @@ function agc_update_host(stats::Vector{SampleStats}, cfg::AgcConfig)
     rc == GAT_OK || error("gat_agc_update_host: status $rc")
     params
 end
+# ---- sample filtering: complex FIR, decimation and an oscillator over the raw samples (include/gat.h) --------------------------
+const GAT_MAX_FIR_TAPS = 256
+const GAT_MAX_FIR_DECIMATION = 64
+struct FirConfig     # gat_fir_config
+    struct_size::UInt32
+    num_taps::Int32
+    decimation::Int32
+    nco_step::Float64    # cycles per INPUT sample
+    nco_phase::Float64   # cycles
+end
+FirConfig(num_taps::Integer, decimation::Integer = 1, nco_step::Real = 0.0, nco_phase::Real = 0.0) =
+    FirConfig(UInt32(sizeof(FirConfig)), Int32(num_taps), Int32(decimation), Float64(nco_step), Float64(nco_phase))
+# outputs of a block of N samples: the "valid" convolution, decimated
+fir_outputs(N::Integer, cfg::FirConfig) = (N - cfg.num_taps) ÷ cfg.decimation + 1
+# the filtered stream: y[q] = exp(-2 pi j (P step + phase)) sum_t g[t] x[q D + T - 1 - t]; `out` describes the device memory the call
+# writes (GAT_LAYOUT_PLANAR or GAT_LAYOUT_INTERLEAVED, the signal's num_ants, num_samples = fir_outputs(desc.num_samples, cfg)) and is
+# afterwards a signal for acquire!, spatial_covariance!, condition_samples! and the correlators; taps: num_taps Float32 each, on the device
+function filter_samples!(ctx::Context, desc::SignalDesc, num_blocks::Integer, taps_re::Ptr{Cfloat}, taps_im::Ptr{Cfloat}, cfg::FirConfig,
+                         out::SignalDesc)
+    check(ctx, ccall((:gat_filter_samples, libgat), Int32,
+                     (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Ptr{Cfloat}, Ptr{Cfloat}, Ref{FirConfig}, Ref{SignalDesc}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), taps_re, taps_im, Ref(cfg), Ref(out)))
+    out
+end
+# the same rule on host memory (both descriptors and the taps are host arrays): the bit-exact reference of the device call
+function filter_samples_host!(desc::SignalDesc, num_blocks::Integer, taps_re::Vector{Float32}, taps_im::Vector{Float32}, cfg::FirConfig,
+                              out::SignalDesc)
+    rc = ccall((:gat_filter_samples_host, libgat), Int32,
+               (Ref{SignalDesc}, Int32, Ptr{Cfloat}, Ptr{Cfloat}, Ref{FirConfig}, Ref{SignalDesc}),
+               Ref(desc), Int32(num_blocks), taps_re, taps_im, Ref(cfg), Ref(out))
+    rc == GAT_OK || error("gat_filter_samples_host: status $rc")
+    out
+end
 # tracking_update! / tracking_update_host! / tracking_run! with weights [M x K] (C_NULL planes: the unweighted calls)
 function tracking_update_weighted!(ctx::Context, acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, K::Integer, M::Integer, cfg::LoopConfig,
                                    state_dev::Ptr{Cvoid}, cur_dev::Ptr{Cvoid}, next_dev::Ptr{Cvoid}, w_re::Ptr{Float64}, w_im::Ptr{Float64})
