@@ -30,6 +30,8 @@ GAT_MAX_ARRAY_ANTS = 64
 GAT_COND_BLANK_ALL_ANTS = 1
 # sample filtering (gat_filter_samples limits)
 GAT_MAX_FIR_TAPS, GAT_MAX_FIR_DECIMATION = 256, 64
+# sample spectrum (gat_sample_spectrum limits)
+GAT_MIN_SPECTRUM_BINS, GAT_MAX_SPECTRUM_BINS, GAT_MAX_SPECTRUM_SEGMENTS = 64, 4096, 4096
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -57,6 +59,8 @@ EXPORTS = [
     "gat_condition_samples", "gat_condition_samples_host", "gat_sample_stats", "gat_agc_update", "gat_agc_update_host",
     # sample filtering: complex FIR, decimation and an oscillator over the raw samples
     "gat_filter_samples", "gat_filter_samples_host",
+    # sample spectrum: the summed periodogram of the raw samples per block and antenna
+    "gat_sample_spectrum", "gat_sample_spectrum_host",
 ]
 
 
@@ -164,6 +168,15 @@ class FirConfig(C.Structure):
 assert C.sizeof(FirConfig) == 32
 
 
+class SpectrumConfig(C.Structure):
+    """gat_spectrum_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("num_bins", C.c_int32), ("hop", C.c_int32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(SpectrumConfig) == 16
+
+
 _LIB = None
 
 
@@ -264,6 +277,8 @@ def load(build_if_missing: bool = True):
         "gat_agc_update_host": (i32, [vp, i32, C.POINTER(AgcConfig), vp]),
         "gat_filter_samples": (i32, [vp, sp, i32, vp, vp, C.POINTER(FirConfig), sp]),
         "gat_filter_samples_host": (i32, [sp, i32, vp, vp, C.POINTER(FirConfig), sp]),
+        "gat_sample_spectrum": (i32, [vp, sp, i32, vp, C.POINTER(SpectrumConfig), vp]),
+        "gat_sample_spectrum_host": (i32, [sp, i32, vp, C.POINTER(SpectrumConfig), vp]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

@@ -17,7 +17,8 @@ SOURCES = ["gat_dc_f0.hip", "gat_dc_f1.hip", "gat_dc_f2.hip", "gat_dc_f3.hip", "
            "gat_resident_f2.hip", "gat_resident_f3.hip",
            "gat_kernels.hip", "gat_mfma.hip", "gat_mfma_bf16.hip", "gat_api.cpp", "gat_planner.cpp", "gat_group.cpp",
            "gat_resident_api.cpp", "gat_codes.cpp", "gat_acq.hip", "gat_acq_api.cpp", "gat_array.hip", "gat_array_api.cpp",
-           "gat_beam.hip", "gat_beam_api.cpp", "gat_cond.hip", "gat_cond_api.cpp", "gat_fir.hip", "gat_fir_api.cpp"]
+           "gat_beam.hip", "gat_beam_api.cpp", "gat_cond.hip", "gat_cond_api.cpp", "gat_fir.hip", "gat_fir_api.cpp",
+           "gat_spec.hip", "gat_spec_api.cpp"]
 # gat_version.cpp is not in SOURCES: it is compiled at every link with the build's identity (git commit, flags)
 HEADERS = [os.path.join(CSRC, "gat_internal.h"), os.path.join(CSRC, "gat_sig_plan.h"), os.path.join(CSRC, "gat_phase.h"), os.path.join(CSRC, "gat_dc.h"),
            os.path.join(CSRC, "gat_dc_body.inc"), os.path.join(CSRC, "gat_resident.h"), os.path.join(CSRC, "gat_ctx.h"),
@@ -26,6 +27,8 @@ HEADERS = [os.path.join(CSRC, "gat_internal.h"), os.path.join(CSRC, "gat_sig_pla
            os.path.join(CSRC, "gat_beam_kernels.h"),
            os.path.join(CSRC, "gat_cond.h"), os.path.join(CSRC, "gat_cond_plan.h"), os.path.join(CSRC, "gat_cond_kernels.h"),
            os.path.join(CSRC, "gat_fir.h"), os.path.join(CSRC, "gat_fir_plan.h"), os.path.join(CSRC, "gat_fir_kernels.h"),
+           os.path.join(CSRC, "gat_sample_load.h"), os.path.join(CSRC, "gat_spec.h"), os.path.join(CSRC, "gat_spec_plan.h"),
+           os.path.join(CSRC, "gat_spec_kernels.h"),
            os.path.join(ROOT, "include", "gat.h")]
 
 
@@ -129,7 +132,9 @@ def build_libgat(force: bool = False, verbose: bool = False, extra_flags: tuple[
             # re-packing them into v_pk_fma_f32 + operand-pairing moves
             # (the sample beamformer too: packed FMAs want operand pairs in vector registers -- with the vectoriser on,
             # beam_stream_kernel<planar, 4, 4> takes 156 VGPRs instead of 124 and <int8, 8, 4> 256 with 8 spilled instead of 246)
-            per_file = ("-fno-slp-vectorize",) if vector_tu or src == "gat_beam.hip" else ()
+            # (the sample spectrum too: the vectoriser packs its butterflies, 12 - 50 more VGPRs an instance and one wave a SIMD at
+            # F = 4096; without it the same run is 4 - 20 % faster on every shape -- DESIGN.md 4.10)
+            per_file = ("-fno-slp-vectorize",) if vector_tu or src in ("gat_beam.hip", "gat_spec.hip") else ()
             jobs.append([hipcc_path(), *_flags(tuple(extra_here) + per_file), "-c", sp, "-o", obj])
 
     def run(cmd):
@@ -155,7 +160,7 @@ def build_libgat(force: bool = False, verbose: bool = False, extra_flags: tuple[
             hipcc_v = "unknown"
         with open(BUILD_INFO, "w") as f:
             json.dump({"kernel_sources_git": ident, "repo_head_git": repo_head(), "flags": flag_str, "hipcc": hipcc_v,
-                       "recipe": " ".join(_flags()[:-2]), "built_utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime())}, f)
+                       "recipe": " ".join(_flags()[:-2]), "no_slp_vectorize": "gat_dc_f*.hip gat_resident_f*.hip gat_beam.hip gat_spec.hip", "built_utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime())}, f)
     return out
 
 

@@ -828,6 +828,58 @@ GAT_API int32_t gat_filter_samples(gat_ctx *ctx, const gat_signal_desc *signal, 
 GAT_API int32_t gat_filter_samples_host(const gat_signal_desc *signal, int32_t num_blocks, const float *taps_re_host,
                                         const float *taps_im_host, const gat_fir_config *cfg, const gat_signal_desc *out);
 
+/* ---- sample spectrum: the summed periodogram (Welch) of the raw samples, per block and antenna ----------------------------
+ * How a receiver looks at the band it works in: where a tone sits before notch_taps can remove it, whether a level is
+ * noise or a jammer.  F = num_bins (a power of two, 64 .. 4096), H = hop (1 .. F), w a real float32 window of F values,
+ * blocks of N >= F samples, S = (N - F) / H + 1 segments a block (1 .. 4096).  For block b, antenna m, segment s:
+ *     v[n]  = w[n] * x[s*H + n], 0 <= n < F        one rounded float32 product per component; integer samples convert
+ *                                                  exactly; nothing outside the block is read, and the block's last
+ *                                                  (N - F) mod H samples are not used
+ *     tw[i] = (c, -s), 0 <= i < F/2                (c, s) the library's float polynomial of exp(j 2 pi i/F): i/F is exact
+ *     X[f]  = sum_n v[n] exp(-j 2 pi f n / F)      by ONE sequence of operations: radix-2 decimation in time on the
+ *                                                  bit-reversed v, stages j = 0 .. log2F - 1, h = 2^j, group g, k < h:
+ *                 a = v[2hg + k], b = v[2hg + k + h], W = tw[k*F/(2h)]
+ *                 t_re = fma(-W_im, b_im, W_re*b_re), t_im = fma(W_im, b_re, W_re*b_im)   (the inner product rounded)
+ *                 a' = a + t, b' = a - t
+ *     p     = fma(X_im, X_im, X_re*X_re)
+ *     power[b][m][f] = sum_s p                     one float32 sum in segment order from +0
+ * power: float32 [num_blocks][M][F], contiguous, in FFT order: bin f is f/F cycles per sample for f < F/2 and (f - F)/F
+ * above.  It is the SUM over the segments, not the mean.  NaN and inf propagate by the IEEE rules: a NaN sample poisons
+ * exactly the segments that hold it.  The bits depend neither on the kernel nor on the work split, and the host twin gives
+ * the same ones.  With A = sum_n |w[n]| (|x_re| + |x_im|) of a segment and u = 2^-24 (DESIGN.md 4.10 derives them):
+ *     |X - X64| <= E = (11 log2F + 1) u A                         per component, and in modulus
+ *     |p - p64| <= (2A + E) E + 2u(1 + u) (A + E)^2               per bin of one segment
+ *     |power - power64| <= sum_s [the above] + (S-1)u / (1 - (S-1)u) * sum_s (A + E)^2 (1 + 2u(1 + u)).
+ * There is no state between calls: the averaging unit is the block.  A spectrogram is blocks of one segment (N = F); a
+ * long stream is several blocks by descriptor (block_stride = S*H continues the segments; overlapping blocks are
+ * allowed).  The sum over a block's segments is sequential by rule, so the work unit is a (block, antenna) pair and is
+ * never split: parallelism comes from num_blocks * M.
+ * signal: any layout, 1 <= M <= GAT_MAX_ARRAY_ANTS, any base alignment and strides, chan_stride 0.  window: F floats,
+ * device memory (the host twin: host memory).  With every block of every antenna starting on a 16-byte boundary and H a
+ * multiple of the samples one 16-byte load holds, the kernel loads with 16-byte loads; everything else runs scalar
+ * loads.  gat_last_launch_info afterwards: vec = the samples per load (1: scalar), workgroups, threads = 256, splits = 1,
+ * ant_tile = 1, lds_bytes, channels_per_wg = the (block, antenna) pairs a workgroup transforms side by side (256 lanes
+ * hold one transform of F >= 1024, four of F = 256, sixteen of F = 64).  Enqueues on the context's stream, does not
+ * synchronise and allocates nothing.  Refusals, all before any launch: GAT_ERR_ARG for null pointers, a wrong
+ * struct_size, num_blocks < 1, bad sizes or strides, N < F, non-zero flags and an output whose byte extent overlaps the
+ * input's; GAT_ERR_RANGE for num_bins not a power of two or outside its limits, hop outside 1 .. F, S above
+ * GAT_MAX_SPECTRUM_SEGMENTS and M above 64; GAT_ERR_UNSUPPORTED for chan_stride != 0. */
+#define GAT_MIN_SPECTRUM_BINS 64
+#define GAT_MAX_SPECTRUM_BINS 4096
+#define GAT_MAX_SPECTRUM_SEGMENTS 4096
+typedef struct gat_spectrum_config {
+    uint32_t struct_size; /* sizeof(gat_spectrum_config) */
+    int32_t num_bins;     /* F: a power of two, GAT_MIN_SPECTRUM_BINS .. GAT_MAX_SPECTRUM_BINS */
+    int32_t hop;          /* H: 1 .. num_bins */
+    uint32_t flags;       /* 0 */
+} gat_spectrum_config;
+GAT_API int32_t gat_sample_spectrum(gat_ctx *ctx, const gat_signal_desc *signal, int32_t num_blocks, const float *window_dev,
+                                    const gat_spectrum_config *cfg, float *power_dev);
+/* The same rule in a plain loop on the HOST (csrc/gat_spec.h, shared with the device): every pointer is host memory; needs
+ * no context and no device.  The bit-exact reference of the device call, with the same refusals. */
+GAT_API int32_t gat_sample_spectrum_host(const gat_signal_desc *signal, int32_t num_blocks, const float *window_host,
+                                         const gat_spectrum_config *cfg, float *power_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -863,6 +863,36 @@ function filter_samples_host!(desc::SignalDesc, num_blocks::Integer, taps_re::Ve
     rc == GAT_OK || error("gat_filter_samples_host: status $rc")
     out
 end
+# ---- sample spectrum: the summed periodogram of the raw samples per block and antenna (include/gat.h) ---------------------------
+const GAT_MIN_SPECTRUM_BINS = 64
+const GAT_MAX_SPECTRUM_BINS = 4096
+const GAT_MAX_SPECTRUM_SEGMENTS = 4096
+struct SpectrumConfig     # gat_spectrum_config
+    struct_size::UInt32
+    num_bins::Int32      # F: a power of two, 64 .. 4096
+    hop::Int32           # H: 1 .. F
+    flags::UInt32        # 0
+end
+SpectrumConfig(num_bins::Integer, hop::Integer = num_bins ÷ 2) =
+    SpectrumConfig(UInt32(sizeof(SpectrumConfig)), Int32(num_bins), Int32(hop), UInt32(0))
+# segments of a block of N samples
+spectrum_segments(N::Integer, cfg::SpectrumConfig) = (N - cfg.num_bins) ÷ cfg.hop + 1
+# power[f, m, b] (Float32, num_bins x num_ants x num_blocks in Julia's order, on the device) = sum over the block's segments of
+# |FFT(window .* x[s H .+ (1:F)])|^2 in FFT order: the sum, not the mean; window: num_bins Float32 on the device
+function sample_spectrum!(ctx::Context, desc::SignalDesc, num_blocks::Integer, window::Ptr{Cfloat}, cfg::SpectrumConfig, power::Ptr{Cfloat})
+    check(ctx, ccall((:gat_sample_spectrum, libgat), Int32,
+                     (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Ptr{Cfloat}, Ref{SpectrumConfig}, Ptr{Cfloat}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), window, Ref(cfg), power))
+    power
+end
+# the same rule on host memory: the bit-exact reference of the device call
+function sample_spectrum_host!(desc::SignalDesc, num_blocks::Integer, window::Vector{Float32}, cfg::SpectrumConfig, power::Array{Float32})
+    rc = ccall((:gat_sample_spectrum_host, libgat), Int32,
+               (Ref{SignalDesc}, Int32, Ptr{Cfloat}, Ref{SpectrumConfig}, Ptr{Cfloat}),
+               Ref(desc), Int32(num_blocks), window, Ref(cfg), power)
+    rc == GAT_OK || error("gat_sample_spectrum_host: status $rc")
+    power
+end
 # tracking_update! / tracking_update_host! / tracking_run! with weights [M x K] (C_NULL planes: the unweighted calls)
 function tracking_update_weighted!(ctx::Context, acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, K::Integer, M::Integer, cfg::LoopConfig,
                                    state_dev::Ptr{Cvoid}, cur_dev::Ptr{Cvoid}, next_dev::Ptr{Cvoid}, w_re::Ptr{Float64}, w_im::Ptr{Float64})
