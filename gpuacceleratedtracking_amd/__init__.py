@@ -10,7 +10,7 @@ from ._lib import GAT_FLAG_GRAPH, GAT_MC_AUTO, GAT_MC_BF16_SPLIT, GAT_MC_F32, GA
 from ._lib import (GAT_FLAG_ATOMIC, GAT_LAYOUT_INTERLEAVED, GAT_LAYOUT_INTERLEAVED_I8,  # noqa: F401
                    GAT_LAYOUT_INTERLEAVED_I16, GAT_LAYOUT_PLANAR, SAMPLE_BYTES, GatError,
                    library_path, load as load_library)
-from .acquisition import AcquisitionResult, acquire, acquisition_stats_host, tracking_init  # noqa: F401
+from .acquisition import AcquisitionResult, acquire, acquire_fft_host, acquire_fft_plan, acquisition_stats_host, tracking_init  # noqa: F401
 from .algorithms import (ALGODICT, ALGODICTINV, MEMDICT, REDDICT, KernelAlgorithm, ReductionAlgorithm,  # noqa: F401
                          ReplicaAlgorithm, cpu_reduce_partial_sum, cuda_reduce_partial_sum, kernel_algorithm)
 from .array import (GAT_BF_CONVENTIONAL, GAT_BF_MVDR, GAT_BF_POWER_INVERSION, beamform, beamform_samples,  # noqa: F401

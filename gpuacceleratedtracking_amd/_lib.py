@@ -51,7 +51,7 @@ EXPORTS = [
     # measurement: per-call statistics, the in-run read ceiling; the texture-addressing study
     "gat_timer_lap", "gat_timer_laps", "gat_debug_read_stream", "gat_gen_code_replica_texaddr",
     # acquisition: the PRN x Doppler x code-phase search that seeds the tracking loops
-    "gat_acquire", "gat_acq_stats_host",
+    "gat_acquire", "gat_acq_stats_host", "gat_acquire_fft", "gat_acquire_fft_plan", "gat_acquire_fft_host",
     # antenna-array processing: spatial covariance, beamformer weights, beamformed accumulators and loop
     "gat_spatial_covariance", "gat_array_weights", "gat_array_weights_host", "gat_beamform", "gat_tracking_update_weighted",
     "gat_tracking_update_host_weighted", "gat_tracking_run_weighted", "gat_beamform_samples",
@@ -143,6 +143,17 @@ ACQ_RESULT_DTYPE = np.dtype([("prn", "<i4"), ("detected", "<i4"), ("doppler_bin"
                              ("peak_to_second", "<f8"), ("cn0_dbhz", "<f8"), ("carrier_doppler_hz", "<f8"),
                              ("code_phase_chips", "<f8"), ("num_noise_bins", "<i8")])
 assert C.sizeof(AcqConfig) == 72 and ACQ_RESULT_DTYPE.itemsize == 80
+
+
+class AcqFftPlan(C.Structure):
+    """gat_acq_fft_plan (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("fft_log2", C.c_int32), ("num_segments", C.c_int32), ("segment_lags", C.c_int32),
+                ("passes", C.c_int32), ("doppler_batch", C.c_int32), ("unit_batch", C.c_int32), ("unit_groups", C.c_int32),
+                ("scratch_bytes", C.c_int64)]
+
+
+assert C.sizeof(AcqFftPlan) == 40
 
 
 class AgcConfig(C.Structure):
@@ -265,6 +276,9 @@ def load(build_if_missing: bool = True):
         "gat_gen_code_replica_texaddr": (i32, [vp, vp, i64, i32, dbl, dbl, dbl, i64, i32, i32]),
         "gat_acquire": (i32, [vp, sp, i32, i32p, i32, dbl, C.POINTER(AcqConfig), vp, vp]),
         "gat_acq_stats_host": (i32, [vp, i32, i32, i32, C.POINTER(AcqConfig), dbl, i64, vp]),
+        "gat_acquire_fft": (i32, [vp, sp, i32, i32p, i32, dbl, C.POINTER(AcqConfig), vp, vp]),
+        "gat_acquire_fft_plan": (i32, [sp, i32, i32, dbl, C.POINTER(AcqConfig), i32, i32, i32, i32, i32, C.POINTER(AcqFftPlan)]),
+        "gat_acquire_fft_host": (i32, [sp, i32, vp, i32, i32, i32p, i32, dbl, C.POINTER(AcqConfig), i32, i32, vp]),
         "gat_spatial_covariance": (i32, [vp, sp, i32, i32, vp, vp]),
         "gat_array_weights": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, dbl, vp, vp]),
         "gat_array_weights_host": (i32, [vp, vp, i32, vp, vp, i32, i32, dbl, vp, vp]),

@@ -63,9 +63,9 @@ def _as_desc(signal, num_samples: int, num_blocks: int, block_stride: int):
 
 def acquire(system: GNSSSystem, signal, sampling_frequency: float, prns=range(32), *, num_samples: int | None = None,
             interm_freq: float = 0.0, max_doppler: float = 7000.0, doppler_step: float | None = None, dopplers=None,
-            code_step_chips: float = 0.5, first_shift: int = 0, num_code_bins: int | None = None, num_blocks: int = 1,
+            code_step_chips: float | None = 0.5, first_shift: int = 0, num_code_bins: int | None = None, num_blocks: int = 1,
             block_stride: int | None = None, min_peak_ratio: float = 2.0, keep_power: bool = False,
-            ctx: Context | None = None, device=None, weights=None) -> list[AcquisitionResult]:
+            ctx: Context | None = None, device=None, weights=None, method: str = "direct") -> list[AcquisitionResult]:
     """Search ``prns`` (code-table columns, 0-based) in ``num_blocks`` blocks of ``num_samples`` samples (default: one
     code period) starting at sample 0 of ``signal``, ``block_stride`` apart (default ``num_samples``).
 
@@ -79,7 +79,19 @@ def acquire(system: GNSSSystem, signal, sampling_frequency: float, prns=range(32
     across them enters at full strength; a beam with a null towards it does not.  With power-inversion weights the result's
     ``CN0``, ``noise_power`` and ``signal_power`` are those of the beam's output (its noise is sum |w_m|^2 times one
     antenna's, and the satellite's gain is whatever the null leaves), not of an antenna.  ``weights=None``: the search on
-    the antennas as they are."""
+    the antennas as they are.
+
+    ``method``: ``"direct"`` (``gat_acquire``: one sum per bin; the default) or ``"fft"`` (``gat_acquire_fft``: every lag of a block
+    from transforms of F > N points -- the same grid under the same contract, within the same 1e-5 of it, not bit-equal to the
+    direct search).  The FFT search costs the same whatever the code step, so with ``method="fft"`` and ``code_step_chips=None``
+    the grid is sample-spaced: s = 1 and J = one code period of samples.  Choose it for s = 1, for long codes (GPS L5) and for many
+    non-coherent blocks; the direct search wins on coarse grids (DESIGN.md 4.6 has the measured ratios).  Blocks of 2^18 samples
+    and more are refused."""
+    if method not in ("direct", "fft"):
+        raise ValueError("method must be 'direct' or 'fft'")
+    if code_step_chips is None:
+        if method != "fft":
+            raise ValueError("code_step_chips=None (sample spacing) needs method='fft'")
     ctx = ctx if ctx is not None else get_context(device)
     ctx.set_codes(system.codes)
     fs = float(sampling_frequency)
@@ -89,7 +101,7 @@ def acquire(system: GNSSSystem, signal, sampling_frequency: float, prns=range(32
     bstride = int(block_stride) if block_stride is not None else N
     if isinstance(signal, _lib.SignalDesc):
         N = int(signal.num_samples)
-    s = max(1, int(round(code_step_chips * fs / fc)))
+    s = 1 if code_step_chips is None else max(1, int(round(code_step_chips * fs / fc)))
     J = int(num_code_bins) if num_code_bins is not None else int(math.ceil(lc * fs / (fc * s)))
     if dopplers is None:
         step = float(doppler_step) if doppler_step is not None else fs / (2.0 * N)
@@ -118,10 +130,11 @@ def acquire(system: GNSSSystem, signal, sampling_frequency: float, prns=range(32
 
     power = torch.empty((P, D, J), dtype=torch.float32, device=ctx.device) if keep_power else None
     res = np.zeros(max(P, 1), dtype=_lib.ACQ_RESULT_DTYPE)
-    rc = ctx.lib.gat_acquire(ctx._h, C.byref(desc), int(num_blocks), prn_arr.ctypes.data_as(C.POINTER(C.c_int32)), P, fs,
-                             C.byref(cfg), C.c_void_p(power.data_ptr() if power is not None else None),
-                             C.c_void_p(res.ctypes.data))
-    ctx.check(rc, "gat_acquire")
+    name = "gat_acquire_fft" if method == "fft" else "gat_acquire"
+    rc = getattr(ctx.lib, name)(ctx._h, C.byref(desc), int(num_blocks), prn_arr.ctypes.data_as(C.POINTER(C.c_int32)), P, fs,
+                                C.byref(cfg), C.c_void_p(power.data_ptr() if power is not None else None),
+                                C.c_void_p(res.ctypes.data))
+    ctx.check(rc, name)
     out = []
     for p in range(P):
         r = res[p]
@@ -132,6 +145,39 @@ def acquire(system: GNSSSystem, signal, sampling_frequency: float, prns=range(32
             second_power=float(r["second_power"]), detected=int(r["detected"]), doppler_bin=int(r["doppler_bin"]),
             code_bin=int(r["code_bin"]), power_bins=power[p] if power is not None else None, dopplers=dop))
     return out
+
+
+def acquire_fft_plan(desc: _lib.SignalDesc, num_blocks: int, num_prns: int, sampling_frequency: float, config: _lib.AcqConfig, *,
+                     fft_log2: int = 0, doppler_batch: int = 0, unit_batch: int = 0, num_cus: int = 256, own_power: bool = False) -> dict:
+    """``gat_acquire_fft_plan``: what ``gat_acquire_fft`` would do with this call (transform length, lag segments, passes, batches,
+    unit groups, scratch bytes), without a device.  ``num_cus``: the device's compute units (``Context.device_info()``); the three
+    options as ``Context.set_option`` would set them.  Raises ``GatError`` with the refusal the call would get."""
+    plan = _lib.AcqFftPlan()
+    plan.struct_size = C.sizeof(_lib.AcqFftPlan)
+    rc = _lib.load().gat_acquire_fft_plan(C.byref(desc) if desc is not None else None, int(num_blocks), int(num_prns), float(sampling_frequency),
+                                          C.byref(config) if config is not None else None, int(fft_log2), int(doppler_batch), int(unit_batch),
+                                          int(num_cus), int(bool(own_power)), C.byref(plan))
+    if rc != 0:
+        raise _lib.GatError(rc, "gat_acquire_fft_plan")
+    return {n: int(getattr(plan, n)) for n, _ in plan._fields_ if n != "struct_size"}
+
+
+def acquire_fft_host(desc: _lib.SignalDesc, num_blocks: int, codes: np.ndarray, prns, sampling_frequency: float, config: _lib.AcqConfig,
+                     fft_log2: int, unit_groups: int = 1) -> np.ndarray:
+    """``gat_acquire_fft_host``: the FFT search's grid [P, D, J] on the host over a descriptor of HOST memory (``frontend.host_desc``),
+    bit for bit the device's for the same ``fft_log2`` and ``unit_groups``.  ``codes``: int8 [rows, Lc]; ``prns``: rows."""
+    tab = np.ascontiguousarray(codes, dtype=np.int8)
+    if tab.ndim != 2:
+        raise ValueError("codes must be [rows, code_length]")
+    prn_arr = np.ascontiguousarray(np.asarray(prns, dtype=np.int32).reshape(-1))
+    P = int(prn_arr.size)
+    power = np.zeros((max(P, 1), max(int(config.num_doppler_bins), 1), max(int(config.num_code_bins), 1)), dtype=np.float32)
+    rc = _lib.load().gat_acquire_fft_host(C.byref(desc), int(num_blocks), C.c_void_p(tab.ctypes.data), int(tab.shape[1]), int(tab.shape[1]),
+                                          prn_arr.ctypes.data_as(C.POINTER(C.c_int32)), P, float(sampling_frequency), C.byref(config),
+                                          int(fft_log2), int(unit_groups), C.c_void_p(power.ctypes.data))
+    if rc != 0:
+        raise _lib.GatError(rc, "gat_acquire_fft_host")
+    return power
 
 
 def acquisition_stats_host(power: np.ndarray, config: _lib.AcqConfig, sampling_frequency: float,

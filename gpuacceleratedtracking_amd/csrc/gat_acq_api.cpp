@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gat_acq.h"
+#include "gat_acq_check.h"
 #include "gat_acq_kernels.h"
 #include "gat_ctx.h"
 
@@ -14,27 +15,13 @@ using namespace gat;
 
 namespace {
 
-constexpr long long kMaxBins = 1ll << 26;            // num_prns * D * J
 constexpr size_t kMaxGroupScratch = (size_t)1 << 30; // bytes of the groups' slices
 
+// the configuration's refusals (gat_acq_check.h, shared with gat_acquire_fft), reported on the context
 int32_t check_config(gat_ctx *c, const gat_acq_config *cfg, int32_t P, int32_t D, int32_t J, double fs)
 {
-    if (!cfg) return fail(c, GAT_ERR_ARG, "null config");
-    if (cfg->struct_size < sizeof(gat_acq_config)) return fail(c, GAT_ERR_ARG, "config.struct_size too small");
-    if (cfg->reserved != 0) return fail(c, GAT_ERR_ARG, "config.reserved must be 0");
-    if (P < 1 || D < 1 || J < 1) return fail(c, GAT_ERR_ARG, "empty grid (PRNs, Doppler bins and code bins must be positive)");
-    if (D != cfg->num_doppler_bins || J != cfg->num_code_bins) return fail(c, GAT_ERR_ARG, "grid size differs from the config");
-    if (cfg->code_step_samples < 1) return fail(c, GAT_ERR_ARG, "code step must be at least one sample");
-    if (cfg->code_step_samples > kAcqMaxCodeStep) return fail(c, GAT_ERR_RANGE, "code step above 31 samples");
-    if ((long long)P * D * J > kMaxBins) return fail(c, GAT_ERR_RANGE, "grid above 2^26 bins");
-    if (!(fs > 0.0) || !std::isfinite(fs)) return fail(c, GAT_ERR_ARG, "sampling frequency must be positive");
-    if (!(cfg->code_freq_hz > 0.0) || !std::isfinite(cfg->code_freq_hz)) return fail(c, GAT_ERR_ARG, "code frequency must be positive");
-    if (!std::isfinite(cfg->if_hz) || !std::isfinite(cfg->doppler_first_hz) || !std::isfinite(cfg->doppler_step_hz) ||
-        !std::isfinite(cfg->min_peak_ratio) || cfg->min_peak_ratio < 0.0)
-        return fail(c, GAT_ERR_ARG, "bad frequency / threshold");
-    const double fmax = std::fabs(cfg->if_hz) + std::fabs(cfg->doppler_first_hz) + std::fabs(cfg->doppler_step_hz) * (double)D;
-    if (!(fmax / fs < 1.0e6)) return fail(c, GAT_ERR_RANGE, "carrier frequency out of range");
-    return GAT_OK;
+    const Refusal r = acq_check_config(cfg, P, D, J, fs);
+    return r.code == GAT_OK ? GAT_OK : fail(c, r.code, r.msg);
 }
 
 void stats_host(const float *power, int32_t P, int32_t D, int32_t J, const gat_acq_config &cfg, double fs, long long N,

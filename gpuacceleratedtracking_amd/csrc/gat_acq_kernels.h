@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "gat.h"
+#include "gat_acq_check.h" // kAcqMaxCodeStep
 
 namespace gat {
 
@@ -16,7 +17,6 @@ constexpr int kAcqCodePerLane = 4;  // code bins of one lane's register tile (la
 constexpr int kAcqDopTile = kAcqDopPerWave * (kAcqThreads / 64); // 32 Doppler bins per workgroup
 constexpr int kAcqCodeTile = kAcqCodePerLane * 64;               // 256 code bins per workgroup
 constexpr int kAcqChunk = 128;      // samples staged per step (a power of two dividing kAcqThreads)
-constexpr int kAcqMaxCodeStep = 31; // s: the replica window (kAcqChunk + s * 255 chip pairs) stays within 64 KB of LDS
 
 struct AcqArgs {
     const void *re, *im;

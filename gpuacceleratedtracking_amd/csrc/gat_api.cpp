@@ -241,6 +241,9 @@ constexpr OptionDesc kOptions[] = {
     {"mc_nct", 0, 4, [](gat_ctx &c, long long v) { c.mc_nct = v == 3 ? 2 : (int)v; }}, // split-bf16 kernel: 32-column channel tiles per workgroup to try first (0 = by rule; A/B runs)
     {"mc_i16_terms", 2, 3, GAT_OPT_INT(mc_i16_terms)},         // split-bf16 kernel, int16 samples: 2 = the exact two-term split (5 products per sample), 3 = the float path's three terms (8)
     {"dc_align", 0, 1, GAT_OPT_INT(align_head)},               // blocks walked from the 128-byte line their first sample lies in (1) or from the sample itself (0)
+    {"acq_fft_log2", 0, 18, GAT_OPT_INT(acq_fft_log2)},        // gat_acquire_fft: log2 of the transform length, 10 .. 18 (0: the plan's choice; 1 .. 9 and 2^v <= N are refused at the call)
+    {"acq_fft_doppler_batch", 0, 1 << 20, GAT_OPT_INT(acq_fft_dbatch)}, // gat_acquire_fft: Doppler bins transformed at a time (0: the plan's choice); changes no bit
+    {"acq_fft_unit_batch", 0, 1 << 20, GAT_OPT_INT(acq_fft_ubatch)},    // gat_acquire_fft: (block, antenna) units whose spectra are held at a time (0: the plan's choice); changes no bit
 };
 #undef GAT_OPT_INT
 

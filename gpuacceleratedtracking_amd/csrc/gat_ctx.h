@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "gat_acq_check.h" // code_span_ok: the host mirror of the kernels' code_span_bad
 #include "gat_internal.h"
 
 struct gat_ctx;
@@ -98,6 +99,7 @@ struct gat_ctx {
     int mc_mode = 1;                          // GAT_MC_* kernel selection (gat_set_matrix_core)
     int mc_nct = 0;                           // option mc_nct
     int mc_i16_terms = 2;                     // option mc_i16_terms
+    int acq_fft_log2 = 0, acq_fft_dbatch = 0, acq_fft_ubatch = 0; // options acq_fft_log2 / acq_fft_doppler_batch / acq_fft_unit_batch (0: the plan's choice)
     std::string err;
     gat_launch_info last{};
 };
@@ -123,13 +125,6 @@ inline int32_t hipfail(gat_ctx *c, hipError_t e, const char *where)
         hipError_t e_ = (call);                               \
         if (e_ != hipSuccess) return hipfail((c), e_, #call); \
     } while (0)
-
-// host mirror of the kernels' code_span_bad (gat_phase.h): what passes here is not poisoned there
-inline bool code_span_ok(double ratio, double tau, double reach, int Lc)
-{
-    const double span = std::fabs(tau) + std::fabs(ratio) * reach + 1.0;
-    return span < 1073741824.0 && (Lc <= 0 || span < 2097152.0 * (double)Lc) && ratio >= 0.0;
-}
 
 // Tracing ranges around the library's launch sequences (the reference wraps every launch of kernel_algorithm in
 // NVTX.@range, src/algorithms.jl:953 ...): roctxRangePush / Pop, resolved at the first use (gat_api.cpp).  RAII; a null

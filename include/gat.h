@@ -400,7 +400,9 @@ GAT_API int32_t gat_set_vector_tiling(gat_ctx *ctx, int32_t max_antenna_tiles, i
  * "dc_bpw_force", "dc_wgs_per_cu", "dc_one_wave", "dc_one_wave_min", "dc_ow_seg", "dc_depth", "dc_keep_l2", "dc_align",
  * "dc_aw2", "dc_quads", "dc_bits", "dc_seg" (round 5: the two-channel tile and its replica fill), "mc_i16_terms" (split-bf16
  * kernel, int16 samples: 2 = the exact two-term split, the default; 3 = the float path's three terms: bit-comparisons),
- * "mc_nct" (32-column tiles per workgroup of the split-bf16 kernel to try first; 0 = by rule).
+ * "mc_nct" (32-column tiles per workgroup of the split-bf16 kernel to try first; 0 = by rule), "acq_fft_log2",
+ * "acq_fft_doppler_batch", "acq_fft_unit_batch" (gat_acquire_fft below: the transform length, which moves a bin by rounding, and
+ * the batches, which change no bit; 0 = the plan's choice).
  * GAT_ERR_ARG: unknown name; GAT_ERR_RANGE: value outside the option's range. */
 GAT_API int32_t gat_set_option(gat_ctx *ctx, const char *name, int64_t value);
 
@@ -604,6 +606,56 @@ GAT_API int32_t gat_acquire(gat_ctx *ctx, const gat_signal_desc *signal, int32_t
 GAT_API int32_t gat_acq_stats_host(const float *power_host, int32_t num_prns, int32_t num_doppler_bins, int32_t num_code_bins,
                                    const gat_acq_config *config, double sampling_freq_hz, int64_t num_samples,
                                    gat_acq_result *results_host);
+
+/* ---- FFT acquisition: every code phase of a block by fast correlation ------------------------------------------------------
+ * The same grid P[p,i,j] under the same contract, arguments, results, synchronisation and error codes as gat_acquire, computed by
+ * transforms instead of one sum per bin.  The replica is a plain (non-circular) window of the code, so R is a LINEAR correlation
+ * and zero padding gives it exactly: with F = 2^L > N, w the wiped samples padded with zeros to F, c_g the F chips from sample
+ * first_shift + g * Jseg on, W = FFT(w) and C_g = FFT(c_g),
+ *   R[l] = IFFT(C_g[q] * W[(F - q) mod F])[l]   for every lag 0 <= l < Jseg = F - N + 1,
+ * and the lag axis first_shift .. first_shift + s (J - 1) is covered by G = ceil((s (J - 1) + 1) / Jseg) such segments; with s > 1
+ * the grid keeps every s-th lag.  The cost is G transforms of F points per (PRN, Doppler bin, block, antenna) whatever s is, so
+ * the method pays at sample spacing (s = 1) and for long codes, and loses to gat_acquire on coarse grids (large s) -- DESIGN.md
+ * 4.6 has the measured ratios.  The arithmetic is one fixed sequence of float32 operations (csrc/gat_acq_fft.h) shared with
+ * gat_acquire_fft_host: the device's grid equals the twin's bit for bit, for the same transform length and unit-group count.
+ * It is deterministic (no float atomics) and within the same 1e-5 of the FP64 contract as gat_acquire, not bit-equal to it.
+ * Refusals beyond gat_acquire's: N >= 2^18 samples (the largest transform), a forced transform length 2^v <= N (option
+ * acq_fft_log2), and a search whose spectra do not fit 1 GiB of scratch at the smallest batches: all GAT_ERR_RANGE.
+ * Options (gat_set_option): acq_fft_log2 (0 = the plan's choice: the F that minimises G F log2 F; else 10 .. 18),
+ * acq_fft_doppler_batch and acq_fft_unit_batch (0 = the plan's choice; how many Doppler bins / (block, antenna) units are
+ * transformed at a time: scratch and launch count, never the bits). */
+GAT_API int32_t gat_acquire_fft(gat_ctx *ctx, const gat_signal_desc *signal, int32_t num_blocks, const int32_t *prns_host,
+                                int32_t num_prns, double sampling_freq_hz, const gat_acq_config *config, float *power_dev,
+                                gat_acq_result *results_host);
+
+/* What gat_acquire_fft would do with a call, without a device.  unit_groups: the (block, antenna) units are dealt to this many
+ * groups, each summed in unit order and the groups then in group order, where (PRN, Doppler, segment) alone gives fewer than two
+ * workgroups per compute unit: the one plan parameter besides fft_log2 that enters the bits. */
+typedef struct gat_acq_fft_plan {
+    uint32_t struct_size;    /* sizeof(gat_acq_fft_plan), set by the caller                                       */
+    int32_t fft_log2;        /* L: the transform has F = 2^L points                                               */
+    int32_t num_segments;    /* G                                                                                 */
+    int32_t segment_lags;    /* Jseg = F - N + 1                                                                  */
+    int32_t passes;          /* 1: the transform stays in one workgroup (F <= 4096); 2: two passes through memory  */
+    int32_t doppler_batch;   /* Doppler bins transformed at a time                                                */
+    int32_t unit_batch;      /* (block, antenna) units whose spectra are held at a time                            */
+    int32_t unit_groups;     /* Gu                                                                                */
+    int64_t scratch_bytes;   /* of the context's scratch buffer                                                   */
+} gat_acq_fft_plan;
+/* config->code_length must be set (there is no bound table to take it from); fft_log2, doppler_batch, unit_batch: the options'
+ * values (0 = the plan's choice); num_cus: the device's compute units (gat_device_info); own_power: 1 when the call would pass
+ * power_dev = NULL.  Returns the refusal gat_acquire_fft would return for the same call, or GAT_OK with *plan filled. */
+GAT_API int32_t gat_acquire_fft_plan(const gat_signal_desc *signal, int32_t num_blocks, int32_t num_prns, double sampling_freq_hz,
+                                     const gat_acq_config *config, int32_t fft_log2, int32_t doppler_batch, int32_t unit_batch,
+                                     int32_t num_cus, int32_t own_power, gat_acq_fft_plan *plan);
+
+/* The twin: the same grid on the HOST, bit for bit what gat_acquire_fft writes when fft_log2 and unit_groups are the device
+ * plan's (gat_acquire_fft_plan).  signal: a descriptor of host memory; codes_host: [rows x code_row_stride] chips, prns_host: rows;
+ * fft_log2 10 .. 18 with 2^fft_log2 > N, 1 <= unit_groups <= num_blocks * num_ants; power_host: [num_prns x D x J].  Plain loops:
+ * meant for small shapes. */
+GAT_API int32_t gat_acquire_fft_host(const gat_signal_desc *signal, int32_t num_blocks, const int8_t *codes_host, int32_t code_length,
+                                     int32_t code_row_stride, const int32_t *prns_host, int32_t num_prns, double sampling_freq_hz,
+                                     const gat_acq_config *config, int32_t fft_log2, int32_t unit_groups, float *power_host);
 
 /* ---- antenna-array processing: spatial covariance, beamformer weights, beamformed samples, accumulators and loop ----
  * The correlators return accumulators per antenna; what an array receiver does with its antennas happens here.

@@ -136,6 +136,18 @@ struct AcqConfig
     code_length::Int32
     reserved::Int32
 end
+# struct gat_acq_fft_plan (40 bytes): what gat_acquire_fft would do with a call (include/gat.h gat_acquire_fft_plan)
+struct AcqFftPlan
+    struct_size::UInt32
+    fft_log2::Int32
+    num_segments::Int32
+    segment_lags::Int32
+    passes::Int32
+    doppler_batch::Int32
+    unit_batch::Int32
+    unit_groups::Int32
+    scratch_bytes::Int64
+end
 struct AcqResult
     prn::Int32
     detected::Int32
@@ -702,6 +714,43 @@ function acquire!(ctx::Context, desc::SignalDesc, num_blocks::Integer, prns::Abs
                      ctx.handle, Ref(desc), Int32(num_blocks), cols, Int32(length(cols)), sampling_frequency_hz, Ref(cfg),
                      power_dev, res))
     res
+end
+# the same search by fast correlation (include/gat.h gat_acquire_fft): the same arguments, results and errors as acquire!; zero-padded
+# transforms of F > N points give every lag of a block, so it is the method for sample-spaced grids (code_step_samples = 1) and long codes
+function acquire_fft!(ctx::Context, desc::SignalDesc, num_blocks::Integer, prns::AbstractVector{<:Integer}, sampling_frequency_hz::Float64,
+                      cfg::AcqConfig, power_dev::Ptr{Cvoid} = C_NULL)
+    cols = Int32[p - 1 for p in prns]
+    res = Vector{AcqResult}(undef, length(cols))
+    check(ctx, ccall((:gat_acquire_fft, libgat), Int32,
+                     (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Ptr{Int32}, Int32, Float64, Ref{AcqConfig}, Ptr{Cvoid}, Ptr{AcqResult}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), cols, Int32(length(cols)), sampling_frequency_hz, Ref(cfg),
+                     power_dev, res))
+    res
+end
+# what acquire_fft! would do with the call, without a device: cfg.code_length must be set; fft_log2, doppler_batch, unit_batch as the
+# options acq_fft_log2 / acq_fft_doppler_batch / acq_fft_unit_batch would set them (0: the plan's choice); num_cus from device_info
+function acquire_fft_plan(desc::SignalDesc, num_blocks::Integer, num_prns::Integer, sampling_frequency_hz::Float64, cfg::AcqConfig;
+                          fft_log2::Integer = 0, doppler_batch::Integer = 0, unit_batch::Integer = 0, num_cus::Integer = 256, own_power::Bool = false)
+    plan = Ref(AcqFftPlan(UInt32(sizeof(AcqFftPlan)), 0, 0, 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_acquire_fft_plan, libgat), Int32,
+               (Ref{SignalDesc}, Int32, Int32, Float64, Ref{AcqConfig}, Int32, Int32, Int32, Int32, Int32, Ref{AcqFftPlan}),
+               Ref(desc), Int32(num_blocks), Int32(num_prns), sampling_frequency_hz, Ref(cfg), Int32(fft_log2), Int32(doppler_batch),
+               Int32(unit_batch), Int32(num_cus), Int32(own_power), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_acquire_fft_plan"))
+    plan[]
+end
+# the twin on the host: desc over host memory, codes[Lc, rows] (Julia's view of the library's [rows x Lc]), prns 1-based rows; the grid
+# power[J, D, P], bit for bit the device's for the same fft_log2 and unit_groups
+function acquire_fft_host(desc::SignalDesc, num_blocks::Integer, codes::Matrix{Int8}, prns::AbstractVector{<:Integer}, sampling_frequency_hz::Float64,
+                          cfg::AcqConfig, fft_log2::Integer, unit_groups::Integer = 1)
+    rows = Int32[p - 1 for p in prns]
+    power = Array{Float32,3}(undef, Int(cfg.num_code_bins), Int(cfg.num_doppler_bins), length(rows))
+    rc = ccall((:gat_acquire_fft_host, libgat), Int32,
+               (Ref{SignalDesc}, Int32, Ptr{Int8}, Int32, Int32, Ptr{Int32}, Int32, Float64, Ref{AcqConfig}, Int32, Int32, Ptr{Cfloat}),
+               Ref(desc), Int32(num_blocks), codes, Int32(size(codes, 1)), Int32(size(codes, 1)), rows, Int32(length(rows)), sampling_frequency_hz,
+               Ref(cfg), Int32(fft_log2), Int32(unit_groups), power)
+    rc == GAT_OK || throw(GatError(rc, "gat_acquire_fft_host"))
+    power
 end
 # the same statistics over a host grid power[J, D, P] (Julia's column-major view of the library's [P x D x J])
 function acq_stats_host(power::Array{Float32,3}, cfg::AcqConfig, sampling_frequency_hz::Float64, num_samples::Integer)
