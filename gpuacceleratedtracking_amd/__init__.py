@@ -28,6 +28,8 @@ from .gen_signal import StructSignal, gen_blank_signal, gen_signal, gen_signal_s
 from .loop import ResidentTrackingLoop, TrackingLoop  # noqa: F401
 from .sharding import DeviceGroup, ShardPlan, gather_outputs, shard_channels, shard_params  # noqa: F401
 from .spectrum import (auto_notch, find_tones, sample_spectrum, sample_spectrum_host, spectrum_stream)  # noqa: F401
+from .spacetime import (spacetime_covariance, spacetime_delay, spacetime_filter, spacetime_filter_host, spacetime_steering,  # noqa: F401
+                        spacetime_stream, spacetime_weights)
 from .signals import GNSSDICT, GPSL1, GPSL5, generate_codes, get_code_frequency, get_code_length  # noqa: F401
 from .tracking import (StreamCorrelator, downconvert_and_accumulate_strided, downconvert_and_correlate,  # noqa: F401
                        gen_code_replica, gen_code_replica_nsat, reduce_cplx_multi)

@@ -32,6 +32,8 @@ GAT_COND_BLANK_ALL_ANTS = 1
 GAT_MAX_FIR_TAPS, GAT_MAX_FIR_DECIMATION = 256, 64
 # sample spectrum (gat_sample_spectrum limits)
 GAT_MIN_SPECTRUM_BINS, GAT_MAX_SPECTRUM_BINS, GAT_MAX_SPECTRUM_SEGMENTS = 64, 4096, 4096
+# space-time adaptive processing (taps per antenna; num_ants * num_taps <= GAT_MAX_ARRAY_ANTS)
+GAT_MAX_ST_TAPS = 16
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -61,6 +63,8 @@ EXPORTS = [
     "gat_filter_samples", "gat_filter_samples_host",
     # sample spectrum: the summed periodogram of the raw samples per block and antenna
     "gat_sample_spectrum", "gat_sample_spectrum_host",
+    # space-time adaptive processing: the tapped covariance and the space-time sample filter
+    "gat_spacetime_covariance", "gat_spacetime_filter", "gat_spacetime_filter_host",
 ]
 
 
@@ -293,6 +297,9 @@ def load(build_if_missing: bool = True):
         "gat_filter_samples_host": (i32, [sp, i32, vp, vp, C.POINTER(FirConfig), sp]),
         "gat_sample_spectrum": (i32, [vp, sp, i32, vp, C.POINTER(SpectrumConfig), vp]),
         "gat_sample_spectrum_host": (i32, [sp, i32, vp, C.POINTER(SpectrumConfig), vp]),
+        "gat_spacetime_covariance": (i32, [vp, sp, i32, i32, i32, vp, vp]),
+        "gat_spacetime_filter": (i32, [vp, sp, i32, vp, vp, i32, i32, sp]),
+        "gat_spacetime_filter_host": (i32, [sp, i32, vp, vp, i32, i32, sp]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

@@ -18,7 +18,7 @@ SOURCES = ["gat_dc_f0.hip", "gat_dc_f1.hip", "gat_dc_f2.hip", "gat_dc_f3.hip", "
            "gat_kernels.hip", "gat_mfma.hip", "gat_mfma_bf16.hip", "gat_api.cpp", "gat_planner.cpp", "gat_group.cpp",
            "gat_resident_api.cpp", "gat_codes.cpp", "gat_acq.hip", "gat_acq_api.cpp", "gat_array.hip", "gat_array_api.cpp",
            "gat_beam.hip", "gat_beam_api.cpp", "gat_cond.hip", "gat_cond_api.cpp", "gat_fir.hip", "gat_fir_api.cpp",
-           "gat_spec.hip", "gat_spec_api.cpp", "gat_acq_fft.hip", "gat_acq_fft_api.cpp"]
+           "gat_spec.hip", "gat_spec_api.cpp", "gat_acq_fft.hip", "gat_acq_fft_api.cpp", "gat_st.hip", "gat_st_api.cpp"]
 # gat_version.cpp is not in SOURCES: it is compiled at every link with the build's identity (git commit, flags)
 HEADERS = [os.path.join(CSRC, "gat_internal.h"), os.path.join(CSRC, "gat_sig_plan.h"), os.path.join(CSRC, "gat_phase.h"), os.path.join(CSRC, "gat_dc.h"),
            os.path.join(CSRC, "gat_dc_body.inc"), os.path.join(CSRC, "gat_resident.h"), os.path.join(CSRC, "gat_ctx.h"),
@@ -30,6 +30,7 @@ HEADERS = [os.path.join(CSRC, "gat_internal.h"), os.path.join(CSRC, "gat_sig_pla
            os.path.join(CSRC, "gat_sample_load.h"), os.path.join(CSRC, "gat_spec.h"), os.path.join(CSRC, "gat_spec_plan.h"),
            os.path.join(CSRC, "gat_spec_kernels.h"), os.path.join(CSRC, "gat_acq_check.h"), os.path.join(CSRC, "gat_acq_fft.h"),
            os.path.join(CSRC, "gat_acq_fft_plan.h"), os.path.join(CSRC, "gat_acq_fft_kernels.h"),
+           os.path.join(CSRC, "gat_st.h"), os.path.join(CSRC, "gat_st_plan.h"), os.path.join(CSRC, "gat_st_kernels.h"),
            os.path.join(ROOT, "include", "gat.h")]
 
 
@@ -135,7 +136,8 @@ def build_libgat(force: bool = False, verbose: bool = False, extra_flags: tuple[
             # beam_stream_kernel<planar, 4, 4> takes 156 VGPRs instead of 124 and <int8, 8, 4> 256 with 8 spilled instead of 246)
             # (the sample spectrum too: the vectoriser packs its butterflies, 12 - 50 more VGPRs an instance and one wave a SIMD at
             # F = 4096; without it the same run is 4 - 20 % faster on every shape -- DESIGN.md 4.10)
-            per_file = ("-fno-slp-vectorize",) if vector_tu or src in ("gat_beam.hip", "gat_spec.hip") else ()
+            # (the space-time filter is the beamformer's sum over a longer vector: the same scalar FMA chains)
+            per_file = ("-fno-slp-vectorize",) if vector_tu or src in ("gat_beam.hip", "gat_spec.hip", "gat_st.hip") else ()
             jobs.append([hipcc_path(), *_flags(tuple(extra_here) + per_file), "-c", sp, "-o", obj])
 
     def run(cmd):
@@ -161,7 +163,7 @@ def build_libgat(force: bool = False, verbose: bool = False, extra_flags: tuple[
             hipcc_v = "unknown"
         with open(BUILD_INFO, "w") as f:
             json.dump({"kernel_sources_git": ident, "repo_head_git": repo_head(), "flags": flag_str, "hipcc": hipcc_v,
-                       "recipe": " ".join(_flags()[:-2]), "no_slp_vectorize": "gat_dc_f*.hip gat_resident_f*.hip gat_beam.hip gat_spec.hip", "built_utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime())}, f)
+                       "recipe": " ".join(_flags()[:-2]), "no_slp_vectorize": "gat_dc_f*.hip gat_resident_f*.hip gat_beam.hip gat_spec.hip gat_st.hip", "built_utc": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime())}, f)
     return out
 
 

@@ -880,6 +880,66 @@ GAT_API int32_t gat_filter_samples(gat_ctx *ctx, const gat_signal_desc *signal, 
 GAT_API int32_t gat_filter_samples_host(const gat_signal_desc *signal, int32_t num_blocks, const float *taps_re_host,
                                         const float *taps_im_host, const gat_fir_config *cfg, const gat_signal_desc *out);
 
+/* ---- space-time adaptive processing: the tapped covariance and the space-time sample filter --------------------------------
+ * An M-antenna array nulls M - 1 interferers.  A tap delay line of T samples behind every antenna, all M*T coefficients
+ * solved at once, has Q - 1 degrees of freedom, Q = M*T: narrow-band jammers are taken out in frequency as well as in space.
+ * The space-time snapshot of block b at sample n, T - 1 <= n < N, is the Q-vector
+ *     z[q] = x[n - t, m, b],  q = t*M + m          tap 0 is the newest sample; the antenna index runs fastest
+ * and the solver is gat_array_weights with num_ants = Q, unchanged: GAT_BF_POWER_INVERSION constrains (tap 0, antenna 0);
+ * GAT_BF_MVDR with a_st[t*M + m] = a[m] * (t == ref_tap) is distortionless for direction a at tap ref_tap (a = e_m: power
+ * inversion referenced to (ref_tap, m)).  The filtered stream is then the input ADVANCED by d = T - 1 - ref_tap samples:
+ * output n' shows the wanted signal of input sample n' + d, so a code phase found on y belongs to sample d of x. */
+#define GAT_MAX_ST_TAPS 16 /* taps per antenna; num_ants * num_taps <= GAT_MAX_ARRAY_ANTS */
+
+/* The space-time covariance, estimates grouped as in gat_spatial_covariance (E = ceil(num_blocks / blocks_per_estimate)):
+ *   R_e[q][q'] = sum_{b in e} sum_{n = T-1}^{N-1} z_q[n] * conj(z_q'[n])           cov_re/cov_im: dev float [E][Q][Q] planar
+ * The covariance method: every entry is summed over the same N - T + 1 snapshots, so R is positive semi-definite by
+ * construction (it is not assembled from lag sums over differing ranges), and no snapshot reads outside its block.
+ * The contract is gat_spatial_covariance's: every layout, any N >= T, any base alignment and strides, chan_stride 0; only
+ * the upper triangle is computed, the mirror is its exact conjugate and the diagonal's imaginary part +0; two-level
+ * float32 sums, per-workgroup slices added in a fixed order by the same finishing kernel, no float atomics: the same bits
+ * every call; integer samples whose sums stay below 2^24 come back exact.  num_taps == 1 IS gat_spatial_covariance (the
+ * call is forwarded: the same bits).  Otherwise a chunk of samples and the T - 1 samples in front of it are staged in LDS
+ * once and the Q virtual antennas are shifted views of the M staged rows.  Refusals: gat_spatial_covariance's, and
+ * GAT_ERR_RANGE for num_taps outside 1 .. GAT_MAX_ST_TAPS or num_ants * num_taps above GAT_MAX_ARRAY_ANTS, GAT_ERR_ARG
+ * for N < num_taps. */
+GAT_API int32_t gat_spacetime_covariance(gat_ctx *ctx, const gat_signal_desc *signal, int32_t num_blocks,
+                                         int32_t blocks_per_estimate, int32_t num_taps, float *cov_re_dev, float *cov_im_dev);
+
+/* The space-time filter: y[n', j, b] = sum_{q < Q} conj(w[j][q]) * z_q[n' + T - 1], 0 <= n' < N - T + 1, 0 <= j < num_beams.
+ * signal: any layout, any base alignment and strides, overlapping blocks included, chan_stride 0, N >= T.
+ * w: dev double [num_beams][Q] planar, exactly what gat_array_weights writes when called with num_ants = Q.
+ * out: describes device memory the call WRITES: GAT_LAYOUT_PLANAR or GAT_LAYOUT_INTERLEAVED float32, num_ants ==
+ *      num_beams, num_samples == N - T + 1, its own strides; nothing outside the described elements is written.  Every
+ *      operator that takes a signal takes it unchanged; num_ants = 1 with chan_stride = ant_stride reads it as one signal
+ *      per channel, as gat_beamform_samples documents.
+ * Arithmetic: gat_beamform_samples' rule with the snapshot in place of the antenna vector: the weights are narrowed to
+ * float32 once; one float32 sum from +0 in q order (all antennas of tap 0, then tap 1, ...), per element yr = fma(wr, xr,
+ * yr), yr = fma(wi, xi, yr), yi = fma(wr, xi, yi), yi = fma(-wi, xr, yi):
+ *     |y - y64| <= (4Q + 4) * 2^-24 * sum_q |w_q| |z_q|  per sample.
+ * Integer samples convert exactly; NaN weights give NaN samples and no error.  The bits depend neither on the kernel nor
+ * on the work split, the host twin gives the same ones, and num_taps == 1 IS gat_beamform_samples: after this call's own
+ * refusals it is forwarded there (the same bits, kernels and launch info).
+ * There is no state between calls: a continuous stream is overlapping blocks by descriptor, as for gat_filter_samples
+ * (input num_samples = Qout + T - 1 and block_stride = Qout, output block_stride = Qout); every partition gives the same bits.
+ * With more than one tap, every block of every antenna and of every beam on a 16-byte boundary and M <= 16, a workgroup stages a tile of
+ * samples and its T - 1 sample halo of all antennas through LDS with 16-byte loads and a lane keeps the sums of up to 4
+ * beams and 4 outputs in registers (a further pass per 4 more beams); everything else runs one output per lane with scalar
+ * loads (8 beams a pass).  gat_last_launch_info afterwards describes this call as for the beams: vec = the samples of a
+ * 16-byte load (tiled) or 1, workgroups, threads, splits (chunks of a block's outputs), ant_tile = M.  Enqueues on the
+ * context's stream and does not synchronise.  Refusals, all before any launch: GAT_ERR_ARG for null pointers, num_blocks or
+ * num_beams < 1, bad sizes or strides, N < T, out->num_ants != num_beams, out->num_samples != N - T + 1, a planar side
+ * without im or an interleaved one with im, and an output whose byte extent overlaps the input's; GAT_ERR_RANGE for
+ * num_taps outside 1 .. GAT_MAX_ST_TAPS, M * num_taps or num_beams above 64; GAT_ERR_UNSUPPORTED for an integer output
+ * layout or chan_stride != 0 on either side. */
+GAT_API int32_t gat_spacetime_filter(gat_ctx *ctx, const gat_signal_desc *signal, int32_t num_blocks, const double *w_re_dev,
+                                     const double *w_im_dev, int32_t num_taps, int32_t num_beams, const gat_signal_desc *out);
+/* The same rule in a plain loop on the HOST (csrc/gat_st.h, shared with the device): every pointer is host memory; needs
+ * no context and no device.  The bit-exact reference of the device call, with the same refusals. */
+GAT_API int32_t gat_spacetime_filter_host(const gat_signal_desc *signal, int32_t num_blocks, const double *w_re_host,
+                                          const double *w_im_host, int32_t num_taps, int32_t num_beams,
+                                          const gat_signal_desc *out);
+
 /* ---- sample spectrum: the summed periodogram (Welch) of the raw samples, per block and antenna ----------------------------
  * How a receiver looks at the band it works in: where a tone sits before notch_taps can remove it, whether a level is
  * noise or a jammer.  F = num_bins (a power of two, 64 .. 4096), H = hop (1 .. F), w a real float32 window of F values,

@@ -912,6 +912,36 @@ function filter_samples_host!(desc::SignalDesc, num_blocks::Integer, taps_re::Ve
     rc == GAT_OK || error("gat_filter_samples_host: status $rc")
     out
 end
+# ---- space-time adaptive processing: the tapped covariance and the space-time sample filter (include/gat.h) ---------------------
+#      The snapshot at sample n is z[t * M + m] = x[n - t, m] (tap 0 the newest sample), Q = M * num_taps elements; the weights
+#      come from array_weights! with num_ants = Q.  Weights referenced to tap r advance the stream by num_taps - 1 - r samples.
+const GAT_MAX_ST_TAPS = 16
+spacetime_delay(num_taps::Integer, ref_tap::Integer) = num_taps - 1 - ref_tap
+# cov_re / cov_im: device Float32 [Q x Q x E]; every entry over the same N - num_taps + 1 snapshots of a block
+function spacetime_covariance!(ctx::Context, desc::SignalDesc, num_blocks::Integer, blocks_per_estimate::Integer, num_taps::Integer,
+                               cov_re::Ptr{Cfloat}, cov_im::Ptr{Cfloat})
+    check(ctx, ccall((:gat_spacetime_covariance, libgat), Int32, (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Int32, Int32, Ptr{Cfloat}, Ptr{Cfloat}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), Int32(blocks_per_estimate), Int32(num_taps), cov_re, cov_im))
+end
+# y[n', j, b] = sum_q conj(w[q, j]) z_q[n' + T - 1]: `out` describes the device memory the call writes (GAT_LAYOUT_PLANAR or
+# GAT_LAYOUT_INTERLEAVED, num_ants = num_beams, num_samples = desc.num_samples - num_taps + 1) and is afterwards a signal for
+# acquire!, spatial_covariance! and the correlators.  w [Q x num_beams] Float64 planes on the device.
+function spacetime_filter!(ctx::Context, desc::SignalDesc, num_blocks::Integer, w_re::Ptr{Float64}, w_im::Ptr{Float64}, num_taps::Integer,
+                           num_beams::Integer, out::SignalDesc)
+    check(ctx, ccall((:gat_spacetime_filter, libgat), Int32,
+                     (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ref{SignalDesc}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), w_re, w_im, Int32(num_taps), Int32(num_beams), Ref(out)))
+    out
+end
+# the same rule on host memory (both descriptors and the weights are host arrays): the bit-exact reference of the device call
+function spacetime_filter_host!(desc::SignalDesc, num_blocks::Integer, w_re::Matrix{Float64}, w_im::Matrix{Float64}, num_taps::Integer,
+                                out::SignalDesc)
+    rc = ccall((:gat_spacetime_filter_host, libgat), Int32,
+               (Ref{SignalDesc}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ref{SignalDesc}),
+               Ref(desc), Int32(num_blocks), w_re, w_im, Int32(num_taps), Int32(size(w_re, 2)), Ref(out))
+    rc == GAT_OK || error("gat_spacetime_filter_host: status $rc")
+    out
+end
 # ---- sample spectrum: the summed periodogram of the raw samples per block and antenna (include/gat.h) ---------------------------
 const GAT_MIN_SPECTRUM_BINS = 64
 const GAT_MAX_SPECTRUM_BINS = 4096
