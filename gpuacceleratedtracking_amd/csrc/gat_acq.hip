@@ -28,30 +28,13 @@
 #include "gat_acq.h"
 #include "gat_acq_kernels.h"
 #include "gat_phase.h"
+#include "gat_sample_load.h"
 
 namespace gat {
 
 namespace {
 
 constexpr int kAcqChunksPerSum = 8; // chunks the register tile sums before it is added to the block's sum
-
-template <int FMT>
-__device__ __forceinline__ void acq_load(const void *re, const void *im, size_t e, float &xr, float &xi)
-{
-    if constexpr (FMT == GAT_LAYOUT_PLANAR) {
-        xr = static_cast<const float *>(re)[e];
-        xi = static_cast<const float *>(im)[e];
-    } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED) {
-        xr = static_cast<const float *>(re)[2 * e];
-        xi = static_cast<const float *>(re)[2 * e + 1];
-    } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED_I16) {
-        xr = (float)static_cast<const short *>(re)[2 * e];
-        xi = (float)static_cast<const short *>(re)[2 * e + 1];
-    } else {
-        xr = (float)static_cast<const signed char *>(re)[2 * e];
-        xi = (float)static_cast<const signed char *>(re)[2 * e + 1];
-    }
-}
 
 template <int FMT>
 __global__ void __launch_bounds__(kAcqThreads, 2) acq_grid_kernel(const AcqArgs a)
@@ -101,7 +84,7 @@ __global__ void __launch_bounds__(kAcqThreads, 2) acq_grid_kernel(const AcqArgs 
                 const int n = tid & (kAcqChunk - 1), dh = tid / kAcqChunk;
                 const long long nn = n0 + n;
                 float xr = 0.f, xi = 0.f;
-                if (nn < a.N) acq_load<FMT>(a.re, a.im, base + (size_t)nn, xr, xi);
+                if (nn < a.N) load_sample<FMT>(a.re, a.im, base + (size_t)nn, xr, xi);
                 float *w = reinterpret_cast<float *>(s_w);
 #pragma unroll 4
                 for (int d = dh; d < kAcqDopTile; d += kAcqThreads / kAcqChunk) {
@@ -251,20 +234,7 @@ hipError_t launch_acq_grid(const AcqArgs &a, int fmt, hipStream_t st)
     const dim3 grid((unsigned)((a.J + kAcqCodeTile - 1) / kAcqCodeTile), (unsigned)((a.D + kAcqDopTile - 1) / kAcqDopTile),
                     (unsigned)(a.P * a.G));
     const size_t lds = acq_grid_lds_bytes(a.s);
-    switch (fmt) {
-    case GAT_LAYOUT_PLANAR:
-        hipLaunchKernelGGL(acq_grid_kernel<GAT_LAYOUT_PLANAR>, grid, dim3(kAcqThreads), lds, st, a);
-        break;
-    case GAT_LAYOUT_INTERLEAVED:
-        hipLaunchKernelGGL(acq_grid_kernel<GAT_LAYOUT_INTERLEAVED>, grid, dim3(kAcqThreads), lds, st, a);
-        break;
-    case GAT_LAYOUT_INTERLEAVED_I16:
-        hipLaunchKernelGGL(acq_grid_kernel<GAT_LAYOUT_INTERLEAVED_I16>, grid, dim3(kAcqThreads), lds, st, a);
-        break;
-    default:
-        hipLaunchKernelGGL(acq_grid_kernel<GAT_LAYOUT_INTERLEAVED_I8>, grid, dim3(kAcqThreads), lds, st, a);
-        break;
-    }
+    dispatch_layout(fmt, [&](auto F) { hipLaunchKernelGGL(acq_grid_kernel<F>, grid, dim3(kAcqThreads), lds, st, a); });
     return hipGetLastError();
 }
 

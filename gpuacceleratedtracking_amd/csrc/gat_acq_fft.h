@@ -101,7 +101,7 @@ inline void acq_fft_host_run(const gat_signal_desc *sig, const int8_t *codes, in
                 float wr = 0.0f, wi = 0.0f;
                 if (n < N) {
                     float xr, xi;
-                    fir_host_load(sig, base + (size_t)n, &xr, &xi);
+                    host_load_sample(sig, base + (size_t)n, &xr, &xi);
                     acq_fft_wipe(xr, xi, n, step, wr, wi);
                 }
                 const unsigned q = spec_bitrev((unsigned)n, L);

@@ -145,7 +145,7 @@ struct Transform {
             float wr = 0.0f, wi = 0.0f;
             if ((long long)n < a.N) {
                 float xr, xi;
-                fir_load_scalar<FMT>(a.re, a.im, base + (size_t)n, xr, xi);
+                load_sample<FMT>(a.re, a.im, base + (size_t)n, xr, xi);
                 acq_fft_wipe(xr, xi, (long long)n, step, wr, wi);
             }
             return make_float2(wr, wi);
@@ -282,13 +282,8 @@ hipError_t launch_acq_fft_replica(const AcqFftArgs &a, hipStream_t st)
 hipError_t launch_acq_fft_signal(const AcqFftArgs &a, int fmt, hipStream_t st)
 {
     const long long transforms = (long long)a.un * a.dn;
-    switch (fmt) {
-    case GAT_LAYOUT_PLANAR: return launch<kSignal, GAT_LAYOUT_PLANAR>(a, transforms, st);
-    case GAT_LAYOUT_INTERLEAVED: return launch<kSignal, GAT_LAYOUT_INTERLEAVED>(a, transforms, st);
-    case GAT_LAYOUT_INTERLEAVED_I16: return launch<kSignal, GAT_LAYOUT_INTERLEAVED_I16>(a, transforms, st);
-    case GAT_LAYOUT_INTERLEAVED_I8: return launch<kSignal, GAT_LAYOUT_INTERLEAVED_I8>(a, transforms, st);
-    default: return hipErrorInvalidValue;
-    }
+    if (fmt < GAT_LAYOUT_PLANAR || fmt > GAT_LAYOUT_INTERLEAVED_I8) return hipErrorInvalidValue;
+    return dispatch_layout(fmt, [&](auto F) { return launch<kSignal, F>(a, transforms, st); });
 }
 
 hipError_t launch_acq_fft_correlate(const AcqFftArgs &a, hipStream_t st)

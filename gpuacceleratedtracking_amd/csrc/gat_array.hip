@@ -28,69 +28,11 @@
 #include "gat_array.h"
 #include "gat_array_kernels.h"
 #include "gat_loop.h"
+#include "gat_sample_load.h"
 
 namespace gat {
 
 namespace {
-
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-
-// ---- sample access ----------------------------------------------------------------------------------------------------------
-template <int FMT>
-__device__ __forceinline__ void cov_load_scalar(const void *re, const void *im, size_t e, float &xr, float &xi)
-{
-    if constexpr (FMT == GAT_LAYOUT_PLANAR) {
-        xr = static_cast<const float *>(re)[e];
-        xi = static_cast<const float *>(im)[e];
-    } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED) {
-        xr = static_cast<const float *>(re)[2 * e];
-        xi = static_cast<const float *>(re)[2 * e + 1];
-    } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED_I16) {
-        xr = (float)static_cast<const short *>(re)[2 * e];
-        xi = (float)static_cast<const short *>(re)[2 * e + 1];
-    } else {
-        xr = (float)static_cast<const signed char *>(re)[2 * e];
-        xi = (float)static_cast<const signed char *>(re)[2 * e + 1];
-    }
-}
-
-template <int FMT>
-struct CovVec {
-    static constexpr int VS = FMT == GAT_LAYOUT_PLANAR ? 4 : FMT == GAT_LAYOUT_INTERLEAVED ? 2 : FMT == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 8;
-    static constexpr int PLANES = FMT == GAT_LAYOUT_PLANAR ? 2 : 1;
-    u4 a, b; // b: the imaginary plane's 16 bytes (planar only)
-
-    // vector v (VS samples) of the antenna stream that starts `base` samples into the planes
-    __device__ __forceinline__ void load(const void *re, const void *im, size_t base, long long v)
-    {
-        constexpr size_t sample_bytes = FMT == GAT_LAYOUT_PLANAR ? 4 : FMT == GAT_LAYOUT_INTERLEAVED ? 8 : FMT == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 2;
-        const u4 *p = reinterpret_cast<const u4 *>(static_cast<const char *>(re) + base * sample_bytes) + v;
-        a = __builtin_nontemporal_load(p);
-        if constexpr (PLANES == 2) {
-            const u4 *q = reinterpret_cast<const u4 *>(static_cast<const char *>(im) + base * sample_bytes) + v;
-            b = __builtin_nontemporal_load(q);
-        }
-    }
-    template <int S>
-    __device__ __forceinline__ void sample(float &xr, float &xi) const
-    {
-        if constexpr (FMT == GAT_LAYOUT_PLANAR) {
-            xr = __uint_as_float(a[S]);
-            xi = __uint_as_float(b[S]);
-        } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED) {
-            xr = __uint_as_float(a[2 * S]);
-            xi = __uint_as_float(a[2 * S + 1]);
-        } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED_I16) {
-            const int w = (int)a[S];
-            xr = (float)((w << 16) >> 16);
-            xi = (float)(w >> 16);
-        } else {
-            const int w = (int)a[S / 2];
-            xr = (float)((w << (24 - 16 * (S % 2))) >> 24);
-            xi = (float)((w << (16 - 16 * (S % 2))) >> 24);
-        }
-    }
-};
 
 // one sample's M (M + 1) / 2 products into the upper-triangle sums (row-major over j >= i; the diagonal's s_im stays unused)
 template <int M>
@@ -111,15 +53,15 @@ __device__ __forceinline__ void cov_accumulate(const float (&xr)[M], const float
         }
 }
 
-template <int FMT, int M, int S>
-__device__ __forceinline__ void cov_accumulate_vec(const CovVec<FMT> (&raw)[M], float (&s_re)[M * (M + 1) / 2], float (&s_im)[M * (M + 1) / 2])
+template <class Vec, int M, int S>
+__device__ __forceinline__ void cov_accumulate_vec(const Vec (&raw)[M], float (&s_re)[M * (M + 1) / 2], float (&s_im)[M * (M + 1) / 2])
 {
-    if constexpr (S < CovVec<FMT>::VS) {
+    if constexpr (S < Vec::VS) {
         float xr[M], xi[M];
 #pragma unroll
-        for (int m = 0; m < M; ++m) raw[m].template sample<S>(xr[m], xi[m]);
+        for (int m = 0; m < M; ++m) raw[m].sample(std::integral_constant<int, S>{}, xr[m], xi[m]);
         cov_accumulate<M>(xr, xi, s_re, s_im);
-        cov_accumulate_vec<FMT, M, S + 1>(raw, s_re, s_im);
+        cov_accumulate_vec<Vec, M, S + 1>(raw, s_re, s_im);
     }
 }
 
@@ -127,10 +69,10 @@ __device__ __forceinline__ void cov_accumulate_vec(const CovVec<FMT> (&raw)[M], 
 template <int FMT, int M>
 __global__ void __launch_bounds__(kCovSmallThreads) cov_small_kernel(const CovArgs a)
 {
-    using Vec = CovVec<FMT>;
-    constexpr int VS = Vec::VS, P = M * (M + 1) / 2;
-    constexpr int kRun = 64 / VS;                                             // vectors of one first-level run: 64 samples per lane
-    constexpr int U = (M * Vec::PLANES <= 2) ? 4 : (M * Vec::PLANES <= 8) ? 2 : 1; // vectors in flight per lane and antenna
+    using Vec = SampleVec<FMT, true>;
+    constexpr int VS = Vec::VS, P = M * (M + 1) / 2, PLANES = FMT == GAT_LAYOUT_PLANAR ? 2 : 1;
+    constexpr int kRun = 64 / VS;                                     // vectors of one first-level run: 64 samples per lane
+    constexpr int U = (M * PLANES <= 2) ? 4 : (M * PLANES <= 8) ? 2 : 1; // vectors in flight per lane and antenna
     __shared__ float s_red[kCovSmallThreads / 64][2][M * M];
 
     const int tid = threadIdx.x, e = blockIdx.x / a.G, g = blockIdx.x % a.G;
@@ -160,13 +102,13 @@ __global__ void __launch_bounds__(kCovSmallThreads) cov_small_kernel(const CovAr
 #pragma unroll
                     for (int m = 0; m < M; ++m) raw[q][m].load(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride, v + q * kCovSmallThreads);
 #pragma unroll
-                for (int q = 0; q < U; ++q) cov_accumulate_vec<FMT, M, 0>(raw[q], s_re, s_im);
+                for (int q = 0; q < U; ++q) cov_accumulate_vec<Vec, M, 0>(raw[q], s_re, s_im);
             }
             for (; k < kRun && v < v1; ++k, v += kCovSmallThreads) {
                 Vec raw[M];
 #pragma unroll
                 for (int m = 0; m < M; ++m) raw[m].load(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride, v);
-                cov_accumulate_vec<FMT, M, 0>(raw, s_re, s_im);
+                cov_accumulate_vec<Vec, M, 0>(raw, s_re, s_im);
             }
 #pragma unroll
             for (int p = 0; p < P; ++p) t_re[p] += s_re[p], t_im[p] += s_im[p];
@@ -174,7 +116,7 @@ __global__ void __launch_bounds__(kCovSmallThreads) cov_small_kernel(const CovAr
         if (n1 == a.N && v1 * VS + tid < a.N) { // the block's last N mod VS samples: one each for the first lanes
             float xr[M], xi[M];
 #pragma unroll
-            for (int m = 0; m < M; ++m) cov_load_scalar<FMT>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)(v1 * VS + tid), xr[m], xi[m]);
+            for (int m = 0; m < M; ++m) load_sample<FMT>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)(v1 * VS + tid), xr[m], xi[m]);
 #pragma unroll
             for (int p = 0; p < P; ++p) s_re[p] = s_im[p] = 0.f;
             cov_accumulate<M>(xr, xi, s_re, s_im);
@@ -256,7 +198,7 @@ __global__ void __launch_bounds__(kCovTileThreads, 2) cov_tiled_kernel(const Cov
             for (int idx = tid; idx < M * chunk; idx += kCovTileThreads) {
                 const int m = idx / chunk, n = idx - m * chunk;
                 float xr = 0.f, xi = 0.f;
-                if (c0 + n < n1) cov_load_scalar<FMT>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)(c0 + n), xr, xi);
+                if (c0 + n < n1) load_sample<FMT>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)(c0 + n), xr, xi);
                 s_x[n * row + m] = make_float2(xr, xi);
             }
             __syncthreads();
@@ -476,12 +418,7 @@ void cov_small_dispatch(const CovArgs &a, hipStream_t st)
 hipError_t launch_cov_small(const CovArgs &a, int fmt, hipStream_t st)
 {
     if (a.M < 1 || a.M > kCovSmallMaxAnts) return hipErrorInvalidValue;
-    switch (fmt) {
-    case GAT_LAYOUT_PLANAR: cov_small_dispatch<GAT_LAYOUT_PLANAR>(a, st); break;
-    case GAT_LAYOUT_INTERLEAVED: cov_small_dispatch<GAT_LAYOUT_INTERLEAVED>(a, st); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: cov_small_dispatch<GAT_LAYOUT_INTERLEAVED_I16>(a, st); break;
-    default: cov_small_dispatch<GAT_LAYOUT_INTERLEAVED_I8>(a, st); break;
-    }
+    dispatch_layout(fmt, [&](auto F) { cov_small_dispatch<F>(a, st); });
     return hipGetLastError();
 }
 
@@ -489,12 +426,7 @@ hipError_t launch_cov_tiled(const CovArgs &a, int fmt, hipStream_t st)
 {
     const CovTileGeom geo = cov_tile_geom(a.M);
     const dim3 grid((unsigned)(a.G * a.E)), block(kCovTileThreads);
-    switch (fmt) {
-    case GAT_LAYOUT_PLANAR: hipLaunchKernelGGL(cov_tiled_kernel<GAT_LAYOUT_PLANAR>, grid, block, geo.lds_bytes, st, a, geo); break;
-    case GAT_LAYOUT_INTERLEAVED: hipLaunchKernelGGL(cov_tiled_kernel<GAT_LAYOUT_INTERLEAVED>, grid, block, geo.lds_bytes, st, a, geo); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: hipLaunchKernelGGL(cov_tiled_kernel<GAT_LAYOUT_INTERLEAVED_I16>, grid, block, geo.lds_bytes, st, a, geo); break;
-    default: hipLaunchKernelGGL(cov_tiled_kernel<GAT_LAYOUT_INTERLEAVED_I8>, grid, block, geo.lds_bytes, st, a, geo); break;
-    }
+    dispatch_layout(fmt, [&](auto F) { hipLaunchKernelGGL(cov_tiled_kernel<F>, grid, block, geo.lds_bytes, st, a, geo); });
     return hipGetLastError();
 }
 

@@ -27,65 +27,13 @@
 #include <hip/hip_runtime.h>
 
 #include "gat_beam_kernels.h"
+#include "gat_sample_load.h"
 
 namespace gat {
 
 namespace {
 
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-template <int FMT>
-__device__ __forceinline__ void beam_load_scalar(const void *re, const void *im, size_t e, float &xr, float &xi)
-{
-    if constexpr (FMT == GAT_LAYOUT_PLANAR) {
-        xr = static_cast<const float *>(re)[e];
-        xi = static_cast<const float *>(im)[e];
-    } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED) {
-        xr = static_cast<const float *>(re)[2 * e];
-        xi = static_cast<const float *>(re)[2 * e + 1];
-    } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED_I16) {
-        xr = (float)static_cast<const short *>(re)[2 * e];
-        xi = (float)static_cast<const short *>(re)[2 * e + 1];
-    } else {
-        xr = (float)static_cast<const signed char *>(re)[2 * e];
-        xi = (float)static_cast<const signed char *>(re)[2 * e + 1];
-    }
-}
-
-// one 16-byte load per plane: VS samples
-template <int FMT>
-struct BeamVec {
-    static constexpr int VS = FMT == GAT_LAYOUT_PLANAR ? 4 : FMT == GAT_LAYOUT_INTERLEAVED ? 2 : FMT == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 8;
-    u4 a, b; // b: the imaginary plane's 16 bytes (planar only)
-
-    // vector v (VS samples) of the antenna stream that starts `base` samples into the planes
-    __device__ __forceinline__ void load(const void *re, const void *im, size_t base, long long v)
-    {
-        constexpr size_t sample_bytes = FMT == GAT_LAYOUT_PLANAR ? 4 : FMT == GAT_LAYOUT_INTERLEAVED ? 8 : FMT == GAT_LAYOUT_INTERLEAVED_I16 ? 4 : 2;
-        a = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(static_cast<const char *>(re) + base * sample_bytes) + v);
-        if constexpr (FMT == GAT_LAYOUT_PLANAR) b = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(static_cast<const char *>(im) + base * sample_bytes) + v);
-    }
-    // sample s < VS (s is a constant once the caller's loop is unrolled)
-    __device__ __forceinline__ void sample(int s, float &xr, float &xi) const
-    {
-        if constexpr (FMT == GAT_LAYOUT_PLANAR) {
-            xr = __uint_as_float(a[s]);
-            xi = __uint_as_float(b[s]);
-        } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED) {
-            xr = __uint_as_float(a[2 * s]);
-            xi = __uint_as_float(a[2 * s + 1]);
-        } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED_I16) {
-            const int w = (int)a[s];
-            xr = (float)((w << 16) >> 16);
-            xi = (float)(w >> 16);
-        } else {
-            const int w = (int)a[s / 2];
-            xr = (float)((w << (24 - 16 * (s % 2))) >> 24);
-            xi = (float)((w << (16 - 16 * (s % 2))) >> 24);
-        }
-    }
-};
 
 // one term of the sum: y += conj(w) x
 __device__ __forceinline__ void beam_term(float wr, float wi, float xr, float xi, float &yr, float &yi)
@@ -144,7 +92,7 @@ __global__ void __launch_bounds__(kBeamThreads) beam_weights_kernel(const double
 template <int FMT, int M, int JT>
 __global__ void __launch_bounds__(kBeamThreads) beam_stream_kernel(const BeamArgs a, const float2 *__restrict__ w32)
 {
-    using Vec = BeamVec<FMT>;
+    using Vec = SampleVec<FMT, true>;
     constexpr int VS = Vec::VS, G = beam_group_samples(FMT), NV = G / VS;
     __shared__ float2 s_w[JT == 1 ? 1 : M * JT];
     const int tid = threadIdx.x;
@@ -215,7 +163,7 @@ __global__ void __launch_bounds__(kBeamThreads) beam_stream_kernel(const BeamArg
 #pragma unroll
                 for (int m = 0; m < M; ++m) {
                     float xr, xi;
-                    beam_load_scalar<FMT>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + n, xr, xi);
+                    load_sample<FMT>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + n, xr, xi);
 #pragma unroll
                     for (int t = 0; t < JT; ++t) beam_term(w[m * JT + t].x, w[m * JT + t].y, xr, xi, yr[t], yi[t]);
                 }
@@ -253,7 +201,7 @@ __global__ void __launch_bounds__(kBeamThreads) beam_general_kernel(const BeamAr
 #pragma unroll 4
                 for (int m = 0; m < M; ++m) {
                     float xr, xi;
-                    beam_load_scalar<FMT>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)n, xr, xi);
+                    load_sample<FMT>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)n, xr, xi);
 #pragma unroll
                     for (int t = 0; t < JT; ++t) {
                         const float2 w = s_w[m][t];
@@ -318,24 +266,14 @@ hipError_t launch_beam_weights(const double *w_re, const double *w_im, int J, in
 hipError_t launch_beam_stream(const BeamArgs &a, int fmt, const float2 *w32, int grid, hipStream_t st)
 {
     if (a.M < 1 || a.M > kBeamStreamMaxAnts || grid < 1) return hipErrorInvalidValue;
-    switch (fmt) {
-    case GAT_LAYOUT_PLANAR: beam_stream_dispatch<GAT_LAYOUT_PLANAR>(a, w32, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED: beam_stream_dispatch<GAT_LAYOUT_INTERLEAVED>(a, w32, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: beam_stream_dispatch<GAT_LAYOUT_INTERLEAVED_I16>(a, w32, grid, st); break;
-    default: beam_stream_dispatch<GAT_LAYOUT_INTERLEAVED_I8>(a, w32, grid, st); break;
-    }
+    dispatch_layout(fmt, [&](auto F) { beam_stream_dispatch<F>(a, w32, grid, st); });
     return hipGetLastError();
 }
 
 hipError_t launch_beam_general(const BeamArgs &a, int fmt, const float2 *w32, int grid, hipStream_t st)
 {
     if (a.M < 1 || a.M > GAT_MAX_ARRAY_ANTS || grid < 1) return hipErrorInvalidValue;
-    switch (fmt) {
-    case GAT_LAYOUT_PLANAR: beam_general_dispatch<GAT_LAYOUT_PLANAR>(a, w32, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED: beam_general_dispatch<GAT_LAYOUT_INTERLEAVED>(a, w32, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: beam_general_dispatch<GAT_LAYOUT_INTERLEAVED_I16>(a, w32, grid, st); break;
-    default: beam_general_dispatch<GAT_LAYOUT_INTERLEAVED_I8>(a, w32, grid, st); break;
-    }
+    dispatch_layout(fmt, [&](auto F) { beam_general_dispatch<F>(a, w32, grid, st); });
     return hipGetLastError();
 }
 

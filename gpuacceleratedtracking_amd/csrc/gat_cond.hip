@@ -24,66 +24,13 @@
 
 #include "gat_cond.h"
 #include "gat_cond_kernels.h"
+#include "gat_sample_load.h"
 
 namespace gat {
 
 namespace {
 
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-
 constexpr bool cond_is_int(int fmt) { return fmt == GAT_LAYOUT_INTERLEAVED_I16 || fmt == GAT_LAYOUT_INTERLEAVED_I8; }
-
-template <int FMT>
-__device__ __forceinline__ void cond_load_scalar(const void *re, const void *im, size_t e, float &xr, float &xi)
-{
-    if constexpr (FMT == GAT_LAYOUT_PLANAR) {
-        xr = static_cast<const float *>(re)[e];
-        xi = static_cast<const float *>(im)[e];
-    } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED) {
-        xr = static_cast<const float *>(re)[2 * e];
-        xi = static_cast<const float *>(re)[2 * e + 1];
-    } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED_I16) {
-        xr = (float)static_cast<const short *>(re)[2 * e];
-        xi = (float)static_cast<const short *>(re)[2 * e + 1];
-    } else {
-        xr = (float)static_cast<const signed char *>(re)[2 * e];
-        xi = (float)static_cast<const signed char *>(re)[2 * e + 1];
-    }
-}
-
-// one 16-byte load per plane: VS samples
-template <int FMT>
-struct CondVec {
-    static constexpr int VS = layout_vec_samples(FMT);
-    u4 a, b; // b: the imaginary plane's 16 bytes (planar only)
-
-    // vector v (VS samples) of the antenna stream that starts `base` samples into the planes
-    __device__ __forceinline__ void load(const void *re, const void *im, size_t base, long long v)
-    {
-        constexpr size_t sample_bytes = layout_sample_bytes(FMT);
-        a = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(static_cast<const char *>(re) + base * sample_bytes) + v);
-        if constexpr (FMT == GAT_LAYOUT_PLANAR) b = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(static_cast<const char *>(im) + base * sample_bytes) + v);
-    }
-    // sample s < VS (s is a constant once the caller's loop is unrolled)
-    __device__ __forceinline__ void sample(int s, float &xr, float &xi) const
-    {
-        if constexpr (FMT == GAT_LAYOUT_PLANAR) {
-            xr = __uint_as_float(a[s]);
-            xi = __uint_as_float(b[s]);
-        } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED) {
-            xr = __uint_as_float(a[2 * s]);
-            xi = __uint_as_float(a[2 * s + 1]);
-        } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED_I16) {
-            const int w = (int)a[s];
-            xr = (float)((w << 16) >> 16);
-            xi = (float)(w >> 16);
-        } else {
-            const int w = (int)a[s / 2];
-            xr = (float)((w << (24 - 16 * (s % 2))) >> 24);
-            xi = (float)((w << (16 - 16 * (s % 2))) >> 24);
-        }
-    }
-};
 
 // One output sample as two 32-bit payloads: a float output's bits, an integer output's codes.  A blanked sample is all zero
 // bits in every layout (+0.0, +0.0 or 0, 0).  clips: components of this sample that were clipped.
@@ -193,7 +140,7 @@ __device__ __forceinline__ void cond_load_records(const gat_cond_params *prm, si
 template <int FI, int FO, int M>
 __global__ void __launch_bounds__(kCondThreads) cond_stream_kernel(const CondArgs a, const gat_cond_params *__restrict__ prm)
 {
-    using Vec = CondVec<FI>;
+    using Vec = SampleVec<FI, true>;
     constexpr int VS = Vec::VS, G = cond_group_samples(FI, FO), NV = G / VS;
     static_assert(G % VS == 0 && G % layout_vec_samples(FO) == 0, "whole loads and whole stores");
     const int tid = threadIdx.x;
@@ -254,7 +201,7 @@ __global__ void __launch_bounds__(kCondThreads) cond_stream_kernel(const CondArg
             const size_t n = (size_t)(g1 * G + tid);
             float xr[M], xi[M];
 #pragma unroll
-            for (int m = 0; m < M; ++m) cond_load_scalar<FI>(a.re, a.im, base + (size_t)m * ant_stride + n, xr[m], xi[m]);
+            for (int m = 0; m < M; ++m) load_sample<FI>(a.re, a.im, base + (size_t)m * ant_stride + n, xr[m], xi[m]);
             bool any = false;
 #pragma unroll
             for (int m = 0; m < M; ++m) any |= !cond_keep(xr[m], xi[m], pr[m].threshold);
@@ -303,12 +250,12 @@ __global__ void __launch_bounds__(kCondThreads) cond_general_kernel(const CondAr
             if (a.blank_all)
                 for (int m = 0; m < M; ++m) {
                     float xr, xi;
-                    cond_load_scalar<FI>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)n, xr, xi);
+                    load_sample<FI>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)n, xr, xi);
                     any |= !cond_keep(xr, xi, s_prm[m].w);
                 }
             for (int m = 0; m < M; ++m) {
                 float xr, xi;
-                cond_load_scalar<FI>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)n, xr, xi);
+                load_sample<FI>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)n, xr, xi);
                 const float4 p = s_prm[m];
                 const bool blanked = any || !cond_keep(xr, xi, p.w);
                 unsigned o_re, o_im, clips;
@@ -343,29 +290,6 @@ void cond_stream_dispatch(const CondArgs &a, const gat_cond_params *prm, int gri
     case 6: hipLaunchKernelGGL((cond_stream_kernel<FI, FO, 6>), g, b, 0, st, a, prm); break;
     case 7: hipLaunchKernelGGL((cond_stream_kernel<FI, FO, 7>), g, b, 0, st, a, prm); break;
     default: hipLaunchKernelGGL((cond_stream_kernel<FI, FO, 8>), g, b, 0, st, a, prm); break;
-    }
-}
-
-template <int FI>
-void cond_stream_dispatch_out(const CondArgs &a, int fo, const gat_cond_params *prm, int grid, hipStream_t st)
-{
-    switch (fo) {
-    case GAT_LAYOUT_PLANAR: cond_stream_dispatch<FI, GAT_LAYOUT_PLANAR>(a, prm, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED: cond_stream_dispatch<FI, GAT_LAYOUT_INTERLEAVED>(a, prm, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: cond_stream_dispatch<FI, GAT_LAYOUT_INTERLEAVED_I16>(a, prm, grid, st); break;
-    default: cond_stream_dispatch<FI, GAT_LAYOUT_INTERLEAVED_I8>(a, prm, grid, st); break;
-    }
-}
-
-template <int FI>
-void cond_general_dispatch_out(const CondArgs &a, int fo, const gat_cond_params *prm, int grid, hipStream_t st)
-{
-    const dim3 g((unsigned)grid), b(kCondThreads);
-    switch (fo) {
-    case GAT_LAYOUT_PLANAR: hipLaunchKernelGGL((cond_general_kernel<FI, GAT_LAYOUT_PLANAR>), g, b, 0, st, a, prm); break;
-    case GAT_LAYOUT_INTERLEAVED: hipLaunchKernelGGL((cond_general_kernel<FI, GAT_LAYOUT_INTERLEAVED>), g, b, 0, st, a, prm); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: hipLaunchKernelGGL((cond_general_kernel<FI, GAT_LAYOUT_INTERLEAVED_I16>), g, b, 0, st, a, prm); break;
-    default: hipLaunchKernelGGL((cond_general_kernel<FI, GAT_LAYOUT_INTERLEAVED_I8>), g, b, 0, st, a, prm); break;
     }
 }
 
@@ -419,13 +343,13 @@ __device__ __forceinline__ void stats_take_scalar(StatsAcc<MT> &c, const StatsAr
 {
     float xr[MT], xi[MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) cond_load_scalar<FI>(a.re, a.im, base + c.ant[i] + n, xr[i], xi[i]);
+    for (int i = 0; i < MT; ++i) load_sample<FI>(a.re, a.im, base + c.ant[i] + n, xr[i], xi[i]);
     bool out = false;
     if (others)
         for (int m = 0; m < a.M; ++m) {
             if (m >= m0 && m < m0 + MT) continue;
             float yr, yi;
-            cond_load_scalar<FI>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + n, yr, yi);
+            load_sample<FI>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + n, yr, yi);
             out |= !cond_keep(yr, yi, a.prm ? a.prm[m].threshold : INFINITY);
         }
     stats_take<MT>(c, xr, xi, out, a.blank_all != 0);
@@ -434,7 +358,7 @@ __device__ __forceinline__ void stats_take_scalar(StatsAcc<MT> &c, const StatsAr
 template <int FI, int MT, bool VEC>
 __global__ void __launch_bounds__(kStatsThreads) stats_kernel(const StatsArgs a)
 {
-    using Vec = CondVec<FI>;
+    using Vec = SampleVec<FI, true>;
     constexpr int VS = Vec::VS;
     __shared__ gat_sample_stats_t s_red[kStatsThreads / 64][MT];
     const int tid = threadIdx.x, e = blockIdx.x / a.G, g = blockIdx.x % a.G;
@@ -584,40 +508,24 @@ void stats_dispatch(const StatsArgs &a, hipStream_t st)
     }
 }
 
-template <bool VEC>
-void stats_dispatch_fmt(const StatsArgs &a, int fmt, hipStream_t st)
-{
-    switch (fmt) {
-    case GAT_LAYOUT_PLANAR: stats_dispatch<GAT_LAYOUT_PLANAR, VEC>(a, st); break;
-    case GAT_LAYOUT_INTERLEAVED: stats_dispatch<GAT_LAYOUT_INTERLEAVED, VEC>(a, st); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: stats_dispatch<GAT_LAYOUT_INTERLEAVED_I16, VEC>(a, st); break;
-    default: stats_dispatch<GAT_LAYOUT_INTERLEAVED_I8, VEC>(a, st); break;
-    }
-}
-
 } // namespace
 
 hipError_t launch_cond_stream(const CondArgs &a, int fmt_in, int fmt_out, const gat_cond_params *prm, int grid, hipStream_t st)
 {
     if (a.M < 1 || a.M > kCondStreamMaxAnts || grid < 1) return hipErrorInvalidValue;
-    switch (fmt_in) {
-    case GAT_LAYOUT_PLANAR: cond_stream_dispatch_out<GAT_LAYOUT_PLANAR>(a, fmt_out, prm, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED: cond_stream_dispatch_out<GAT_LAYOUT_INTERLEAVED>(a, fmt_out, prm, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: cond_stream_dispatch_out<GAT_LAYOUT_INTERLEAVED_I16>(a, fmt_out, prm, grid, st); break;
-    default: cond_stream_dispatch_out<GAT_LAYOUT_INTERLEAVED_I8>(a, fmt_out, prm, grid, st); break;
-    }
+    dispatch_layout(fmt_in, [&](auto FI) {
+        dispatch_layout(fmt_out, [&](auto FO) { cond_stream_dispatch<decltype(FI)::value, FO>(a, prm, grid, st); });
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_cond_general(const CondArgs &a, int fmt_in, int fmt_out, const gat_cond_params *prm, int grid, hipStream_t st)
 {
     if (a.M < 1 || a.M > GAT_MAX_ARRAY_ANTS || grid < 1) return hipErrorInvalidValue;
-    switch (fmt_in) {
-    case GAT_LAYOUT_PLANAR: cond_general_dispatch_out<GAT_LAYOUT_PLANAR>(a, fmt_out, prm, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED: cond_general_dispatch_out<GAT_LAYOUT_INTERLEAVED>(a, fmt_out, prm, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: cond_general_dispatch_out<GAT_LAYOUT_INTERLEAVED_I16>(a, fmt_out, prm, grid, st); break;
-    default: cond_general_dispatch_out<GAT_LAYOUT_INTERLEAVED_I8>(a, fmt_out, prm, grid, st); break;
-    }
+    const dim3 g((unsigned)grid), b(kCondThreads);
+    dispatch_layout(fmt_in, [&](auto FI) {
+        dispatch_layout(fmt_out, [&](auto FO) { hipLaunchKernelGGL((cond_general_kernel<decltype(FI)::value, FO>), g, b, 0, st, a, prm); });
+    });
     return hipGetLastError();
 }
 
@@ -625,9 +533,9 @@ hipError_t launch_stats(const StatsArgs &a, int fmt, bool vec, hipStream_t st)
 {
     if (a.M < 1 || a.M > GAT_MAX_ARRAY_ANTS || a.E < 1 || a.G < 1 || (vec && a.M > kStatsTile)) return hipErrorInvalidValue;
     if (vec)
-        stats_dispatch_fmt<true>(a, fmt, st);
+        dispatch_layout(fmt, [&](auto F) { stats_dispatch<F, true>(a, st); });
     else
-        stats_dispatch_fmt<false>(a, fmt, st);
+        dispatch_layout(fmt, [&](auto F) { stats_dispatch<F, false>(a, st); });
     return hipGetLastError();
 }
 

@@ -20,17 +20,6 @@ bool agc_config_ok(const gat_agc_config *cfg)
            !std::isnan(cfg->blank_factor);
 }
 
-// host access to one sample of a descriptor's memory
-void host_load(const gat_signal_desc *d, size_t e, float *xr, float *xi)
-{
-    switch (d->layout) {
-    case GAT_LAYOUT_PLANAR: *xr = static_cast<const float *>(d->re)[e], *xi = static_cast<const float *>(d->im)[e]; break;
-    case GAT_LAYOUT_INTERLEAVED: *xr = static_cast<const float *>(d->re)[2 * e], *xi = static_cast<const float *>(d->re)[2 * e + 1]; break;
-    case GAT_LAYOUT_INTERLEAVED_I16: *xr = (float)static_cast<const int16_t *>(d->re)[2 * e], *xi = (float)static_cast<const int16_t *>(d->re)[2 * e + 1]; break;
-    default: *xr = (float)static_cast<const int8_t *>(d->re)[2 * e], *xi = (float)static_cast<const int8_t *>(d->re)[2 * e + 1]; break;
-    }
-}
-
 // one output sample by the rule; returns the clipped components
 int host_store(const gat_signal_desc *d, size_t e, bool keep, float xr, float xi, const gat_cond_params &p)
 {
@@ -106,7 +95,7 @@ GAT_API int32_t gat_condition_samples_host(const gat_signal_desc *sig, int32_t B
         for (int64_t n = 0; n < sig->num_samples; ++n) {
             bool any = false;
             for (int m = 0; m < M; ++m) { // every antenna is read before any is written: in place is safe
-                host_load(sig, (size_t)n + (size_t)m * (size_t)sig->ant_stride + (size_t)b * (size_t)sig->block_stride, &xr[m], &xi[m]);
+                host_load_sample(sig, (size_t)n + (size_t)m * (size_t)sig->ant_stride + (size_t)b * (size_t)sig->block_stride, &xr[m], &xi[m]);
                 any |= !cond_keep(xr[m], xi[m], params[m].threshold);
             }
             for (int m = 0; m < M; ++m) {

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "gat.h"
+#include "gat_sig_plan.h" // host_load_sample
 
 #ifndef GAT_HD
 #if defined(__HIPCC__)
@@ -99,17 +100,6 @@ GAT_HD inline void fir_rotate(const FirNco &nco, long long P, float zr, float zi
     yi = __builtin_fmaf(-s, zr, ci);
 }
 
-// host access to one sample of a descriptor's memory
-inline void fir_host_load(const gat_signal_desc *d, size_t e, float *xr, float *xi)
-{
-    switch (d->layout) {
-    case GAT_LAYOUT_PLANAR: *xr = static_cast<const float *>(d->re)[e], *xi = static_cast<const float *>(d->im)[e]; break;
-    case GAT_LAYOUT_INTERLEAVED: *xr = static_cast<const float *>(d->re)[2 * e], *xi = static_cast<const float *>(d->re)[2 * e + 1]; break;
-    case GAT_LAYOUT_INTERLEAVED_I16: *xr = (float)static_cast<const int16_t *>(d->re)[2 * e], *xi = (float)static_cast<const int16_t *>(d->re)[2 * e + 1]; break;
-    default: *xr = (float)static_cast<const int8_t *>(d->re)[2 * e], *xi = (float)static_cast<const int8_t *>(d->re)[2 * e + 1]; break;
-    }
-}
-
 // The rule as a plain loop over host memory, for a call the plan (gat_fir_plan.h) has accepted: the output is float32, planar or
 // interleaved.  Reads samples [0, N) of every (block, antenna) and nothing else; writes the Q described outputs of each.
 inline void fir_host_run(const gat_signal_desc *sig, int B, const float *taps_re, const float *taps_im, int T, int D, double step, double phase,
@@ -127,7 +117,7 @@ inline void fir_host_run(const gat_signal_desc *sig, int B, const float *taps_re
                 float zr = 0.0f, zi = 0.0f;
                 for (int t = 0; t < T; ++t) {
                     float xr, xi;
-                    fir_host_load(sig, base + (size_t)(p - t), &xr, &xi);
+                    host_load_sample(sig, base + (size_t)(p - t), &xr, &xi);
                     fir_tap(zr, zi, taps_re[t], taps_im[t], xr, xi);
                 }
                 float yr, yi;

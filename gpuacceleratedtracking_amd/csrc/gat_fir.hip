@@ -80,7 +80,7 @@ __device__ __forceinline__ void fir_tile_outputs_run(const FirArgs &a, const flo
 template <int FI, int FO>
 __global__ void __launch_bounds__(kFirThreads) fir_tiled_kernel(const FirArgs a, const float *__restrict__ taps_re, const float *__restrict__ taps_im)
 {
-    using Vec = FirVec<FI>;
+    using Vec = SampleVec<FI, false>;
     constexpr int VS = Vec::VS;
     __shared__ float2 s_x[kFirLdsSamples];
     const int tid = threadIdx.x;
@@ -103,14 +103,17 @@ __global__ void __launch_bounds__(kFirThreads) fir_tiled_kernel(const FirArgs a,
 #pragma unroll
                 for (int s = 0; s < VS; ++s) {
                     const long long p = v * VS + s;
-                    if (p >= p0 && p < p1) s_x[fir_lds_index((unsigned)(p - p0), (unsigned)a.D, (unsigned)a.row)] = raw.sample(s);
+                    if (p < p0 || p >= p1) continue;
+                    float xr, xi;
+                    raw.sample(s, xr, xi);
+                    s_x[fir_lds_index((unsigned)(p - p0), (unsigned)a.D, (unsigned)a.row)] = make_float2(xr, xi);
                 }
             }
             // the block's last N mod VS samples, one to a lane
             const long long t0 = v1 * VS > p0 ? v1 * VS : p0;
             for (long long p = t0 + tid; p < p1; p += kFirThreads) {
                 float xr, xi;
-                fir_load_scalar<FI>(a.re, a.im, base + (size_t)p, xr, xi);
+                load_sample<FI>(a.re, a.im, base + (size_t)p, xr, xi);
                 s_x[fir_lds_index((unsigned)(p - p0), (unsigned)a.D, (unsigned)a.row)] = make_float2(xr, xi);
             }
             __syncthreads();
@@ -144,7 +147,7 @@ __global__ void __launch_bounds__(kFirThreads) fir_general_kernel(const FirArgs 
             float zr = 0.0f, zi = 0.0f;
             for (int t = 0; t < a.T; ++t) {
                 float xr, xi;
-                fir_load_scalar<FI>(a.re, a.im, base + (size_t)(p - t), xr, xi);
+                load_sample<FI>(a.re, a.im, base + (size_t)(p - t), xr, xi);
                 const float2 g = s_g[t];
                 fir_tap(zr, zi, g.x, g.y, xr, xi);
             }
@@ -187,12 +190,7 @@ hipError_t fir_dispatch(const FirArgs &a, int fi, int fo, int grid, hipStream_t 
         return hipErrorInvalidValue;
     if (TILED && (a.tile < 1 || a.tile > kFirThreads * kFirLaneOutputs || a.row < a.tile + fir_halo_cols(a.T, a.D) || (long long)a.row * a.D > kFirLdsSamples))
         return hipErrorInvalidValue;
-    switch (fi) {
-    case GAT_LAYOUT_PLANAR: fir_dispatch_out<GAT_LAYOUT_PLANAR, TILED>(a, fo, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED: fir_dispatch_out<GAT_LAYOUT_INTERLEAVED, TILED>(a, fo, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: fir_dispatch_out<GAT_LAYOUT_INTERLEAVED_I16, TILED>(a, fo, grid, st); break;
-    default: fir_dispatch_out<GAT_LAYOUT_INTERLEAVED_I8, TILED>(a, fo, grid, st); break;
-    }
+    dispatch_layout(fi, [&](auto FI) { fir_dispatch_out<FI, TILED>(a, fo, grid, st); });
     return hipGetLastError();
 }
 

@@ -1,5 +1,7 @@
-// gat_sample_load.h -- how the kernels over the raw sample stream (gat_fir.hip, gat_spec.hip) read a gat_signal_desc's memory: one
-// sample with scalar loads, or the samples of one 16-byte load per plane.  Integer layouts convert exactly.  Device code only.
+// gat_sample_load.h -- how every kernel over the raw sample stream (gat_acq.hip, gat_array.hip, gat_beam.hip, gat_cond.hip,
+// gat_fir.hip, gat_spec.hip, gat_st.hip, gat_acq_fft.hip) reads a gat_signal_desc's memory: one sample with scalar loads, or the
+// samples of one 16-byte load per plane.  Integer layouts convert exactly.  Device code only; the host's twin is
+// host_load_sample (gat_sig_plan.h).  The correlator keeps a loader of its own (gat_dc.h SampleIO).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,8 +13,9 @@ namespace gat {
 
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
+// sample e of the planes
 template <int FMT>
-__device__ __forceinline__ void fir_load_scalar(const void *re, const void *im, size_t e, float &xr, float &xi)
+__device__ __forceinline__ void load_sample(const void *re, const void *im, size_t e, float &xr, float &xi)
 {
     if constexpr (FMT == GAT_LAYOUT_PLANAR) {
         xr = static_cast<const float *>(re)[e];
@@ -29,31 +32,47 @@ __device__ __forceinline__ void fir_load_scalar(const void *re, const void *im, 
     }
 }
 
-// one 16-byte load per plane: VS samples
-template <int FMT>
-struct FirVec {
+// one 16-byte load per plane: VS samples.  NT: a non-temporal load, for a stream that is read once
+template <int FMT, bool NT>
+struct SampleVec {
     static constexpr int VS = layout_vec_samples(FMT);
     u4 a, b; // b: the imaginary plane's 16 bytes (planar only)
 
+    static __device__ __forceinline__ u4 load16(const void *plane, size_t base, long long v)
+    {
+        const u4 *p = reinterpret_cast<const u4 *>(static_cast<const char *>(plane) + base * (size_t)layout_sample_bytes(FMT)) + v;
+        if constexpr (NT)
+            return __builtin_nontemporal_load(p);
+        else
+            return *p;
+    }
     // vector v (VS samples) of the antenna stream that starts `base` samples into the planes, on a 16-byte boundary
     __device__ __forceinline__ void load(const void *re, const void *im, size_t base, long long v)
     {
-        constexpr size_t sample_bytes = layout_sample_bytes(FMT);
-        a = *(reinterpret_cast<const u4 *>(static_cast<const char *>(re) + base * sample_bytes) + v);
-        if constexpr (FMT == GAT_LAYOUT_PLANAR) b = *(reinterpret_cast<const u4 *>(static_cast<const char *>(im) + base * sample_bytes) + v);
+        a = load16(re, base, v);
+        if constexpr (FMT == GAT_LAYOUT_PLANAR) b = load16(im, base, v);
     }
-    __device__ __forceinline__ float2 sample(int s) const
+    // sample s < VS: an int (a constant once the caller's loop is unrolled) or a std::integral_constant<int, s>.  The two are not
+    // the same to the optimiser: it sees this function before it is inlined, and with an int it turns the 16-byte read into one
+    // of a single element.  cov_small_kernel (gat_array.hip) was tuned on the constant's code and passes one; the others pass ints.
+    template <class S>
+    __device__ __forceinline__ void sample(S s_, float &xr, float &xi) const
     {
+        const int s = s_;
         if constexpr (FMT == GAT_LAYOUT_PLANAR) {
-            return make_float2(__uint_as_float(a[s]), __uint_as_float(b[s]));
+            xr = __uint_as_float(a[s]);
+            xi = __uint_as_float(b[s]);
         } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED) {
-            return make_float2(__uint_as_float(a[2 * s]), __uint_as_float(a[2 * s + 1]));
+            xr = __uint_as_float(a[2 * s]);
+            xi = __uint_as_float(a[2 * s + 1]);
         } else if constexpr (FMT == GAT_LAYOUT_INTERLEAVED_I16) {
             const unsigned w = a[s]; // (shifted left as unsigned, right as signed: the sign extension)
-            return make_float2((float)((int)(w << 16) >> 16), (float)((int)w >> 16));
+            xr = (float)((int)(w << 16) >> 16);
+            xi = (float)((int)w >> 16);
         } else {
             const unsigned w = a[s / 2];
-            return make_float2((float)((int)(w << (24 - 16 * (s % 2))) >> 24), (float)((int)(w << (16 - 16 * (s % 2))) >> 24));
+            xr = (float)((int)(w << (24 - 16 * (s % 2))) >> 24);
+            xi = (float)((int)(w << (16 - 16 * (s % 2))) >> 24);
         }
     }
 };

@@ -1,11 +1,14 @@
 // gat_sig_plan.h -- the host-side rules that the operators over a gat_signal_desc of raw samples share (gat_spatial_covariance,
 // gat_beamform_samples, gat_sample_stats, gat_condition_samples, gat_acquire, the correlator's planner), each stated once, as pure
-// functions of descriptors and sizes.  No HIP call and no HIP header: the device entry points, the operators' pure plans
-// (gat_cond_plan.h, gat_beam_plan.h) and a stand-alone test program (tests/condplan) compile the same text.
+// functions of descriptors and sizes, and with them the host's read of one sample and the launchers' layout dispatch.  No HIP call
+// and no HIP header: the device entry points, the operators' pure plans (gat_cond_plan.h, gat_beam_plan.h) and the stand-alone
+// test programs (tests/condplan and its kin) compile the same text.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "gat.h"
 
@@ -19,6 +22,30 @@ constexpr int layout_sample_bytes(int fmt)
 }
 constexpr int layout_vec_samples(int fmt) { return 16 / layout_sample_bytes(fmt); }
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// Host access to sample e of a descriptor's memory (the host twins; the kernels' reads are gat_sample_load.h).
+inline void host_load_sample(const gat_signal_desc *d, size_t e, float *xr, float *xi)
+{
+    switch (d->layout) {
+    case GAT_LAYOUT_PLANAR: *xr = static_cast<const float *>(d->re)[e], *xi = static_cast<const float *>(d->im)[e]; break;
+    case GAT_LAYOUT_INTERLEAVED: *xr = static_cast<const float *>(d->re)[2 * e], *xi = static_cast<const float *>(d->re)[2 * e + 1]; break;
+    case GAT_LAYOUT_INTERLEAVED_I16: *xr = (float)static_cast<const int16_t *>(d->re)[2 * e], *xi = (float)static_cast<const int16_t *>(d->re)[2 * e + 1]; break;
+    default: *xr = (float)static_cast<const int8_t *>(d->re)[2 * e], *xi = (float)static_cast<const int8_t *>(d->re)[2 * e + 1]; break;
+    }
+}
+
+// A runtime layout as a compile-time one: calls f(std::integral_constant<int, GAT_LAYOUT_*>), which a launcher hands on as a
+// template argument.  A value outside the four goes the int8 way; the plans have refused it before any launcher is reached.
+template <class F>
+decltype(auto) dispatch_layout(int fmt, F &&f)
+{
+    switch (fmt) {
+    case GAT_LAYOUT_PLANAR: return f(std::integral_constant<int, GAT_LAYOUT_PLANAR>{});
+    case GAT_LAYOUT_INTERLEAVED: return f(std::integral_constant<int, GAT_LAYOUT_INTERLEAVED>{});
+    case GAT_LAYOUT_INTERLEAVED_I16: return f(std::integral_constant<int, GAT_LAYOUT_INTERLEAVED_I16>{});
+    default: return f(std::integral_constant<int, GAT_LAYOUT_INTERLEAVED_I8>{});
+    }
+}
 
 // What planning returns: GAT_OK, or a refusal's code and message (the caller reports it with fail()).
 struct Refusal {

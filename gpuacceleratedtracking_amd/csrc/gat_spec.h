@@ -81,7 +81,7 @@ inline void spec_host_run(const gat_signal_desc *sig, int B, const float *window
             for (long long s = 0; s < S; ++s) {
                 for (int n = 0; n < F; ++n) {
                     float xr, xi;
-                    fir_host_load(sig, base + (size_t)(s * H + n), &xr, &xi);
+                    host_load_sample(sig, base + (size_t)(s * H + n), &xr, &xi);
                     const unsigned q = spec_bitrev((unsigned)n, L);
                     vr[q] = spec_mul(window[n], xr), vi[q] = spec_mul(window[n], xi);
                 }

@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(kSpecThreads) spec_kernel(const SpecArgs a, co
 
         // raw samples of one segment: the general path's floats, the aligned path's 16-byte vectors
         float rr[VEC ? 1 : R], ri[VEC ? 1 : R];
-        FirVec<FMT> rv[VEC ? NL : 1];
+        SampleVec<FMT, false> rv[VEC ? NL : 1];
         auto fetch = [&](int s) {
             const size_t seg = base + (size_t)s * (size_t)a.H;
 #pragma unroll
@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(kSpecThreads) spec_kernel(const SpecArgs a, co
                 if constexpr (VEC)
                     rv[c].load(a.re, a.im, seg, (long long)((int)t + team * c));
                 else
-                    fir_load_scalar<FMT>(a.re, a.im, seg + (size_t)((int)t + team * c), rr[c], ri[c]);
+                    load_sample<FMT>(a.re, a.im, seg + (size_t)((int)t + team * c), rr[c], ri[c]);
             }
         };
         fetch(0);
@@ -114,14 +114,14 @@ __global__ void __launch_bounds__(kSpecThreads) spec_kernel(const SpecArgs a, co
                 if (!active || !has[c]) continue;
 #pragma unroll
                 for (int e = 0; e < VS; ++e) {
-                    float2 x;
+                    float sr, si;
                     if constexpr (VEC)
-                        x = rv[c].sample(e);
+                        rv[c].sample(e, sr, si);
                     else
-                        x = make_float2(rr[c], ri[c]);
+                        sr = rr[c], si = ri[c];
                     const float w = win[c * VS + e];
                     const unsigned n = (unsigned)(((int)t + team * c) * VS + e);
-                    pts[spec_skew(spec_bitrev(n, L))] = make_float2(spec_mul(w, x.x), spec_mul(w, x.y));
+                    pts[spec_skew(spec_bitrev(n, L))] = make_float2(spec_mul(w, sr), spec_mul(w, si));
                 }
             }
             if (s + 1 < a.S) fetch(s + 1);
@@ -164,12 +164,7 @@ void spec_dispatch_points(const SpecArgs &a, int R, int grid, hipStream_t st)
 template <bool VEC>
 void spec_dispatch(const SpecArgs &a, int R, int fmt, int grid, hipStream_t st)
 {
-    switch (fmt) {
-    case GAT_LAYOUT_PLANAR: spec_dispatch_points<GAT_LAYOUT_PLANAR, VEC>(a, R, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED: spec_dispatch_points<GAT_LAYOUT_INTERLEAVED, VEC>(a, R, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: spec_dispatch_points<GAT_LAYOUT_INTERLEAVED_I16, VEC>(a, R, grid, st); break;
-    default: spec_dispatch_points<GAT_LAYOUT_INTERLEAVED_I8, VEC>(a, R, grid, st); break;
-    }
+    dispatch_layout(fmt, [&](auto F) { spec_dispatch_points<F, VEC>(a, R, grid, st); });
 }
 
 } // namespace

@@ -11,7 +11,7 @@
 #include <stdint.h>
 
 #include "gat.h"
-#include "gat_fir.h" // fir_host_load: host access to one sample of a descriptor's memory
+#include "gat_fir.h" // GAT_HD, and with it gat_sig_plan.h: host_load_sample
 
 namespace gat {
 
@@ -52,7 +52,7 @@ inline void st_host_run(const gat_signal_desc *sig, int B, const double *w_re, c
                 for (int t = 0; t < T; ++t)
                     for (int m = 0; m < M; ++m) {
                         float xr, xi;
-                        fir_host_load(sig, base + (size_t)m * (size_t)sig->ant_stride + (size_t)(n + T - 1 - t), &xr, &xi);
+                        host_load_sample(sig, base + (size_t)m * (size_t)sig->ant_stride + (size_t)(n + T - 1 - t), &xr, &xi);
                         const size_t q = (size_t)j * (size_t)Q + (size_t)(t * M + m);
                         st_term((float)w_re[q], (float)w_im[q], xr, xi, yr, yi);
                     }

@@ -85,7 +85,7 @@ __device__ __forceinline__ void st_tile_run(const StArgs &a, const float2 *s_x, 
 template <int FI, int FO, int JT>
 __global__ void __launch_bounds__(kStThreads) st_tiled_kernel(const StArgs a, const float2 *__restrict__ w32)
 {
-    using Vec = FirVec<FI>;
+    using Vec = SampleVec<FI, false>;
     constexpr int VS = Vec::VS;
     __shared__ __align__(16) float2 s_x[kStLdsSamples];
     __shared__ __align__(16) float2 s_w[GAT_MAX_ARRAY_ANTS * JT];
@@ -114,7 +114,10 @@ __global__ void __launch_bounds__(kStThreads) st_tiled_kernel(const StArgs a, co
 #pragma unroll
                     for (int s = 0; s < VS; ++s) {
                         const long long p = v * VS + s;
-                        if (p >= p0 && p < p1) s_x[m * a.row + (int)(p - p0)] = raw.sample(s);
+                        if (p < p0 || p >= p1) continue;
+                        float xr, xi;
+                        raw.sample(s, xr, xi);
+                        s_x[m * a.row + (int)(p - p0)] = make_float2(xr, xi);
                     }
                 }
                 // the block's last N mod VS samples, one to a lane
@@ -124,7 +127,7 @@ __global__ void __launch_bounds__(kStThreads) st_tiled_kernel(const StArgs a, co
                     const int m = idx / ntail;
                     const long long p = t0 + (idx - m * ntail);
                     float xr, xi;
-                    fir_load_scalar<FI>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)p, xr, xi);
+                    load_sample<FI>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)p, xr, xi);
                     s_x[m * a.row + (int)(p - p0)] = make_float2(xr, xi);
                 }
                 __syncthreads(); // (the pass's weights too)
@@ -163,7 +166,7 @@ __global__ void __launch_bounds__(kStThreads) st_general_kernel(const StArgs a, 
                     const size_t p = base + (size_t)(n + (a.T - 1 - t));
                     for (int m = 0; m < M; ++m, ++q) {
                         float xr, xi;
-                        fir_load_scalar<FI>(a.re, a.im, p + (size_t)m * (size_t)a.ant_stride, xr, xi);
+                        load_sample<FI>(a.re, a.im, p + (size_t)m * (size_t)a.ant_stride, xr, xi);
 #pragma unroll
                         for (int t2 = 0; t2 < JT; ++t2) {
                             const float2 w = s_w[q][t2];
@@ -233,7 +236,7 @@ __global__ void __launch_bounds__(kStCovThreads, 2) st_cov_kernel(const CovArgs 
             for (int idx = tid; idx < M * cols; idx += kStCovThreads) {
                 const int m = idx / cols, c = idx - m * cols; // column c: sample c0 + c
                 float xr = 0.f, xi = 0.f;
-                if (c0 + c < lim) fir_load_scalar<FMT>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)(c0 + c), xr, xi);
+                if (c0 + c < lim) load_sample<FMT>(a.re, a.im, base + (size_t)m * (size_t)a.ant_stride + (size_t)(c0 + c), xr, xi);
                 s_x[kStCovPad + c * M + (M - 1 - m)] = make_float2(xr, xi);
             }
             __syncthreads();
@@ -332,12 +335,7 @@ hipError_t st_dispatch(const StArgs &a, int fi, const float2 *w32, int grid, hip
         return hipErrorInvalidValue;
     if (TILED && (a.M > kStTiledMaxAnts || a.tile < 1 || a.tile > kStThreads * kStLaneOutputs || a.row < a.tile + a.T - 1 || (long long)a.row * a.M > kStLdsSamples))
         return hipErrorInvalidValue;
-    switch (fi) {
-    case GAT_LAYOUT_PLANAR: st_dispatch_out<GAT_LAYOUT_PLANAR, TILED>(a, w32, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED: st_dispatch_out<GAT_LAYOUT_INTERLEAVED, TILED>(a, w32, grid, st); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: st_dispatch_out<GAT_LAYOUT_INTERLEAVED_I16, TILED>(a, w32, grid, st); break;
-    default: st_dispatch_out<GAT_LAYOUT_INTERLEAVED_I8, TILED>(a, w32, grid, st); break;
-    }
+    dispatch_layout(fi, [&](auto FI) { st_dispatch_out<FI, TILED>(a, w32, grid, st); });
     return hipGetLastError();
 }
 
@@ -353,12 +351,7 @@ hipError_t launch_st_cov(const CovArgs &a, int T, int fmt, hipStream_t st)
     const StCovGeom geo = st_cov_geom(a.M, T);
     if (geo.lds_bytes > 65536 || a.seg_len % geo.chunk != 0) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(a.G * a.E)), block(kStCovThreads);
-    switch (fmt) {
-    case GAT_LAYOUT_PLANAR: hipLaunchKernelGGL(st_cov_kernel<GAT_LAYOUT_PLANAR>, grid, block, geo.lds_bytes, st, a, geo, T); break;
-    case GAT_LAYOUT_INTERLEAVED: hipLaunchKernelGGL(st_cov_kernel<GAT_LAYOUT_INTERLEAVED>, grid, block, geo.lds_bytes, st, a, geo, T); break;
-    case GAT_LAYOUT_INTERLEAVED_I16: hipLaunchKernelGGL(st_cov_kernel<GAT_LAYOUT_INTERLEAVED_I16>, grid, block, geo.lds_bytes, st, a, geo, T); break;
-    default: hipLaunchKernelGGL(st_cov_kernel<GAT_LAYOUT_INTERLEAVED_I8>, grid, block, geo.lds_bytes, st, a, geo, T); break;
-    }
+    dispatch_layout(fmt, [&](auto F) { hipLaunchKernelGGL(st_cov_kernel<F>, grid, block, geo.lds_bytes, st, a, geo, T); });
     return hipGetLastError();
 }
 

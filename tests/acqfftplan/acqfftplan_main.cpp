@@ -205,7 +205,7 @@ void run_host_loop(std::mt19937_64 &rng, int li, int B, int M, long long N, long
                 long double rr = 0, ri = 0, A = 0;
                 for (long long n = 0; n < N; ++n) {
                     float xr, xi;
-                    fir_host_load(&sg, (size_t)(b * bs + m * as + n), &xr, &xi);
+                    host_load_sample(&sg, (size_t)(b * bs + m * as + n), &xr, &xi);
                     const long long x = n + first_shift + (long long)s * j;
                     const double ph = ratio * (double)x + tau;
                     long long ip = (long long)std::floor(ph) % Lc;

@@ -154,7 +154,7 @@ void run_host_loop(std::mt19937_64 &rng, int li, int lo, int B, int M, long long
         long double zr = 0, zi = 0, S = 0;
         for (int t = 0; t < T; ++t) {
             float xr, xi;
-            fir_host_load(&s, (size_t)(b * ibs + m * ias + pn - t), &xr, &xi);
+            host_load_sample(&s, (size_t)(b * ibs + m * ias + pn - t), &xr, &xi);
             zr += (long double)g_re[(size_t)t] * xr - (long double)g_im[(size_t)t] * xi;
             zi += (long double)g_re[(size_t)t] * xi + (long double)g_im[(size_t)t] * xr;
             S += (fabsl(g_re[(size_t)t]) + fabsl(g_im[(size_t)t])) * (fabsl(xr) + fabsl(xi));

@@ -171,7 +171,7 @@ void run_host_loop(std::mt19937_64 &rng, int li, int B, int M, long long N, long
             long double xr = 0, xi = 0, A = 0;
             for (int n = 0; n < F; ++n) {
                 float sr, si;
-                fir_host_load(&s, (size_t)(b * bs + m * as + sg * H + n), &sr, &si);
+                host_load_sample(&s, (size_t)(b * bs + m * as + sg * H + n), &sr, &si);
                 const long double ph = two_pi * (long double)(((long long)f * n) % F) / F, cc = cosl(ph), ss = sinl(ph);
                 xr += (long double)w[(size_t)n] * (sr * cc + si * ss);
                 xi += (long double)w[(size_t)n] * (si * cc - sr * ss);

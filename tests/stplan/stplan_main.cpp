@@ -161,7 +161,7 @@ void run_host_loop(std::mt19937_64 &rng, int li, int lo, int B, int M, long long
         for (int t = 0; t < T; ++t)
             for (int m = 0; m < M; ++m) {
                 float xr, xi;
-                fir_host_load(&s, (size_t)(b * ibs + m * ias + n + T - 1 - t), &xr, &xi);
+                host_load_sample(&s, (size_t)(b * ibs + m * ias + n + T - 1 - t), &xr, &xi);
                 const long double wr = w_re[(size_t)j * Q + t * M + m], wi = w_im[(size_t)j * Q + t * M + m];
                 yr += wr * xr + wi * xi;
                 yi += wr * xi - wi * xr;
