@@ -34,6 +34,8 @@ GAT_MAX_FIR_TAPS, GAT_MAX_FIR_DECIMATION = 256, 64
 GAT_MIN_SPECTRUM_BINS, GAT_MAX_SPECTRUM_BINS, GAT_MAX_SPECTRUM_SEGMENTS = 64, 4096, 4096
 # space-time adaptive processing (taps per antenna; num_ants * num_taps <= GAT_MAX_ARRAY_ANTS)
 GAT_MAX_ST_TAPS = 16
+# tracking monitor (gat_track_monitor limits)
+GAT_MAX_SYMBOL_BLOCKS, GAT_MAX_MONITOR_BLOCKS, GAT_MAX_MONITOR_CHANNELS = 128, 1 << 20, 4096
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -65,6 +67,8 @@ EXPORTS = [
     "gat_sample_spectrum", "gat_sample_spectrum_host",
     # space-time adaptive processing: the tapped covariance and the space-time sample filter
     "gat_spacetime_covariance", "gat_spacetime_filter", "gat_spacetime_filter_host",
+    # tracking monitor: C/N0, phase lock, bit synchronisation and data symbols from the accumulator history
+    "gat_track_monitor", "gat_track_monitor_host", "gat_track_monitor_plan",
 ]
 
 
@@ -192,6 +196,30 @@ class SpectrumConfig(C.Structure):
 assert C.sizeof(SpectrumConfig) == 16
 
 
+class MonitorConfig(C.Structure):
+    """gat_monitor_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("num_taps", C.c_int32), ("prompt_index", C.c_int32), ("window_blocks", C.c_int32),
+                ("symbol_blocks", C.c_int32), ("symbol_offset", C.c_int32), ("first_block", C.c_int64), ("overlay", C.c_int8 * 128)]
+
+
+class MonitorPlan(C.Structure):
+    """gat_monitor_plan (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("num_windows", C.c_int32), ("search_symbols", C.c_int32), ("symbol_capacity", C.c_int32),
+                ("prompt_workgroups", C.c_int32), ("window_workgroups", C.c_int32), ("term_workgroups", C.c_int32),
+                ("energy_workgroups", C.c_int32), ("pick_workgroups", C.c_int32), ("symbol_workgroups", C.c_int32),
+                ("scratch_bytes", C.c_int64)]
+
+
+# gat_monitor_window and gat_monitor_channel (include/gat.h)
+MONITOR_WINDOW_DTYPE = np.dtype([("sum_p2", "<f8"), ("sum_p4", "<f8"), ("sum_d", "<f8"), ("sum_i", "<f8"), ("sum_q", "<f8"), ("blocks", "<i8")])
+MONITOR_CHANNEL_DTYPE = np.dtype([("symbol_offset", "<i4"), ("start", "<i4"), ("num_symbols", "<i4"), ("reserved", "<i4"),
+                                  ("e_max", "<f8"), ("e_second", "<f8")])
+assert C.sizeof(MonitorConfig) == 160 and C.sizeof(MonitorPlan) == 48
+assert MONITOR_WINDOW_DTYPE.itemsize == 48 and MONITOR_CHANNEL_DTYPE.itemsize == 32
+
+
 _LIB = None
 
 
@@ -300,6 +328,9 @@ def load(build_if_missing: bool = True):
         "gat_spacetime_covariance": (i32, [vp, sp, i32, i32, i32, vp, vp]),
         "gat_spacetime_filter": (i32, [vp, sp, i32, vp, vp, i32, i32, sp]),
         "gat_spacetime_filter_host": (i32, [sp, i32, vp, vp, i32, i32, sp]),
+        "gat_track_monitor": (i32, [vp, vp, vp, i64, i32, i32, i32, C.POINTER(MonitorConfig), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gat_track_monitor_host": (i32, [vp, vp, i64, i32, i32, i32, C.POINTER(MonitorConfig), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gat_track_monitor_plan": (i32, [i64, i32, i32, i32, C.POINTER(MonitorConfig), i32, i32, C.POINTER(MonitorPlan)]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

@@ -8,12 +8,7 @@
 #include <math.h>
 
 #include "gat.h"
-
-#if defined(__HIPCC__)
-#define GAT_HD __host__ __device__
-#else
-#define GAT_HD
-#endif
+#include "gat_mon.h" // GAT_HD, tap_sum
 
 namespace gat {
 
@@ -25,23 +20,7 @@ GAT_HD inline void loop_update_channel(const float *acc_re, const float *acc_im,
                                        const double *w_im = nullptr)
 {
     const int L = cfg.num_taps;
-    auto tap = [&](int l, double &re, double &im) {
-        re = im = 0.0;
-        if (w_re && w_im) {
-            for (int m = 0; m < M; ++m) {
-                const size_t o = ((size_t)k * L + l) * M + m;
-                const double ar = (double)acc_re[o], ai = (double)acc_im[o], wr = w_re[(size_t)k * M + m], wi = w_im[(size_t)k * M + m];
-                re += wr * ar + wi * ai;
-                im += wr * ai - wi * ar;
-            }
-            return;
-        }
-        for (int m = 0; m < M; ++m) {
-            const size_t o = ((size_t)k * L + l) * M + m;
-            re += (double)acc_re[o];
-            im += (double)acc_im[o];
-        }
-    };
+    auto tap = [&](int l, double &re, double &im) { tap_sum(acc_re, acc_im, k, L, l, M, w_re, w_im, re, im); }; // gat_mon.h: the monitor's prompt too
     double pr, pi, er, ei, lr, li;
     tap(cfg.prompt_index, pr, pi);
     tap(cfg.early_index, er, ei);

@@ -142,6 +142,19 @@ class TrackingLoop:
             self.out_im.copy_(acc_im[-1:])
         return acc_re, acc_im
 
+    def monitor(self, acc_re: torch.Tensor, acc_im: torch.Tensor, **kw):
+        """``monitor.monitor_accumulators`` over accumulators of this loop (``run(keep=True)``) with the loop's prompt tap, block
+        length, beamformer weights and its system's overlay filled in; every keyword of that function may be given."""
+        from .monitor import monitor_accumulators, overlay_for
+
+        kw.setdefault("block_seconds", self.config.block_seconds)
+        kw.setdefault("prompt_index", int(self.config.prompt_index))
+        kw.setdefault("overlay", overlay_for(self.system))
+        kw.setdefault("ctx", self.ctx)
+        if self._w_re is not None:
+            kw.setdefault("weights", (self._w_re, self._w_im))
+        return monitor_accumulators(acc_re, acc_im, **kw)
+
     def params(self) -> np.ndarray:
         """Current per-channel parameters (host copy; synchronises)."""
         return self._params[self._cur].cpu().numpy().view(_lib.PARAMS_DTYPE).copy()

@@ -992,6 +992,103 @@ GAT_API int32_t gat_sample_spectrum(gat_ctx *ctx, const gat_signal_desc *signal,
 GAT_API int32_t gat_sample_spectrum_host(const gat_signal_desc *signal, int32_t num_blocks, const float *window_host,
                                          const gat_spectrum_config *cfg, float *power_host);
 
+/* ---- tracking monitor: C/N0, phase lock, bit synchronisation and data symbols from the accumulator history ----------------
+ * What a receiver asks of its tracking channels, computed from the accumulators gat_tracking_run (or the correlator) left
+ * on the device: B blocks, block b at acc + b * acc_block_stride floats, element [k][l][m] at (k*L + l)*M + m.  Everything
+ * is double precision, every sum is sequential from +0 in the stated order and every expression is evaluated as written
+ * (csrc/gat_mon.h, shared by the kernels and the host twin: the same bits); no transcendental function and no sqrt is
+ * evaluated: the call writes raw sums, and decibels are made by the caller (below).
+ *   prompt   P[k][b] = the loop's prompt (gat_tracking_update): sum_m acc[b][k][prompt_index][m], or with weights
+ *            sum_m conj(w[k][m]) * acc, in m order: re += wr*ar + wi*ai, im += wr*ai - wi*ar.  I = re P, Q = im P.
+ *   windows  W = window_blocks, NW = ceil(B / W), the last window takes what is left.  Window v of channel k, over its
+ *            blocks in order: sum_p2 = sum (I*I + Q*Q), sum_p4 = sum (I*I + Q*Q)*(I*I + Q*Q), sum_d = sum (I*I - Q*Q),
+ *            sum_i = sum I, sum_q = sum Q, blocks.
+ *   symbols  Pd = symbol_blocks (1 .. GAT_MAX_SYMBOL_BLOCKS) blocks make one data symbol; overlay[0 .. Pd) holds the
+ *            secondary code as +1 / -1 (all +1 for GPS L1 C/A with Pd = 20; NH10 0000110101 for L5 I5, NH20
+ *            00000100110101001110 for L5 Q5, a 0 bit being +1).  For a call-relative start c and symbol j
+ *                S[c][j] = sum_{i < Pd} overlay[i] * P[k][c + j*Pd + i]     re and im apart, in i order
+ *                wbp[c][j] = sum_i (I*I + Q*Q)                              over the same blocks
+ *   bit sync J = floor((B - Pd + 1) / Pd) symbols for EVERY candidate c = 0 .. Pd-1, E[k][c] = sum_{j < J} (Sr*Sr + Si*Si)
+ *            in j order, and c* = the lowest c with the largest E.  J = 0: c* = -1, no symbols, E = 0.  |S|^2 needs no
+ *            phase lock and works under a secondary code, where a histogram of sign changes does not.  A forced
+ *            symbol_offset = o >= 0 sets c* = (o - first_block) mod Pd and skips the choice (E is computed all the same).
+ *   record   per channel: symbol_offset = (first_block + c*) mod Pd, the offset in terms of the STREAM (first_block: the
+ *            stream's block number of this call's block 0), start = c*, num_symbols = floor((B - c*) / Pd), e_max = E[c*],
+ *            e_second = the largest E at another c (0 if Pd = 1).  With c* = -1: -1, -1, 0, 0, 0.
+ *   demod    symbol j < num_symbols of channel k is S[c*][j] (sym_re, sym_im) with wbp[c*][j] (sym_wbp); entries from
+ *            num_symbols to the capacity floor(B / Pd) are written as 0.
+ * What the caller makes of the sums (T = the block's seconds):
+ *   phase lock   sum_d / sum_p2: an estimate of cos 2 phi that does not depend on the data bits
+ *   C/N0 (moments)  M2 = sum_p2 / blocks, M4 = sum_p4 / blocks, Ps = sqrt(2 M2^2 - M4) (no estimate where the radicand
+ *                is <= 0), C/N0 = 10 log10(Ps / ((M2 - Ps) T)) dB-Hz
+ *   C/N0 (narrow-to-wide power ratio)  mu = mean over the symbols of |S|^2 / wbp, C/N0 = 10 log10((mu - 1) / ((Pd - mu) T))
+ *                (no estimate for Pd = 1 or mu outside (1, Pd))
+ *   bits         the sign of sym_re; the Costas loop's half-cycle ambiguity is left in (one sign per channel)
+ * Both C/N0 estimators read low when a bit edge falls inside a block.
+ * There is no state between calls: a continuing stream passes first_block and, once synchronised, the forced offset.
+ * Outputs, every one optional (null: not written; at least one is given): prompt_re / prompt_im double [K][B]; windows
+ * [K][NW]; energy double [K][Pd]; channels [K]; sym_re / sym_im / sym_wbp double [K][floor(B / Pd)] (nothing is written
+ * where that is 0).  w_re / w_im: double [K][M] as gat_array_weights writes them, both or neither.
+ * The call enqueues on the context's stream, does not synchronise and allocates nothing but the context's scratch; c* is
+ * chosen on the device and read there by the kernel that writes the symbols.  No atomics: the same bits every call.
+ * Refusals, all before any launch (the host twin: before any write): GAT_ERR_ARG for a null accumulator pointer or
+ * config, a wrong struct_size, num_blocks, num_channels, num_ants or num_taps < 1, window_blocks < 1, an overlay entry
+ * that is not +1 or -1, first_block < 0, acc_block_stride < K*L*M with more than one block, one weight pointer without
+ * the other and a call with every output null; GAT_ERR_RANGE for num_ants above GAT_MAX_ARRAY_ANTS, num_blocks above 2^20,
+ * num_channels above 4096, prompt_index outside [0, num_taps), symbol_blocks outside 1 .. GAT_MAX_SYMBOL_BLOCKS,
+ * symbol_offset outside -1 .. Pd-1 and a call whose scratch would exceed 1 GiB (about 3 * 8 * K * B bytes). */
+#define GAT_MAX_SYMBOL_BLOCKS 128
+#define GAT_MAX_MONITOR_BLOCKS 1048576
+#define GAT_MAX_MONITOR_CHANNELS 4096
+typedef struct gat_monitor_config {
+    uint32_t struct_size;  /* sizeof(gat_monitor_config) */
+    int32_t num_taps;      /* L of the accumulators */
+    int32_t prompt_index;  /* 0 .. L-1, the loop configuration's */
+    int32_t window_blocks; /* W >= 1 */
+    int32_t symbol_blocks; /* Pd: 1 .. GAT_MAX_SYMBOL_BLOCKS */
+    int32_t symbol_offset; /* -1: search; 0 .. Pd-1: forced, in stream terms */
+    int64_t first_block;   /* >= 0: the stream's number of this call's block 0 */
+    int8_t overlay[128];   /* [0 .. Pd): +1 / -1; the rest is ignored */
+} gat_monitor_config;
+typedef struct gat_monitor_window {
+    double sum_p2, sum_p4, sum_d, sum_i, sum_q;
+    int64_t blocks;
+} gat_monitor_window;
+typedef struct gat_monitor_channel {
+    int32_t symbol_offset; /* (first_block + start) mod Pd, or -1 */
+    int32_t start;         /* c*: the call's block at which symbol 0 begins, or -1 */
+    int32_t num_symbols;
+    int32_t reserved;
+    double e_max, e_second;
+} gat_monitor_channel;
+GAT_API int32_t gat_track_monitor(gat_ctx *ctx, const float *acc_re_dev, const float *acc_im_dev, int64_t acc_block_stride,
+                                  int32_t num_blocks, int32_t num_channels, int32_t num_ants, const gat_monitor_config *config,
+                                  const double *w_re_dev, const double *w_im_dev, double *prompt_re, double *prompt_im,
+                                  gat_monitor_window *windows, double *energy, gat_monitor_channel *channels, double *sym_re,
+                                  double *sym_im, double *sym_wbp);
+/* The same rule in plain loops on the HOST (csrc/gat_mon.h, shared with the device): every pointer is host memory; needs
+ * no context and no device.  The bit-exact reference of the device call, with the same refusals. */
+GAT_API int32_t gat_track_monitor_host(const float *acc_re_host, const float *acc_im_host, int64_t acc_block_stride,
+                                       int32_t num_blocks, int32_t num_channels, int32_t num_ants, const gat_monitor_config *config,
+                                       const double *w_re_host, const double *w_im_host, double *prompt_re, double *prompt_im,
+                                       gat_monitor_window *windows, double *energy, gat_monitor_channel *channels, double *sym_re,
+                                       double *sym_im, double *sym_wbp);
+/* What gat_track_monitor would do with a call (csrc/gat_mon_plan.h; no context, no device, nothing is read but config):
+ * the counts, the bytes of context scratch and the workgroups of each kernel (256 threads each; the window kernel gives
+ * one wave of 64 lanes to a window).  own_prompts: the caller passes no prompt buffers, the series lives in the scratch;
+ * want_symbols: one of energy, channels and the symbol outputs is asked for.  The refusals are the call's. */
+typedef struct gat_monitor_plan {
+    uint32_t struct_size; /* sizeof(gat_monitor_plan), set by the caller */
+    int32_t num_windows;      /* NW */
+    int32_t search_symbols;   /* J */
+    int32_t symbol_capacity;  /* floor(B / Pd) */
+    int32_t prompt_workgroups, window_workgroups, term_workgroups, energy_workgroups, pick_workgroups, symbol_workgroups;
+    int64_t scratch_bytes;
+} gat_monitor_plan;
+GAT_API int32_t gat_track_monitor_plan(int64_t acc_block_stride, int32_t num_blocks, int32_t num_channels, int32_t num_ants,
+                                       const gat_monitor_config *config, int32_t own_prompts, int32_t want_symbols,
+                                       gat_monitor_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1000,4 +1000,114 @@ function tracking_run_weighted!(ctx::Context, desc::SignalDesc, num_blocks::Inte
     cur_is_b[] != 0
 end
 
+# ---- tracking monitor: C/N0, phase lock, bit synchronisation and data symbols from the accumulator history (include/gat.h) ----
+# struct gat_monitor_config (160 bytes)
+struct MonitorConfig
+    struct_size::UInt32
+    num_taps::Int32
+    prompt_index::Int32       # 0-based, the loop configuration's
+    window_blocks::Int32
+    symbol_blocks::Int32      # Pd: 1 .. 128
+    symbol_offset::Int32      # -1: search; 0 .. Pd-1: forced, in stream blocks
+    first_block::Int64        # the stream's number of this call's block 0
+    overlay::NTuple{128,Int8} # +1 / -1 for the Pd blocks of a symbol
+end
+function MonitorConfig(num_taps::Integer, prompt_index::Integer, overlay::AbstractVector{<:Integer}; window_blocks::Integer = 20,
+                       symbol_offset::Integer = -1, first_block::Integer = 0)
+    ov = ntuple(i -> i <= length(overlay) ? Int8(overlay[i]) : Int8(0), 128)
+    MonitorConfig(UInt32(sizeof(MonitorConfig)), Int32(num_taps), Int32(prompt_index), Int32(window_blocks), Int32(length(overlay)),
+                  Int32(symbol_offset), Int64(first_block), ov)
+end
+# the secondary codes as +-1 (a 0 bit is +1): GPS L5 I5 and Q5; GPS L1 C/A has none: ones(Int8, 20)
+const NH10 = Int8[1 - 2 * (c - '0') for c in "0000110101"]
+const NH20 = Int8[1 - 2 * (c - '0') for c in "00000100110101001110"]
+struct MonitorWindow
+    sum_p2::Float64
+    sum_p4::Float64
+    sum_d::Float64
+    sum_i::Float64
+    sum_q::Float64
+    blocks::Int64
+end
+struct MonitorChannel
+    symbol_offset::Int32
+    start::Int32
+    num_symbols::Int32
+    reserved::Int32
+    e_max::Float64
+    e_second::Float64
+end
+struct MonitorPlan
+    struct_size::UInt32
+    num_windows::Int32
+    search_symbols::Int32
+    symbol_capacity::Int32
+    prompt_workgroups::Int32
+    window_workgroups::Int32
+    term_workgroups::Int32
+    energy_workgroups::Int32
+    pick_workgroups::Int32
+    symbol_workgroups::Int32
+    scratch_bytes::Int64
+end
+# what the caller makes of the raw sums (T: seconds of a block): decibels are not made on the device
+phase_lock(w::MonitorWindow) = w.sum_d / w.sum_p2
+function cn0_m2m4(w::MonitorWindow, T::Float64)
+    m2, m4 = w.sum_p2 / w.blocks, w.sum_p4 / w.blocks
+    rad = 2 * m2 * m2 - m4
+    rad > 0 || return NaN
+    ps = sqrt(rad)
+    10 * log10(ps / ((m2 - ps) * T))
+end
+function cn0_nwpr(sym_re::AbstractVector{Float64}, sym_im::AbstractVector{Float64}, sym_wbp::AbstractVector{Float64}, Pd::Integer, T::Float64)
+    (Pd == 1 || isempty(sym_re)) && return NaN
+    mu = sum((sym_re .^ 2 .+ sym_im .^ 2) ./ sym_wbp) / length(sym_re)
+    1 < mu < Pd || return NaN
+    10 * log10((mu - 1) / ((Pd - mu) * T))
+end
+# Every output is a device pointer or C_NULL (not written); acc: [M x L x K] floats a block, blocks acc_block_stride floats apart;
+# prompts [B x K], windows [NW x K], energy [Pd x K], channels [K], symbols [floor(B / Pd) x K] in Julia's order.  Enqueues only.
+function track_monitor!(ctx::Context, acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, acc_block_stride::Integer, num_blocks::Integer,
+                        num_channels::Integer, num_ants::Integer, cfg::MonitorConfig; w_re::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                        w_im::Ptr{Float64} = Ptr{Float64}(C_NULL), prompt_re::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                        prompt_im::Ptr{Float64} = Ptr{Float64}(C_NULL), windows::Ptr{MonitorWindow} = Ptr{MonitorWindow}(C_NULL),
+                        energy::Ptr{Float64} = Ptr{Float64}(C_NULL), channels::Ptr{MonitorChannel} = Ptr{MonitorChannel}(C_NULL),
+                        sym_re::Ptr{Float64} = Ptr{Float64}(C_NULL), sym_im::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                        sym_wbp::Ptr{Float64} = Ptr{Float64}(C_NULL))
+    check(ctx, ccall((:gat_track_monitor, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Int32, Int32, Int32, Ref{MonitorConfig}, Ptr{Float64}, Ptr{Float64},
+                      Ptr{Float64}, Ptr{Float64}, Ptr{MonitorWindow}, Ptr{Float64}, Ptr{MonitorChannel}, Ptr{Float64}, Ptr{Float64},
+                      Ptr{Float64}),
+                     ctx.handle, acc_re, acc_im, Int64(acc_block_stride), Int32(num_blocks), Int32(num_channels), Int32(num_ants), Ref(cfg),
+                     w_re, w_im, prompt_re, prompt_im, windows, energy, channels, sym_re, sym_im, sym_wbp))
+end
+# the same rule on host memory, the bit-exact reference of the device call: acc [M, L, K, B] contiguous; returns
+# (windows [NW, K], energy [Pd, K], channels [K], sym_re, sym_im, sym_wbp [floor(B / Pd), K])
+function track_monitor_host(acc_re::Array{Float32,4}, acc_im::Array{Float32,4}, cfg::MonitorConfig)
+    M, L, K, B = size(acc_re)
+    Pd, W = Int(cfg.symbol_blocks), Int(cfg.window_blocks)
+    windows = Matrix{MonitorWindow}(undef, cld(B, W), K)
+    energy = Matrix{Float64}(undef, Pd, K)
+    channels = Vector{MonitorChannel}(undef, K)
+    sym_re, sym_im, sym_wbp = zeros(Float64, B ÷ Pd, K), zeros(Float64, B ÷ Pd, K), zeros(Float64, B ÷ Pd, K)
+    rc = ccall((:gat_track_monitor_host, libgat), Int32,
+               (Ptr{Cfloat}, Ptr{Cfloat}, Int64, Int32, Int32, Int32, Ref{MonitorConfig}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Ptr{MonitorWindow}, Ptr{Float64}, Ptr{MonitorChannel}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+               acc_re, acc_im, Int64(M * L * K), Int32(B), Int32(K), Int32(M), Ref(cfg), C_NULL, C_NULL, C_NULL, C_NULL, windows, energy,
+               channels, sym_re, sym_im, sym_wbp)
+    rc == GAT_OK || throw(GatError(rc, "gat_track_monitor_host"))
+    windows, energy, channels, sym_re, sym_im, sym_wbp
+end
+# what track_monitor! would do with the call, without a device
+function track_monitor_plan(acc_block_stride::Integer, num_blocks::Integer, num_channels::Integer, num_ants::Integer, cfg::MonitorConfig;
+                            own_prompts::Bool = true, want_symbols::Bool = true)
+    plan = Ref(MonitorPlan(UInt32(sizeof(MonitorPlan)), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_track_monitor_plan, libgat), Int32,
+               (Int64, Int32, Int32, Int32, Ref{MonitorConfig}, Int32, Int32, Ref{MonitorPlan}),
+               Int64(acc_block_stride), Int32(num_blocks), Int32(num_channels), Int32(num_ants), Ref(cfg), Int32(own_prompts),
+               Int32(want_symbols), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_track_monitor_plan"))
+    plan[]
+end
+
 end # module
