@@ -24,7 +24,7 @@ from .array import beamform_desc
 from .context import Context, get_context
 from .gen_signal import make_params
 from .signals import GNSSSystem, get_code_frequency
-from .tracking import _signal_desc
+from .streams import input_desc, ref, vp
 
 
 @dataclass
@@ -52,13 +52,7 @@ class AcquisitionResult:
 def _as_desc(signal, num_samples: int, num_blocks: int, block_stride: int):
     """``signal``: planar (re, im) float32 tensors [M, Ntot], or one interleaved tensor [M, Ntot, 2] of float32, int16 or
     int8 pairs, on the device; or a ready gat_signal_desc (then ``num_samples`` etc. are taken from it)."""
-    if isinstance(signal, _lib.SignalDesc):
-        return signal
-    re, im = (signal if isinstance(signal, (tuple, list)) else (signal, None))
-    ntot = re.shape[-1] if im is not None else re.shape[-2]
-    if (num_blocks - 1) * block_stride + num_samples > ntot:
-        raise ValueError("signal shorter than (num_blocks - 1) * block_stride + num_samples")
-    return _signal_desc(re, im, num_samples, block_stride=block_stride)
+    return signal if isinstance(signal, _lib.SignalDesc) else input_desc(signal, num_samples, num_blocks, 0, block_stride)[1]
 
 
 def acquire(system: GNSSSystem, signal, sampling_frequency: float, prns=range(32), *, num_samples: int | None = None,
@@ -132,8 +126,7 @@ def acquire(system: GNSSSystem, signal, sampling_frequency: float, prns=range(32
     res = np.zeros(max(P, 1), dtype=_lib.ACQ_RESULT_DTYPE)
     name = "gat_acquire_fft" if method == "fft" else "gat_acquire"
     rc = getattr(ctx.lib, name)(ctx._h, C.byref(desc), int(num_blocks), prn_arr.ctypes.data_as(C.POINTER(C.c_int32)), P, fs,
-                                C.byref(cfg), C.c_void_p(power.data_ptr() if power is not None else None),
-                                C.c_void_p(res.ctypes.data))
+                                C.byref(cfg), vp(power), C.c_void_p(res.ctypes.data))
     ctx.check(rc, name)
     out = []
     for p in range(P):
@@ -154,9 +147,8 @@ def acquire_fft_plan(desc: _lib.SignalDesc, num_blocks: int, num_prns: int, samp
     options as ``Context.set_option`` would set them.  Raises ``GatError`` with the refusal the call would get."""
     plan = _lib.AcqFftPlan()
     plan.struct_size = C.sizeof(_lib.AcqFftPlan)
-    rc = _lib.load().gat_acquire_fft_plan(C.byref(desc) if desc is not None else None, int(num_blocks), int(num_prns), float(sampling_frequency),
-                                          C.byref(config) if config is not None else None, int(fft_log2), int(doppler_batch), int(unit_batch),
-                                          int(num_cus), int(bool(own_power)), C.byref(plan))
+    rc = _lib.load().gat_acquire_fft_plan(ref(desc), int(num_blocks), int(num_prns), float(sampling_frequency), ref(config), int(fft_log2),
+                                          int(doppler_batch), int(unit_batch), int(num_cus), int(bool(own_power)), C.byref(plan))
     if rc != 0:
         raise _lib.GatError(rc, "gat_acquire_fft_plan")
     return {n: int(getattr(plan, n)) for n, _ in plan._fields_ if n != "struct_size"}
@@ -164,7 +156,7 @@ def acquire_fft_plan(desc: _lib.SignalDesc, num_blocks: int, num_prns: int, samp
 
 def acquire_fft_host(desc: _lib.SignalDesc, num_blocks: int, codes: np.ndarray, prns, sampling_frequency: float, config: _lib.AcqConfig,
                      fft_log2: int, unit_groups: int = 1) -> np.ndarray:
-    """``gat_acquire_fft_host``: the FFT search's grid [P, D, J] on the host over a descriptor of HOST memory (``frontend.host_desc``),
+    """``gat_acquire_fft_host``: the FFT search's grid [P, D, J] on the host over a descriptor of HOST memory (``streams.host_desc``),
     bit for bit the device's for the same ``fft_log2`` and ``unit_groups``.  ``codes``: int8 [rows, Lc]; ``prns``: rows."""
     tab = np.ascontiguousarray(codes, dtype=np.int8)
     if tab.ndim != 2:

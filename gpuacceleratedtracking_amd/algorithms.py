@@ -17,10 +17,10 @@ import torch
 
 from . import _lib
 from .context import get_context
-from .correlator import _as_int
+from .correlator import as_int
 from .gen_signal import make_params
 from .signals import GNSSSystem
-from .tracking import _signal_desc
+from .streams import signal_desc
 
 
 class _Selector:
@@ -161,9 +161,9 @@ def kernel_algorithm(*args):
         raise ValueError("code_length does not match the code table")
     ctx = get_context(signal_re.device)
     ctx.set_codes(table)
-    M = _as_int(num_ants)
+    M = as_int(num_ants)
     sh = np.ascontiguousarray(shifts, dtype=np.int32)
-    desc = _signal_desc(signal_re, signal_im, int(num_samples))
+    desc = signal_desc(signal_re, signal_im, int(num_samples))
     if desc.num_ants != M:
         raise ValueError("num_ants does not match the signal")
     prm = make_params(int(prn) - 1, code_frequency, carrier_frequency, start_code_phase, carrier_phase, shape=(1, 1))

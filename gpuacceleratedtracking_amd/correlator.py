@@ -28,7 +28,7 @@ class NumAccumulators:
         return self.value
 
 
-def _as_int(x) -> int:
+def as_int(x) -> int:
     return int(getattr(x, "value", x))
 
 
@@ -40,8 +40,8 @@ class EarlyPromptLateCorrelator:
     ``accumulators`` copies them to the host (synchronising)."""
 
     def __init__(self, num_ants=NumAnts(1), num_accumulators=NumAccumulators(3), _re=None, _im=None):
-        self.num_ants = _as_int(num_ants)
-        self.num_accumulators = _as_int(num_accumulators)
+        self.num_ants = as_int(num_ants)
+        self.num_accumulators = as_int(num_accumulators)
         if self.num_ants < 1 or self.num_accumulators < 1:
             raise ValueError("num_ants and num_accumulators must be positive")
         self._re = _re  # torch float32 [L, M] (device) or None

@@ -22,8 +22,8 @@ import torch
 
 from . import _lib
 from .context import Context, get_context
-from .frontend import _input_desc, host_desc  # noqa: F401
-from .tracking import _signal_desc
+from .streams import addr, alloc_stream, input_desc, keep_alive, output_desc, overlap_save_blocks, ref, stream_views, vp
+from .streams import host_desc  # noqa: F401  (the name the host twin's docstring points to)
 
 
 # ---- tap design (numpy float64) ------------------------------------------------------------------------------------------------
@@ -82,15 +82,8 @@ def num_outputs(num_samples: int, num_taps: int, decimation: int = 1) -> int:
 
 
 def _alloc_out(M: int, Q: int, nb: int, interleaved: bool, device):
-    """Zeroed float32 output with every block start padded to 16 bytes; returns (tensor(s), descriptor)."""
-    vs = 2 if interleaved else 4
-    ostride = (Q + vs - 1) // vs * vs
-    ld = nb * ostride
-    if interleaved:
-        out = torch.zeros((M, ld, 2), dtype=torch.float32, device=device)
-        return out, _lib.SignalDesc(out.data_ptr(), None, _lib.GAT_LAYOUT_INTERLEAVED, M, Q, ld, ostride, 0)
-    out = (torch.zeros((M, ld), dtype=torch.float32, device=device), torch.zeros((M, ld), dtype=torch.float32, device=device))
-    return out, _lib.SignalDesc(out[0].data_ptr(), out[1].data_ptr(), _lib.GAT_LAYOUT_PLANAR, M, Q, ld, ostride, 0)
+    """``alloc_stream`` for a float32 output, in the argument order the tests call it with."""
+    return alloc_stream(M, Q, nb, device, planar=not interleaved)
 
 
 def filter_samples(signal, taps, num_samples: int, num_blocks: int = 1, decimation: int = 1, nco_step: float = 0.0, nco_phase: float = 0.0,
@@ -98,14 +91,14 @@ def filter_samples(signal, taps, num_samples: int, num_blocks: int = 1, decimati
                    out_block_stride: int | None = None):
     """``y[q] = exp(-j 2 pi (P step + phase)) sum_t taps[t] x[q D + T - 1 - t]`` for every block of ``num_samples`` input samples
     (``P``: the newest sample's position in the stream, ``start`` excluded), ``Q = (num_samples - T) / D + 1`` outputs a block.
-    ``signal`` as ``spatial_covariance`` takes it (any of the four layouts); ``taps`` real or complex ``[T]``, narrowed to float32.
+    ``signal`` as ``streams.input_desc`` takes it (any of the four layouts); ``taps`` real or complex ``[T]``, narrowed to float32.
     Returns ``(tensor(s), desc)``: a float32 ``(re, im)`` pair ``[M, Ntot]`` or, with ``interleaved=True``, one tensor ``[M, Ntot,
     2]``, and its descriptor (it points into the tensor: keep both), which ``acquire``, ``spatial_covariance``,
     ``beamform_samples``, ``sample_stats`` / ``condition_samples`` and the correlators take as it is.  Allocated here, block b
     starts ``b * stride`` outputs in with ``stride`` = Q rounded up to 16 bytes (what lies between blocks is zero); a caller's
     ``out`` (with ``out_block_stride``, default Q) is described as it is."""
     g_re, g_im = _tap_planes(taps)
-    re, desc = _input_desc(signal, num_samples, num_blocks, start, block_stride)
+    re, desc = input_desc(signal, num_samples, num_blocks, start, block_stride)
     nb, N, M, T, D = int(num_blocks), int(num_samples), int(desc.num_ants), g_re.size, int(decimation)
     if D < 1 or N < T:
         raise ValueError("decimation must be positive and a block no shorter than the filter")
@@ -113,15 +106,12 @@ def filter_samples(signal, taps, num_samples: int, num_blocks: int = 1, decimati
     ctx = ctx if ctx is not None else get_context(re.device)
     t_re, t_im = torch.from_numpy(g_re).to(re.device), torch.from_numpy(g_im).to(re.device)
     if out is None:
-        out, odesc = _alloc_out(M, Q, nb, interleaved, re.device)
+        out, odesc = alloc_stream(M, Q, nb, re.device, planar=not interleaved)
     else:
-        o_re, o_im = out if isinstance(out, (tuple, list)) else (out, None)
-        odesc = _signal_desc(o_re, o_im, Q, block_stride=Q if out_block_stride is None else int(out_block_stride))
+        odesc = output_desc(out, Q, out_block_stride)
     cfg = _config(T, D, nco_step, nco_phase)
-    ctx.check(ctx.lib.gat_filter_samples(ctx._h, C.byref(desc), nb, C.c_void_p(t_re.data_ptr()), C.c_void_p(t_im.data_ptr()), C.byref(cfg),
-                                         C.byref(odesc)), "gat_filter_samples")
-    odesc._keep = (t_re, t_im)  # the kernel reads the taps after this call returns
-    return out, odesc
+    ctx.check(ctx.lib.gat_filter_samples(ctx._h, C.byref(desc), nb, vp(t_re), vp(t_im), C.byref(cfg), C.byref(odesc)), "gat_filter_samples")
+    return out, keep_alive(odesc, t_re, t_im)
 
 
 def filter_samples_host(desc: _lib.SignalDesc, num_blocks: int, taps, out_desc: _lib.SignalDesc, decimation: int = 1, nco_step: float = 0.0,
@@ -137,22 +127,16 @@ def filter_samples_host(desc: _lib.SignalDesc, num_blocks: int, taps, out_desc: 
         g_re, g_im = _tap_planes(taps)
     T = g_re.size if g_re is not None else (g_im.size if g_im is not None else 1)
     cfg = config if config is not None else _config(T, decimation, nco_step, nco_phase)
-    return int(_lib.load().gat_filter_samples_host(C.byref(desc) if desc is not None else None, int(num_blocks),
-                                                   g_re.ctypes.data if g_re is not None else None, g_im.ctypes.data if g_im is not None else None,
-                                                   C.byref(cfg), C.byref(out_desc) if out_desc is not None else None))
+    return int(_lib.load().gat_filter_samples_host(ref(desc), int(num_blocks), addr(g_re), addr(g_im), C.byref(cfg), ref(out_desc)))
 
 
 def stream_blocks(total_samples: int, num_taps: int, decimation: int, num_blocks: int = 1):
     """Overlap-save geometry of a contiguous stream of ``total_samples``: ``(N, in_stride, Q, B, outputs)`` -- B blocks of N = Q D +
     T - 1 input samples every Q D samples give Q outputs each, ``outputs = B Q`` in all (the stream's own (total - T) / D + 1,
     rounded down to a multiple of B)."""
-    T, D, B = int(num_taps), int(decimation), int(num_blocks)
-    if B < 1 or int(total_samples) < T:
+    if int(num_blocks) < 1 or int(total_samples) < int(num_taps):
         raise ValueError("num_blocks must be positive and the stream no shorter than the filter")
-    Q = num_outputs(total_samples, T, D) // B
-    if Q < 1:
-        raise ValueError("more blocks than outputs")
-    return Q * D + T - 1, Q * D, Q, B, B * Q
+    return overlap_save_blocks(total_samples, num_taps, decimation, num_blocks)
 
 
 def filter_stream(signal, taps, total_samples: int, decimation: int = 1, nco_step: float = 0.0, nco_phase: float = 0.0, num_blocks: int = 1,
@@ -162,14 +146,9 @@ def filter_stream(signal, taps, total_samples: int, decimation: int = 1, nco_ste
     on ``num_blocks``.  Returns ``(tensor(s), desc)``; the descriptor is one block of all the outputs."""
     g_re, _ = _tap_planes(taps)
     N, stride, Q, B, total_out = stream_blocks(total_samples, g_re.size, decimation, num_blocks)
-    re, desc = _input_desc(signal, N, B, start, stride)
+    re, desc = input_desc(signal, N, B, start, stride)
     M = int(desc.num_ants)
-    # (rows padded to 16 bytes, so that an aligned input runs the tiled kernel; the tensors returned are views of total_out samples)
-    if interleaved:
-        out = torch.zeros((M, (total_out + 1) // 2 * 2, 2), dtype=torch.float32, device=re.device)[:, :total_out]
-    else:
-        ld = (total_out + 3) // 4 * 4
-        out = tuple(torch.zeros((M, ld), dtype=torch.float32, device=re.device)[:, :total_out] for _ in range(2))
+    out = stream_views(alloc_stream(M, total_out, 1, re.device, planar=not interleaved)[0], total_out)
     _, odesc = filter_samples(signal, taps, N, B, decimation, nco_step, nco_phase, start, stride, interleaved, out, ctx, out_block_stride=Q)
     odesc.num_samples, odesc.block_stride = total_out, total_out
     return out, odesc

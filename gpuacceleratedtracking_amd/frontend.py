@@ -19,14 +19,8 @@ import torch
 from . import _lib
 from ._lib import COND_PARAMS_DTYPE, GAT_COND_BLANK_ALL_ANTS, SAMPLE_STATS_DTYPE  # noqa: F401
 from .context import Context, get_context
-from .tracking import _signal_desc
-
-_OUT_LAYOUT = {torch.int8: _lib.GAT_LAYOUT_INTERLEAVED_I8, torch.int16: _lib.GAT_LAYOUT_INTERLEAVED_I16,
-               torch.float32: _lib.GAT_LAYOUT_INTERLEAVED}
-
-
-def _vp(t: torch.Tensor | None):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from .streams import addr, alloc_stream, input_desc, keep_alive, output_desc, ref, vp
+from .streams import host_desc  # noqa: F401  (the name the host twins' docstrings point to)
 
 
 class SampleStats:
@@ -62,26 +56,14 @@ def _records(params, M: int, device) -> torch.Tensor:
     return t
 
 
-def _input_desc(signal, num_samples: int, num_blocks: int, start: int, block_stride: int | None):
-    re, im = signal if isinstance(signal, (tuple, list)) else (signal, None)
-    nb, N = int(num_blocks), int(num_samples)
-    if nb < 1 or N < 1:
-        raise ValueError("num_blocks and num_samples must be positive")
-    stride = N if block_stride is None else int(block_stride)
-    ntot = re.shape[-2] if im is None else re.shape[-1]
-    if stride < 0 or start + (nb - 1) * stride + N > ntot:
-        raise ValueError("signal shorter than start + (num_blocks - 1) * block_stride + num_samples")
-    return re, _signal_desc(re, im, N, start=int(start), block_stride=stride)
-
-
 def sample_stats(signal, num_samples: int, num_blocks: int = 1, blocks_per_estimate: int | None = None, params=None,
                  blank_all: bool = False, ctx: Context | None = None, start: int = 0, block_stride: int | None = None,
                  out: SampleStats | None = None) -> SampleStats:
     """Level statistics per (estimate, antenna) over the samples the blanking rule keeps: counts, ``sum x``, ``sum |x|^2`` and
     the largest component, ``E = ceil(num_blocks / blocks_per_estimate)`` estimates (default: one over all blocks).  ``signal``
-    as ``spatial_covariance`` takes it.  ``params``: records ``[M, 4]`` of which only the threshold is read, or None (keep every
+    as ``streams.input_desc`` takes it.  ``params``: records ``[M, 4]`` of which only the threshold is read, or None (keep every
     sample).  The same bits on every call; FP64 sums.  ``out``: an earlier result to write into (no allocation)."""
-    re, desc = _input_desc(signal, num_samples, num_blocks, start, block_stride)
+    re, desc = input_desc(signal, num_samples, num_blocks, start, block_stride)
     nb = int(num_blocks)
     bpe = nb if blocks_per_estimate is None else int(blocks_per_estimate)
     if bpe < 1:
@@ -94,9 +76,8 @@ def sample_stats(signal, num_samples: int, num_blocks: int = 1, blocks_per_estim
     elif out.shape != (E, M):
         raise ValueError("out has another shape")
     flags = GAT_COND_BLANK_ALL_ANTS if blank_all else 0
-    ctx.check(ctx.lib.gat_sample_stats(ctx._h, C.byref(desc), nb, bpe, _vp(prm), flags, _vp(out.raw)), "gat_sample_stats")
-    out._keep = prm  # the kernel reads it after this call returns
-    return out
+    ctx.check(ctx.lib.gat_sample_stats(ctx._h, C.byref(desc), nb, bpe, vp(prm), flags, vp(out.raw)), "gat_sample_stats")
+    return keep_alive(out, prm)
 
 
 def _agc_config(target_rms: float, blank_factor: float, remove_dc: bool) -> _lib.AgcConfig:
@@ -118,7 +99,7 @@ def agc_params(stats: SampleStats, target_rms: float, blank_factor: float = 0.0,
     elif tuple(out.shape) != (M, 4) or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError("out must be a contiguous float32 [M, 4]")
     cfg = _agc_config(target_rms, blank_factor, remove_dc)
-    ctx.check(ctx.lib.gat_agc_update(ctx._h, _vp(stats.raw), M, C.byref(cfg), _vp(out)), "gat_agc_update")
+    ctx.check(ctx.lib.gat_agc_update(ctx._h, vp(stats.raw), M, C.byref(cfg), vp(out)), "gat_agc_update")
     return out
 
 
@@ -127,30 +108,10 @@ def agc_params_host(stats: np.ndarray, target_rms: float, blank_factor: float = 
     st = np.ascontiguousarray(stats, dtype=SAMPLE_STATS_DTYPE).reshape(-1)
     out = np.zeros(st.size, dtype=COND_PARAMS_DTYPE)
     cfg = _agc_config(target_rms, blank_factor, remove_dc)
-    rc = _lib.load().gat_agc_update_host(st.ctypes.data, st.size, C.byref(cfg), out.ctypes.data)
+    rc = _lib.load().gat_agc_update_host(addr(st), st.size, C.byref(cfg), addr(out))
     if rc != _lib.GAT_OK:
         raise _lib.GatError(rc, "gat_agc_update_host")
     return out
-
-
-def _alloc_out(M: int, N: int, nb: int, out_dtype, planar: bool, device):
-    """Zeroed output with every block start padded to 16 bytes; returns (tensor(s), descriptor)."""
-    if planar:
-        if out_dtype != torch.float32:
-            raise ValueError("a planar output is float32")
-        layout = _lib.GAT_LAYOUT_PLANAR
-    elif out_dtype in _OUT_LAYOUT:
-        layout = _OUT_LAYOUT[out_dtype]
-    else:
-        raise ValueError("out_dtype must be torch.int8, torch.int16 or torch.float32")
-    vs = 16 // (4 if planar else _lib.SAMPLE_BYTES[layout])
-    ostride = (N + vs - 1) // vs * vs
-    ld = nb * ostride
-    if planar:
-        out = (torch.zeros((M, ld), dtype=torch.float32, device=device), torch.zeros((M, ld), dtype=torch.float32, device=device))
-        return out, _lib.SignalDesc(out[0].data_ptr(), out[1].data_ptr(), layout, M, N, ld, ostride, 0)
-    out = torch.zeros((M, ld, 2), dtype=out_dtype, device=device)
-    return out, _lib.SignalDesc(out.data_ptr(), None, layout, M, N, ld, ostride, 0)
 
 
 def condition_samples(signal, params, num_samples: int, num_blocks: int = 1, out_dtype=torch.int8, blank_all: bool = False, out=None,
@@ -164,27 +125,19 @@ def condition_samples(signal, params, num_samples: int, num_blocks: int = 1, out
     to ``counts`` when one is passed.  Allocated here, block b starts ``b * stride`` samples in with ``stride`` = ``num_samples``
     rounded up to 16 bytes (what lies between blocks is zero); a caller's ``out`` (with ``out_block_stride``, default
     ``num_samples``) is described as it is -- the input itself for in-place work."""
-    re, desc = _input_desc(signal, num_samples, num_blocks, start, block_stride)
+    re, desc = input_desc(signal, num_samples, num_blocks, start, block_stride)
     nb, N, M = int(num_blocks), int(num_samples), int(desc.num_ants)
     ctx = ctx if ctx is not None else get_context(re.device)
     prm = _records(params, M, re.device)
     if out is None:
-        out, odesc = _alloc_out(M, N, nb, out_dtype, planar, re.device)
+        out, odesc = alloc_stream(M, N, nb, re.device, out_dtype, planar)
     else:
-        o_re, o_im = out if isinstance(out, (tuple, list)) else (out, None)
-        odesc = _signal_desc(o_re, o_im, N, block_stride=N if out_block_stride is None else int(out_block_stride))
+        odesc = output_desc(out, N, out_block_stride)
     if counts is None:
         counts = torch.zeros((M, 2), dtype=torch.int64, device=re.device)
     flags = GAT_COND_BLANK_ALL_ANTS if blank_all else 0
-    ctx.check(ctx.lib.gat_condition_samples(ctx._h, C.byref(desc), nb, _vp(prm), flags, C.byref(odesc), _vp(counts)), "gat_condition_samples")
-    odesc._keep = prm  # the kernel reads the records after this call returns
-    return out, odesc, counts
-
-
-def _host_desc(arr, im, layout: int, M: int, N: int, ant_stride: int, block_stride: int, offset: int = 0) -> _lib.SignalDesc:
-    step = 4 if layout == _lib.GAT_LAYOUT_PLANAR else _lib.SAMPLE_BYTES.get(layout, 1)  # (an unknown layout is the callee's to refuse)
-    return _lib.SignalDesc(arr.ctypes.data + offset * step, None if im is None else im.ctypes.data + offset * step, layout, M, N,
-                           ant_stride, block_stride, 0)
+    ctx.check(ctx.lib.gat_condition_samples(ctx._h, C.byref(desc), nb, vp(prm), flags, C.byref(odesc), vp(counts)), "gat_condition_samples")
+    return out, keep_alive(odesc, prm), counts
 
 
 def condition_samples_host(desc: _lib.SignalDesc, num_blocks: int, params: np.ndarray, out_desc: _lib.SignalDesc, blank_all: bool = False,
@@ -195,13 +148,7 @@ def condition_samples_host(desc: _lib.SignalDesc, num_blocks: int, params: np.nd
     if counts is not None and (counts.dtype != np.uint64 or not counts.flags.c_contiguous):
         raise ValueError("counts must be a contiguous uint64 [M, 2]")
     flags = GAT_COND_BLANK_ALL_ANTS if blank_all is True else int(blank_all)
-    return int(_lib.load().gat_condition_samples_host(C.byref(desc) if desc is not None else None, int(num_blocks),
-                                                      prm.ctypes.data if prm is not None else None, flags,
-                                                      C.byref(out_desc) if out_desc is not None else None,
-                                                      counts.ctypes.data if counts is not None else None))
-
-
-host_desc = _host_desc
+    return int(_lib.load().gat_condition_samples_host(ref(desc), int(num_blocks), addr(prm), flags, ref(out_desc), addr(counts)))
 
 
 def requantize(signal, num_samples: int, num_blocks: int = 1, out_dtype=torch.int8, target_rms: float = 16.0, blank_factor: float = 0.0,

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from .context import get_context
-from .correlator import _as_int
+from .correlator import as_int
 from .signals import GNSSSystem, get_code_frequency
 
 
@@ -40,7 +40,7 @@ class StructSignal:
 def gen_blank_signal(system: GNSSSystem, num_samples: int, num_ants=1, prns=None, device=None) -> StructSignal:
     """``gen_blank_signal`` (src/gen_signal.jl:177-184): zero-filled planar signal."""
     ctx = get_context(device)
-    m = _as_int(num_ants)
+    m = as_int(num_ants)
     shape = (m, num_samples) if prns is None else (len(prns), m, num_samples)
     return StructSignal(torch.zeros(shape, dtype=torch.float32, device=ctx.device),
                         torch.zeros(shape, dtype=torch.float32, device=ctx.device))
@@ -83,7 +83,7 @@ def gen_signal_stream(system: GNSSSystem, params: np.ndarray, sampling_frequency
     if params.ndim != 2:
         raise ValueError("params must be [B, K]")
     B, K = params.shape
-    m = _as_int(num_ants)
+    m = as_int(num_ants)
     dparams = ctx.params_to_device(params)
     row = B * num_samples + int(ant_pad)
     if layout == _lib.GAT_LAYOUT_PLANAR:
@@ -107,7 +107,7 @@ def gen_signal(system: GNSSSystem, prn, carrier_frequency: float, num_samples: i
     a list of PRNs yields one signal per satellite, shape [K, M, N] (src/gen_signal.jl:27-51,
     :155-175).  Returns ``(StructSignal, sampling_frequency)``."""
     fs = num_samples / duration  # src/gen_signal.jl:11
-    m = _as_int(num_ants)
+    m = as_int(num_ants)
     prns = list(prn) if isinstance(prn, (list, tuple, np.ndarray)) else None
     fc = get_code_frequency(system)
     if prns is None:

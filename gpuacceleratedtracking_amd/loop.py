@@ -16,7 +16,7 @@ from . import _lib
 from .context import Context, get_context
 from .gen_signal import make_params
 from .signals import GNSSSystem, get_code_frequency
-from .tracking import _signal_desc
+from .streams import input_desc, signal_desc
 
 
 class TrackingLoop:
@@ -89,7 +89,7 @@ class TrackingLoop:
         """Correlate the block starting at sample ``start`` of the given signal with the current
         parameters, then update them on the device.  Nothing is synchronised."""
         self.ctx.set_codes(self.system.codes)  # the context may have been bound to another system's table meanwhile
-        desc = _signal_desc(re, im, self.N, start=start)
+        desc = signal_desc(re, im, self.N, start=start)
         cur, nxt = self._params[self._cur], self._params[1 - self._cur]
         self.ctx.downconvert_and_correlate(desc, cur, 1, self.K, self.shifts, self.fs, self.out_re, self.out_im)
         args = (self.ctx._h, C.c_void_p(self.out_re.data_ptr()), C.c_void_p(self.out_im.data_ptr()), self.K, self.M,
@@ -111,10 +111,7 @@ class TrackingLoop:
         instantiated hipGraph (the context must be bound to a non-default stream)."""
         nb = int(num_blocks)
         self.ctx.set_codes(self.system.codes)  # the context may have been bound to another system's table meanwhile
-        desc = _signal_desc(re, im, self.N, start=start)
-        ntot = re.shape[-2] if im is None else re.shape[-1]
-        if start + nb * self.N > ntot:
-            raise ValueError("signal shorter than start + num_blocks * num_samples")
+        _, desc = input_desc((re, im), self.N, nb, start)
         if keep:
             if out is not None:
                 acc_re, acc_im = out
@@ -187,7 +184,7 @@ class ResidentTrackingLoop:
         self._next = self._cur.copy()
         self._state = dev_loop.state().copy()
         self._signal = (re, im)  # kept alive: the resident kernel reads it
-        desc = _signal_desc(re, im, self.N, start=0)
+        desc = signal_desc(re, im, self.N, start=0)
         self._samples = int(re.shape[-2] if im is None else re.shape[-1])  # per antenna: every block has to end inside
         torch.cuda.current_stream(self.ctx.device).synchronize()  # the signal is on the device before the first ring
         self.resident = self.ctx.open_resident(desc, self.K, self.shifts, self.fs, buffer_samples=self._samples, **resident_config)

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from .context import Context, get_context
+from .streams import addr, keep_alive, vp
 
 NH10 = "0000110101"
 NH20 = "00000100110101001110"
@@ -203,14 +204,11 @@ def monitor_accumulators(acc_re: torch.Tensor, acc_im: torch.Tensor, *, block_se
     if keep_prompts:
         raw["prompt_re"] = torch.empty((K, B), dtype=torch.float64, device=dev)
         raw["prompt_im"] = torch.empty((K, B), dtype=torch.float64, device=dev)
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     rc = ctx.lib.gat_track_monitor(ctx._h, vp(acc_re), vp(acc_im), stride, B, K, M, C.byref(cfg), vp(w_re), vp(w_im),
                                    vp(raw.get("prompt_re")), vp(raw.get("prompt_im")), vp(raw["windows"]), vp(raw["energy"]),
                                    vp(raw["channels"]), vp(raw["sym_re"]), vp(raw["sym_im"]), vp(raw["sym_wbp"]))
     ctx.check(rc, "gat_track_monitor")
-    mon = TrackMonitor(raw, block_seconds, Pd, min_sync_ratio, ctx)
-    mon._keep = (acc_re, acc_im, w_re, w_im)  # the kernels read them after this call returns
-    return mon
+    return keep_alive(TrackMonitor(raw, block_seconds, Pd, min_sync_ratio, ctx), acc_re, acc_im, w_re, w_im)
 
 
 def monitor_accumulators_host(acc_re, acc_im, *, block_seconds: float, prompt_index: int, window_blocks: int = 20, overlay=None,
@@ -231,10 +229,9 @@ def monitor_accumulators_host(acc_re, acc_im, *, block_seconds: float, prompt_in
         raw[name] = np.zeros((K, cap))
     if keep_prompts:
         raw["prompt_re"], raw["prompt_im"] = np.zeros((K, B)), np.zeros((K, B))
-    vp = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-    rc = _lib.load().gat_track_monitor_host(vp(acc_re), vp(acc_im), stride, B, K, M, C.byref(cfg), vp(w_re), vp(w_im),
-                                            vp(raw.get("prompt_re")), vp(raw.get("prompt_im")), vp(raw["windows"]), vp(raw["energy"]),
-                                            vp(raw["channels"]), vp(raw["sym_re"]), vp(raw["sym_im"]), vp(raw["sym_wbp"]))
+    rc = _lib.load().gat_track_monitor_host(addr(acc_re), addr(acc_im), stride, B, K, M, C.byref(cfg), addr(w_re), addr(w_im),
+                                            addr(raw.get("prompt_re")), addr(raw.get("prompt_im")), addr(raw["windows"]), addr(raw["energy"]),
+                                            addr(raw["channels"]), addr(raw["sym_re"]), addr(raw["sym_im"]), addr(raw["sym_wbp"]))
     if rc != 0:
         raise _lib.GatError(rc, "gat_track_monitor_host")
     return TrackMonitor(raw, block_seconds, Pd, min_sync_ratio)

@@ -20,11 +20,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .array import _planes, _vp, beamformer_weights
+from .array import beamformer_weights
 from .context import Context, get_context
-from .filtering import _alloc_out
-from .frontend import _input_desc, host_desc  # noqa: F401
-from .tracking import _signal_desc
+from .streams import addr, alloc_stream, input_desc, keep_alive, output_desc, overlap_save_blocks, planes, ref, stream_views, vp
+from .streams import host_desc  # noqa: F401  (the name the host twin's docstring points to)
 
 
 def spacetime_delay(num_taps: int, ref_tap: int) -> int:
@@ -55,10 +54,10 @@ def spacetime_steering(a, num_taps: int, ref_tap: int) -> torch.Tensor:
 def spacetime_covariance(signal, num_samples: int, num_blocks: int = 1, num_taps: int = 1, blocks_per_estimate: int | None = None,
                          start: int = 0, block_stride: int | None = None, ctx: Context | None = None) -> torch.Tensor:
     """``R_e[q, q'] = sum_{b in e} sum_{n = T-1}^{N-1} z_q[n] conj(z_q'[n])`` as complex64 ``[E, Q, Q]``, ``Q = M num_taps``: the
-    covariance method -- every entry over the same ``N - T + 1`` snapshots, none reading outside its block.  ``signal`` and the
-    estimate grouping as ``spatial_covariance`` takes them; ``num_taps = 1`` IS ``spatial_covariance`` (the same bits).  Exactly
-    Hermitian, and the same bits on every call."""
-    re, desc = _input_desc(signal, num_samples, num_blocks, start, block_stride)
+    covariance method -- every entry over the same ``N - T + 1`` snapshots, none reading outside its block.  ``signal`` as
+    ``streams.input_desc`` takes it, the estimate grouping as in ``spatial_covariance``; ``num_taps = 1`` IS
+    ``spatial_covariance`` (the same bits).  Exactly Hermitian, and the same bits on every call."""
+    re, desc = input_desc(signal, num_samples, num_blocks, start, block_stride)
     nb, T = int(num_blocks), int(num_taps)
     bpe = nb if blocks_per_estimate is None else int(blocks_per_estimate)
     if bpe < 1 or T < 1:
@@ -67,7 +66,7 @@ def spacetime_covariance(signal, num_samples: int, num_blocks: int = 1, num_taps
     E, Q = (nb + bpe - 1) // bpe, int(desc.num_ants) * T
     cov_re = torch.empty((E, Q, Q), dtype=torch.float32, device=re.device)
     cov_im = torch.empty_like(cov_re)
-    ctx.check(ctx.lib.gat_spacetime_covariance(ctx._h, C.byref(desc), nb, bpe, T, _vp(cov_re), _vp(cov_im)), "gat_spacetime_covariance")
+    ctx.check(ctx.lib.gat_spacetime_covariance(ctx._h, C.byref(desc), nb, bpe, T, vp(cov_re), vp(cov_im)), "gat_spacetime_covariance")
     return torch.complex(cov_re, cov_im)
 
 
@@ -103,19 +102,19 @@ def _weight_planes(weights, Q: int, device):
     w = w.reshape(1, -1) if w.dim() == 1 else w
     if w.dim() != 2 or int(w.shape[1]) != Q:
         raise ValueError("weights must be [J, num_ants * num_taps] or [num_ants * num_taps]")
-    return _planes(w.to(device), torch.float64), int(w.shape[0])
+    return planes(w.to(device), torch.float64), int(w.shape[0])
 
 
 def spacetime_filter(signal, weights, num_taps: int, num_samples: int, num_blocks: int = 1, start: int = 0, block_stride: int | None = None,
                      interleaved: bool = False, out=None, ctx: Context | None = None, out_block_stride: int | None = None):
     """``y[j, n'] = sum_q conj(w[j, q]) z_q[n' + T - 1]`` for every block of ``num_samples`` input samples, ``N - T + 1`` outputs a
-    block.  ``signal`` as ``spatial_covariance`` takes it; ``weights`` complex ``[J, Q]`` or ``[Q]`` as ``spacetime_weights``
+    block.  ``signal`` as ``streams.input_desc`` takes it; ``weights`` complex ``[J, Q]`` or ``[Q]`` as ``spacetime_weights``
     returns them.  Returns ``(tensor(s), desc)`` as ``filter_samples`` does: a float32 ``(re, im)`` pair ``[J, Ntot]`` or, with
     ``interleaved=True``, one tensor ``[J, Ntot, 2]``, and its descriptor (it points into the tensor: keep both), a J-antenna
     signal for ``acquire``, ``spatial_covariance`` and the correlators.  float32 sums in q order: ``|y - y64| <= (4 Q + 4) 2^-24
     sum_q |w_q| |z_q|``; one tap gives ``beamform_samples``' bits."""
     T = int(num_taps)
-    re, desc = _input_desc(signal, num_samples, num_blocks, start, block_stride)
+    re, desc = input_desc(signal, num_samples, num_blocks, start, block_stride)
     nb, N, M = int(num_blocks), int(num_samples), int(desc.num_ants)
     if T < 1 or N < T:
         raise ValueError("num_taps must be positive and a block no shorter than the tap delay line")
@@ -123,13 +122,11 @@ def spacetime_filter(signal, weights, num_taps: int, num_samples: int, num_block
     No = N - T + 1
     ctx = ctx if ctx is not None else get_context(re.device)
     if out is None:
-        out, odesc = _alloc_out(J, No, nb, interleaved, re.device)
+        out, odesc = alloc_stream(J, No, nb, re.device, planar=not interleaved)
     else:
-        o_re, o_im = out if isinstance(out, (tuple, list)) else (out, None)
-        odesc = _signal_desc(o_re, o_im, No, block_stride=No if out_block_stride is None else int(out_block_stride))
-    ctx.check(ctx.lib.gat_spacetime_filter(ctx._h, C.byref(desc), nb, _vp(w_re), _vp(w_im), T, J, C.byref(odesc)), "gat_spacetime_filter")
-    odesc._keep = (w_re, w_im)  # the kernel reads the weights after this call returns
-    return out, odesc
+        odesc = output_desc(out, No, out_block_stride)
+    ctx.check(ctx.lib.gat_spacetime_filter(ctx._h, C.byref(desc), nb, vp(w_re), vp(w_im), T, J, C.byref(odesc)), "gat_spacetime_filter")
+    return out, keep_alive(odesc, w_re, w_im)
 
 
 def spacetime_filter_host(desc: _lib.SignalDesc, num_blocks: int, weights, num_taps: int, out_desc: _lib.SignalDesc,
@@ -145,24 +142,18 @@ def spacetime_filter_host(desc: _lib.SignalDesc, num_blocks: int, weights, num_t
         w = np.asarray(weights).astype(np.complex128)
         w = w.reshape(1, -1) if w.ndim == 1 else w
         w_re, w_im = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
-    ref = w_re if w_re is not None else w_im
-    J = int(num_beams) if num_beams is not None else (int(ref.shape[0]) if ref is not None and ref.ndim == 2 else 1)
-    return int(_lib.load().gat_spacetime_filter_host(C.byref(desc) if desc is not None else None, int(num_blocks),
-                                                     w_re.ctypes.data if w_re is not None else None, w_im.ctypes.data if w_im is not None else None,
-                                                     int(num_taps), J, C.byref(out_desc) if out_desc is not None else None))
+    plane = w_re if w_re is not None else w_im
+    J = int(num_beams) if num_beams is not None else (int(plane.shape[0]) if plane is not None and plane.ndim == 2 else 1)
+    return int(_lib.load().gat_spacetime_filter_host(ref(desc), int(num_blocks), addr(w_re), addr(w_im), int(num_taps), J, ref(out_desc)))
 
 
 def stream_blocks(total_samples: int, num_taps: int, num_blocks: int = 1):
     """Overlap-save geometry of a contiguous stream of ``total_samples``: ``(N, in_stride, Qout, B, outputs)`` -- B blocks of N =
     Qout + T - 1 input samples every Qout samples give Qout outputs each, ``outputs = B Qout`` in all (the stream's own total - T
     + 1, rounded down to a multiple of B)."""
-    T, B = int(num_taps), int(num_blocks)
-    if B < 1 or T < 1 or int(total_samples) < T:
+    if int(num_blocks) < 1 or int(num_taps) < 1 or int(total_samples) < int(num_taps):
         raise ValueError("num_blocks and num_taps must be positive and the stream no shorter than the tap delay line")
-    Qout = (int(total_samples) - T + 1) // B
-    if Qout < 1:
-        raise ValueError("more blocks than outputs")
-    return Qout + T - 1, Qout, Qout, B, B * Qout
+    return overlap_save_blocks(total_samples, num_taps, 1, num_blocks)
 
 
 def spacetime_stream(signal, weights, num_taps: int, total_samples: int, num_blocks: int = 1, start: int = 0, interleaved: bool = False,
@@ -171,15 +162,10 @@ def spacetime_stream(signal, weights, num_taps: int, total_samples: int, num_blo
     by descriptor: no carry state), written back to back: ONE seamless output of ``num_blocks * Qout`` samples whose bits do not
     depend on ``num_blocks``.  Returns ``(tensor(s), desc)``; the descriptor is one block of all the outputs."""
     N, stride, Qout, B, total_out = stream_blocks(total_samples, num_taps, num_blocks)
-    re, desc = _input_desc(signal, N, B, start, stride)
+    re, desc = input_desc(signal, N, B, start, stride)
     w = torch.as_tensor(weights)
     J = 1 if w.dim() == 1 else int(w.shape[0])
-    # (rows padded to 16 bytes, so that an aligned input runs the tiled kernel; the tensors returned are views of total_out samples)
-    if interleaved:
-        out = torch.zeros((J, (total_out + 1) // 2 * 2, 2), dtype=torch.float32, device=re.device)[:, :total_out]
-    else:
-        ld = (total_out + 3) // 4 * 4
-        out = tuple(torch.zeros((J, ld), dtype=torch.float32, device=re.device)[:, :total_out] for _ in range(2))
+    out = stream_views(alloc_stream(J, total_out, 1, re.device, planar=not interleaved)[0], total_out)
     _, odesc = spacetime_filter(signal, weights, num_taps, N, B, start, stride, interleaved, out, ctx, out_block_stride=Qout)
     odesc.num_samples, odesc.block_stride = total_out, total_out
     return out, odesc

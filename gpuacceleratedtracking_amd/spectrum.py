@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from .context import Context, get_context
 from .filtering import filter_stream, notch_taps
-from .frontend import _input_desc
+from .streams import addr, input_desc, keep_alive, ref, vp
 
 WINDOWS = ("hann", "hamming", "blackman", "rect")
 
@@ -65,25 +65,23 @@ def sample_spectrum(signal, num_bins: int, num_samples: int, num_blocks: int = 1
                     block_stride: int | None = None, ctx: Context | None = None):
     """``power[b, m, f] = sum_s |FFT_F(w x[s H : s H + F])[f]|^2`` for every block of ``num_samples`` samples: float32 ``[B, M, F]``
     in FFT order (bin f is f / F cycles per sample below F / 2 and (f - F) / F above) -- the SUM over the ``S`` segments -- and S.
-    ``signal`` as ``filter_samples`` takes it (any of the four layouts); ``hop`` defaults to F / 2; ``window``: a name of
+    ``signal`` as ``streams.input_desc`` takes it (any of the four layouts); ``hop`` defaults to F / 2; ``window``: a name of
     ``WINDOWS`` or F values."""
     F, H = int(num_bins), _hop(num_bins, hop)
-    re, desc = _input_desc(signal, num_samples, num_blocks, start, block_stride)
+    re, desc = input_desc(signal, num_samples, num_blocks, start, block_stride)
     if int(num_samples) < F or H < 1:
         raise ValueError("a block must hold one segment of num_bins samples, and hop must be positive")
     ctx = ctx if ctx is not None else get_context(re.device)
     w = torch.from_numpy(window_values(window, F)).to(re.device)
     out = torch.empty((int(num_blocks), int(desc.num_ants), F), dtype=torch.float32, device=re.device)
     cfg = _config(F, H)
-    ctx.check(ctx.lib.gat_sample_spectrum(ctx._h, C.byref(desc), int(num_blocks), C.c_void_p(w.data_ptr()), C.byref(cfg), C.c_void_p(out.data_ptr())),
-              "gat_sample_spectrum")
-    out._keep = w  # the kernel reads the window after this call returns
-    return out, num_segments(num_samples, F, H)
+    ctx.check(ctx.lib.gat_sample_spectrum(ctx._h, C.byref(desc), int(num_blocks), vp(w), C.byref(cfg), vp(out)), "gat_sample_spectrum")
+    return keep_alive(out, w), num_segments(num_samples, F, H)
 
 
 def sample_spectrum_host(desc: _lib.SignalDesc, num_blocks: int, window, num_bins: int, hop: int, out: np.ndarray | None,
                          config: _lib.SpectrumConfig | None = None) -> int:
-    """``gat_sample_spectrum_host`` on a descriptor of HOST memory (``frontend.host_desc`` builds one over numpy arrays) into
+    """``gat_sample_spectrum_host`` on a descriptor of HOST memory (``streams.host_desc`` builds one over numpy arrays) into
     ``out``, float32 ``[B, M, F]``.  Returns the status instead of raising: the refusals are part of what the twin is a reference
     of.  ``window``: float32 ``[F]`` or None (a null pointer); ``config`` overrides the one made of ``num_bins`` and ``hop``."""
     if window is not None and (window.dtype != np.float32 or not window.flags.c_contiguous):
@@ -91,9 +89,7 @@ def sample_spectrum_host(desc: _lib.SignalDesc, num_blocks: int, window, num_bin
     if out is not None and (out.dtype != np.float32 or not out.flags.c_contiguous):
         raise ValueError("out must be a contiguous float32 array")
     cfg = config if config is not None else _config(num_bins, hop)
-    return int(_lib.load().gat_sample_spectrum_host(C.byref(desc) if desc is not None else None, int(num_blocks),
-                                                    window.ctypes.data if window is not None else None, C.byref(cfg),
-                                                    out.ctypes.data if out is not None else None))
+    return int(_lib.load().gat_sample_spectrum_host(ref(desc), int(num_blocks), addr(window), C.byref(cfg), addr(out)))
 
 
 def stream_partition(total_samples: int, num_bins: int, hop: int, num_ants: int, units_wanted: int = 2048):
@@ -118,7 +114,7 @@ def spectrum_stream(signal, num_bins: int, total_samples: int, hop: int | None =
     x antennas cover the device; the blocks' float32 sums -- whose bits the rule of gat.h fixes -- are added in float64 in block
     order and divided by the segment count.  The last bits of the mean therefore depend on ``units_wanted``, nothing else does."""
     F, H = int(num_bins), _hop(num_bins, hop)
-    re, desc = _input_desc(signal, total_samples, 1, start, None)
+    re, desc = input_desc(signal, total_samples, 1, start, None)
     S_total, S_block, B, S_rest = stream_partition(total_samples, F, H, int(desc.num_ants), units_wanted)
     blocks, _ = sample_spectrum(signal, F, (S_block - 1) * H + F, B, H, window, start, S_block * H, ctx)
     total = blocks.cpu().numpy().astype(np.float64).sum(axis=0)  # (axis 0 of a C-ordered array: row after row, in block order)
@@ -175,7 +171,7 @@ def auto_notch(signal, total_samples: int, num_bins: int = 1024, num_taps: int =
     psd, _ = spectrum_stream(signal, num_bins, total_samples, hop, "hann", start, ctx)
     tones = find_tones(psd, threshold_db, max_tones, guard_bins, "hann")
     if not tones:
-        _, desc = _input_desc(signal, total_samples, 1, start, None)
+        _, desc = input_desc(signal, total_samples, 1, start, None)
         return signal, desc, tones
     taps = np.ones(1, np.complex128)
     for nu, _ in tones:

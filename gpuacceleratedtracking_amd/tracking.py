@@ -24,51 +24,9 @@ from .context import Context, get_context
 from .correlator import EarlyPromptLateCorrelator
 from .gen_signal import StructSignal, make_params
 from .signals import GNSSSystem, get_code_frequency
+from .streams import signal_desc
 
-
-_DTYPE_LAYOUT = {torch.float32: _lib.GAT_LAYOUT_INTERLEAVED, torch.int16: _lib.GAT_LAYOUT_INTERLEAVED_I16,
-                 torch.int8: _lib.GAT_LAYOUT_INTERLEAVED_I8}
-
-
-def _signal_desc(re: torch.Tensor, im: torch.Tensor | None, num_samples: int, start: int = 0,
-                 block_stride: int | None = None, per_channel: bool = False) -> _lib.SignalDesc:
-    """Describe a planar float32 pair [(K,) M, Ntot] or an interleaved tensor [(K,) M, Ntot, 2] of
-    float32 (ComplexF32), int16 or int8 {re, im} pairs."""
-    il = im is None
-    t = re
-    if not t.is_cuda:
-        raise ValueError("signal must live on the HIP device")
-    if il:
-        if t.dtype not in _DTYPE_LAYOUT:
-            raise ValueError("interleaved signal must be float32, int16 or int8")
-        if t.shape[-1] != 2 or t.stride(-1) != 1 or t.stride(-2) != 2:
-            raise ValueError("interleaved signal must be [..., N, 2] with unit inner strides")
-        dims = t.dim() - 1
-        stride = lambda d: t.stride(d - 1) // 2  # noqa: E731  (in complex samples)
-        ntot = t.shape[-2]
-        layout = _DTYPE_LAYOUT[t.dtype]
-    else:
-        if t.dtype != torch.float32 or im.dtype != torch.float32:
-            raise ValueError("planar signal planes must be float32")
-        if t.stride(-1) != 1 or im.stride() != t.stride() or im.shape != t.shape:
-            raise ValueError("planar signal planes must be sample-contiguous with equal strides")
-        dims = t.dim()
-        stride = lambda d: t.stride(d)  # noqa: E731
-        ntot = t.shape[-1]
-        layout = _lib.GAT_LAYOUT_PLANAR
-    if start < 0 or start + num_samples > ntot:
-        raise ValueError("signal_start_sample/num_samples outside the signal")
-    d = _lib.SignalDesc()
-    off = start * (_lib.SAMPLE_BYTES[layout] if il else 4)
-    d.re = t.data_ptr() + off
-    d.im = None if il else im.data_ptr() + off
-    d.layout = layout
-    d.num_samples = num_samples
-    d.num_ants = t.shape[dims - 2] if dims >= 2 else 1
-    d.ant_stride = stride(-2) if dims >= 2 else ntot
-    d.block_stride = num_samples if block_stride is None else block_stride
-    d.chan_stride = stride(-3) if (per_channel and dims >= 3) else 0
-    return d
+_signal_desc = signal_desc  # the name the tests import
 
 
 def downconvert_and_correlate(system: GNSSSystem, signal: StructSignal, correlator: EarlyPromptLateCorrelator,
@@ -92,7 +50,7 @@ def downconvert_and_correlate(system: GNSSSystem, signal: StructSignal, correlat
         raise ValueError("one sample shift per accumulator is required")
     if not 1 <= prn <= system.codes.shape[0]:
         raise ValueError(f"prn {prn} outside 1..{system.codes.shape[0]}")
-    desc = _signal_desc(signal.re, signal.im, num_samples, start=signal_start_sample - 1)
+    desc = signal_desc(signal.re, signal.im, num_samples, start=signal_start_sample - 1)
     prm = make_params(prn - 1, code_frequency, carrier_frequency, code_phase, carrier_phase, shape=(1, 1))
     L, M = shifts.size, correlator.num_ants
     out_re = torch.empty((L, M), dtype=torch.float32, device=ctx.device)
@@ -155,7 +113,7 @@ def downconvert_and_accumulate_strided(accum_re, accum_im, carrier_replica_re, c
     [N x M x L]); any of them may be None.  The code replica is evaluated in place (no replica buffer argument)."""
     ctx = get_context(signal_re.device)
     ctx.set_codes(system.codes)
-    desc = _signal_desc(signal_re, signal_im, int(num_samples))
+    desc = signal_desc(signal_re, signal_im, int(num_samples))
     prm = make_params(int(prn) - 1, code_frequency, carrier_frequency, start_code_phase, carrier_phase, shape=(1,))
     ctx.downconvert_and_accumulate(desc, prm, correlator_sample_shifts, sampling_frequency, carrier_replica_re,
                                    carrier_replica_im, downconverted_signal_re, downconverted_signal_im, accum_re, accum_im)
@@ -197,7 +155,7 @@ class StreamCorrelator:
         self.params_dev = self.ctx.params_to_device(params)
 
     def describe(self, re: torch.Tensor, im: torch.Tensor | None) -> _lib.SignalDesc:
-        d = _signal_desc(re, im, self.N, per_channel=self.per_channel_signal)
+        d = signal_desc(re, im, self.N, per_channel=self.per_channel_signal)
         ntot = re.shape[-2] if im is None else re.shape[-1]
         if ntot < self.B * self.N:
             raise ValueError("signal shorter than num_blocks * num_samples")

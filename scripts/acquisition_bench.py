@@ -72,8 +72,8 @@ def main():
         dop = -7000.0 + 500.0 * np.arange(D)
         cp = g.make_params(np.repeat(np.arange(P), D), fc, np.tile(dop, P), 0.0, 0.0, shape=(1, P * D))
         cp_dev = ctx.params_to_device(cp)
-        from gpuacceleratedtracking_amd.tracking import _signal_desc
-        desc = _signal_desc(re, im, N)
+        from gpuacceleratedtracking_amd.streams import signal_desc
+        desc = signal_desc(re, im, N)
         K = P * D
         o_re = torch.empty((K * 32 * M,), dtype=torch.float32, device="cuda")
         o_im = torch.empty_like(o_re)

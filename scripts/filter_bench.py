@@ -43,7 +43,7 @@ def main():
     import torch
 
     import gpuacceleratedtracking_amd as g
-    from gpuacceleratedtracking_amd import _lib, filtering
+    from gpuacceleratedtracking_amd import _lib, filtering, streams
 
     g.load_library()
     ctx = g.get_context()
@@ -62,7 +62,7 @@ def main():
         taps = filtering.shift_taps(filtering.lowpass_taps(T, 0.25 / D), step)
         g_re, g_im = filtering._tap_planes(taps)
         t_re, t_im = torch.from_numpy(g_re).to(dev), torch.from_numpy(g_im).to(dev)
-        first, desc = filtering._input_desc(signal, N, B, 0, None)
+        first, desc = streams.input_desc(signal, N, B, 0, None)
         Q = filtering.num_outputs(N, T, D)
         ostride = (Q + 3) // 4 * 4
         o_re, o_im = (torch.zeros(M * B * ostride + 4, dtype=torch.float32, device=dev) for _ in range(2))

@@ -36,7 +36,7 @@ def main():
     import torch
 
     import gpuacceleratedtracking_amd as g
-    from gpuacceleratedtracking_amd import frontend
+    from gpuacceleratedtracking_amd import frontend, streams
 
     N, M, L, K, B = 20000, 4, 3, 2, args.blocks
     op, desc, sig, prm = g.build_stream("GPSL1", N, M, L, K, B)
@@ -54,7 +54,7 @@ def main():
 
     def bench_condition(signal, in_bytes, label):
         out, odesc, counts = frontend.condition_samples(signal, params, N, B, torch.int8, ctx=ctx)
-        _, idesc = frontend._input_desc(signal, N, B, 0, None)
+        _, idesc = streams.input_desc(signal, N, B, 0, None)
         fn = ctx.lib.gat_condition_samples
         cargs = (ctx._h, C.byref(idesc), B, C.c_void_p(params.data_ptr()), 0, C.byref(odesc), C.c_void_p(counts.data_ptr()))
 
@@ -73,7 +73,7 @@ def main():
     ctx.sync()
     bench_condition(sig16, 4, "int16_to_int8")
 
-    _, idesc = frontend._input_desc(sig, N, B, 0, None)
+    _, idesc = streams.input_desc(sig, N, B, 0, None)
     sfn, sargs = ctx.lib.gat_sample_stats, (ctx._h, C.byref(idesc), B, B, None, 0, C.c_void_p(st.raw.data_ptr()))
 
     def stats_launch():

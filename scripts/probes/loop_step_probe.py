@@ -5,7 +5,7 @@ import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch, ctypes as C
 import gpuacceleratedtracking_amd as g
-from gpuacceleratedtracking_amd.tracking import _signal_desc
+from gpuacceleratedtracking_amd.streams import signal_desc
 system = g.GPSL1()
 side = torch.cuda.Stream(); torch.cuda.set_stream(side)
 for (K, M, fs) in [tuple(float(x) if i == 2 else int(x) for i, x in enumerate(s.split(","))) for s in sys.argv[1:]] or ((4, 4, 20e6), (1, 4, 4e6), (4, 4, 20e6), (1, 4, 4e6)):
@@ -23,7 +23,7 @@ for (K, M, fs) in [tuple(float(x) if i == 2 else int(x) for i, x in enumerate(s.
     t0a = time.perf_counter()
     for i in range(nblk):
         t0 = time.perf_counter(); ctx.set_codes(system.codes); t1 = time.perf_counter()
-        desc = _signal_desc(re, im, N, start=i * N); t2 = time.perf_counter()
+        desc = signal_desc(re, im, N, start=i * N); t2 = time.perf_counter()
         cur, nxt = a._params[a._cur], a._params[1 - a._cur]
         ctx.downconvert_and_correlate(desc, cur, 1, K, a.shifts, a.fs, a.out_re, a.out_im); t3 = time.perf_counter()
         rc = ctx.lib.gat_tracking_update(ctx._h, C.c_void_p(a.out_re.data_ptr()), C.c_void_p(a.out_im.data_ptr()), K, M, C.byref(a.config), C.c_void_p(a._state.data_ptr()), C.c_void_p(cur.data_ptr()), C.c_void_p(nxt.data_ptr())); t4 = time.perf_counter()

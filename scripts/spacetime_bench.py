@@ -50,8 +50,7 @@ def main():
 
     import gpuacceleratedtracking_amd as g
     from gpuacceleratedtracking_amd import _lib
-    from gpuacceleratedtracking_amd.filtering import _alloc_out
-    from gpuacceleratedtracking_amd.frontend import _input_desc
+    from gpuacceleratedtracking_amd.streams import alloc_stream, input_desc
 
     g.load_library()
     ctx = g.get_context()
@@ -71,10 +70,10 @@ def main():
         return C.c_void_p(t.data_ptr())
 
     def bench(label, signal, reader_ms, M, N, B, T):
-        first, desc = _input_desc(signal, N, B, 0, None)
+        first, desc = input_desc(signal, N, B, 0, None)
         Q, No = M * T, N - T + 1
         w = torch.randn((2, 1, Q), generator=gen, device=dev, dtype=torch.float64) / Q
-        out, odesc = _alloc_out(1, No, B, False, dev)
+        out, odesc = alloc_stream(1, No, B, dev, planar=True)
         cov = torch.zeros((2, 1, Q, Q), dtype=torch.float32, device=dev)
         launches = {}
 

@@ -61,7 +61,7 @@ def main():
 
     import gpuacceleratedtracking_amd as g
     from gpuacceleratedtracking_amd import _lib, spectrum
-    from gpuacceleratedtracking_amd.frontend import _input_desc
+    from gpuacceleratedtracking_amd.streams import input_desc
 
     g.load_library()
     ctx = g.get_context()
@@ -77,7 +77,7 @@ def main():
     gen.manual_seed(1)
 
     def bench(label, signal, reader_ms, M, N, B, F, H):
-        first, desc = _input_desc(signal, N, B, 0, None)
+        first, desc = input_desc(signal, N, B, 0, None)
         w = torch.from_numpy(spectrum.window_values("hann", F)).to(dev)
         power = torch.zeros((B, M, F), dtype=torch.float32, device=dev)
         cfg = spectrum._config(F, H)
