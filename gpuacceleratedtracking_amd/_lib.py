@@ -36,6 +36,8 @@ GAT_MIN_SPECTRUM_BINS, GAT_MAX_SPECTRUM_BINS, GAT_MAX_SPECTRUM_SEGMENTS = 64, 40
 GAT_MAX_ST_TAPS = 16
 # tracking monitor (gat_track_monitor limits)
 GAT_MAX_SYMBOL_BLOCKS, GAT_MAX_MONITOR_BLOCKS, GAT_MAX_MONITOR_CHANNELS = 128, 1 << 20, 4096
+# subspace (gat_accumulator_covariance's chunk, gat_hermitian_eig's sweep limit and input flag)
+GAT_ACC_COV_CHUNK, GAT_EIG_MAX_SWEEPS, GAT_EIG_INPUT_F32 = 256, 60, 1
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -69,6 +71,9 @@ EXPORTS = [
     "gat_spacetime_covariance", "gat_spacetime_filter", "gat_spacetime_filter_host",
     # tracking monitor: C/N0, phase lock, bit synchronisation and data symbols from the accumulator history
     "gat_track_monitor", "gat_track_monitor_host", "gat_track_monitor_plan",
+    # subspace: the accumulators' covariance, the batched Hermitian eigensolver and their plan
+    "gat_accumulator_covariance", "gat_accumulator_covariance_host", "gat_hermitian_eig", "gat_hermitian_eig_host",
+    "gat_subspace_plan",
 ]
 
 
@@ -212,6 +217,17 @@ class MonitorPlan(C.Structure):
                 ("scratch_bytes", C.c_int64)]
 
 
+class SubspacePlan(C.Structure):
+    """gat_subspace_plan_info (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("num_estimates", C.c_int32), ("chunks_per_estimate", C.c_int32), ("cov_split", C.c_int32),
+                ("cov_workgroups", C.c_int32), ("cov_threads", C.c_int32), ("cov_lds_bytes", C.c_int32), ("cov_reduce_workgroups", C.c_int32),
+                ("eig_workgroups", C.c_int32), ("eig_threads", C.c_int32), ("eig_lds_bytes", C.c_int32), ("reserved", C.c_int32),
+                ("scratch_bytes", C.c_int64)]
+
+
+assert C.sizeof(SubspacePlan) == 56
+
 # gat_monitor_window and gat_monitor_channel (include/gat.h)
 MONITOR_WINDOW_DTYPE = np.dtype([("sum_p2", "<f8"), ("sum_p4", "<f8"), ("sum_d", "<f8"), ("sum_i", "<f8"), ("sum_q", "<f8"), ("blocks", "<i8")])
 MONITOR_CHANNEL_DTYPE = np.dtype([("symbol_offset", "<i4"), ("start", "<i4"), ("num_symbols", "<i4"), ("reserved", "<i4"),
@@ -331,6 +347,11 @@ def load(build_if_missing: bool = True):
         "gat_track_monitor": (i32, [vp, vp, vp, i64, i32, i32, i32, C.POINTER(MonitorConfig), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "gat_track_monitor_host": (i32, [vp, vp, i64, i32, i32, i32, C.POINTER(MonitorConfig), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "gat_track_monitor_plan": (i32, [i64, i32, i32, i32, C.POINTER(MonitorConfig), i32, i32, C.POINTER(MonitorPlan)]),
+        "gat_accumulator_covariance": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp]),
+        "gat_accumulator_covariance_host": (i32, [vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp]),
+        "gat_hermitian_eig": (i32, [vp, vp, vp, i32, i32, i32, u32, vp, vp, vp, vp]),
+        "gat_hermitian_eig_host": (i32, [vp, vp, i32, i32, i32, u32, vp, vp, vp, vp]),
+        "gat_subspace_plan": (i32, [i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(SubspacePlan)]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

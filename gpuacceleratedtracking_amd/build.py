@@ -19,7 +19,7 @@ SOURCES = ["gat_dc_f0.hip", "gat_dc_f1.hip", "gat_dc_f2.hip", "gat_dc_f3.hip", "
            "gat_resident_api.cpp", "gat_codes.cpp", "gat_acq.hip", "gat_acq_api.cpp", "gat_array.hip", "gat_array_api.cpp",
            "gat_beam.hip", "gat_beam_api.cpp", "gat_cond.hip", "gat_cond_api.cpp", "gat_fir.hip", "gat_fir_api.cpp",
            "gat_spec.hip", "gat_spec_api.cpp", "gat_acq_fft.hip", "gat_acq_fft_api.cpp", "gat_st.hip", "gat_st_api.cpp",
-           "gat_mon.hip", "gat_mon_api.cpp"]
+           "gat_mon.hip", "gat_mon_api.cpp", "gat_eig.hip", "gat_eig_api.cpp"]
 # gat_version.cpp is not in SOURCES: it is compiled at every link with the build's identity (git commit, flags)
 HEADERS = [os.path.join(CSRC, "gat_internal.h"), os.path.join(CSRC, "gat_sig_plan.h"), os.path.join(CSRC, "gat_phase.h"), os.path.join(CSRC, "gat_dc.h"),
            os.path.join(CSRC, "gat_dc_body.inc"), os.path.join(CSRC, "gat_resident.h"), os.path.join(CSRC, "gat_ctx.h"),
@@ -33,6 +33,7 @@ HEADERS = [os.path.join(CSRC, "gat_internal.h"), os.path.join(CSRC, "gat_sig_pla
            os.path.join(CSRC, "gat_acq_fft_plan.h"), os.path.join(CSRC, "gat_acq_fft_kernels.h"),
            os.path.join(CSRC, "gat_st.h"), os.path.join(CSRC, "gat_st_plan.h"), os.path.join(CSRC, "gat_st_kernels.h"),
            os.path.join(CSRC, "gat_mon.h"), os.path.join(CSRC, "gat_mon_plan.h"), os.path.join(CSRC, "gat_mon_kernels.h"),
+           os.path.join(CSRC, "gat_eig.h"), os.path.join(CSRC, "gat_eig_plan.h"), os.path.join(CSRC, "gat_eig_kernels.h"),
            os.path.join(ROOT, "include", "gat.h")]
 
 

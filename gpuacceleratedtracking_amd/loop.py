@@ -152,6 +152,15 @@ class TrackingLoop:
             kw.setdefault("weights", (self._w_re, self._w_im))
         return monitor_accumulators(acc_re, acc_im, **kw)
 
+    def steering(self, acc_re: torch.Tensor, acc_im: torch.Tensor, **kw):
+        """``subspace.steering_from_accumulators`` over accumulators of this loop (``run(keep=True)``) with the loop's prompt tap
+        filled in: ``(steering [E, K, M], eigenvalues)`` on the device; every keyword of that function may be given."""
+        from .subspace import steering_from_accumulators
+
+        kw.setdefault("tap_index", int(self.config.prompt_index))
+        kw.setdefault("ctx", self.ctx)
+        return steering_from_accumulators(acc_re, acc_im, **kw)
+
     def params(self) -> np.ndarray:
         """Current per-channel parameters (host copy; synchronises)."""
         return self._params[self._cur].cpu().numpy().view(_lib.PARAMS_DTYPE).copy()

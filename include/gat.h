@@ -1089,6 +1089,92 @@ GAT_API int32_t gat_track_monitor_plan(int64_t acc_block_stride, int32_t num_blo
                                        const gat_monitor_config *config, int32_t own_prompts, int32_t want_symbols,
                                        gat_monitor_plan *plan);
 
+/* ---- subspace: the accumulators' covariance, a batched Hermitian eigensolver and with them the steering estimate ---------
+ * An uncalibrated array does not know its steering vectors.  The prompt accumulators of a tracking channel are
+ * A * a + noise per block; their covariance over the blocks is |A|^2 a a^H + noise, without the data bits and without the
+ * loop's common phase error, and its principal eigenvector is the steering vector as the receiver's own hardware sees it
+ * (the eigenbeamformer).  Everything is double precision and every expression is evaluated as written (csrc/gat_eig.h,
+ * shared by the kernels and the host twins: the same bits); sqrt and / are IEEE.
+ *
+ * gat_accumulator_covariance: the accumulators are gat_track_monitor's (B blocks, block b at acc + b * acc_block_stride
+ * floats, element [k][l][m] at (k*L + l)*M + m).  blocks_per_estimate <= 0 (or >= B): one estimate of all blocks; else
+ * E = ceil(B / blocks_per_estimate) estimates, the last taking what is left.  cov_re / cov_im: double [E][K][M][M].
+ *   x_m = (double) acc[b][k][tap_index][m].  For i >= j the term of a block is
+ *       re = xr_i*xr_j + xi_i*xi_j        im = xi_i*xr_j - xr_i*xi_j          (x_i conj(x_j); the products are exact)
+ *   The sum of an estimate has two levels: chunks of GAT_ACC_COV_CHUNK consecutive blocks of the estimate (the last chunk
+ *   shorter), each summed in block order from +0, and the chunk sums added in chunk order from +0.  Entry [j][i] is the
+ *   conjugate (re, -im) of entry [i][j]; the diagonal's imaginary part is written as +0.
+ * Whether the chunk sums pass through the context's scratch to a second kernel or one workgroup walks its chunks is the
+ * plan's choice (gat_subspace_plan) and does not change a bit.  No atomics: the same bits every call.  NaN accumulators
+ * give NaN entries, not an error.  Refusals, before any launch (the host twin: before any write): GAT_ERR_ARG for a null
+ * pointer, num_blocks, num_channels, num_taps or num_ants < 1 and acc_block_stride < K*L*M with more than one block;
+ * GAT_ERR_RANGE for num_ants above GAT_MAX_ARRAY_ANTS, num_blocks above 2^20, num_channels above 4096, tap_index outside
+ * [0, num_taps), more than 2^31 - 1 workgroups and a call whose scratch would exceed 1 GiB (with fewer than 512 (estimate,
+ * channel) pairs the chunk sums take 16 bytes for every chunk and lower-triangle entry of each: fewer blocks a call).
+ *
+ * gat_hermitian_eig: n Hermitian matrices of order Q (1 .. GAT_MAX_ARRAY_ANTS), planar [n][Q][Q], double or -- with
+ * GAT_EIG_INPUT_F32 -- float (what gat_spatial_covariance and gat_spacetime_covariance write).  Only the lower triangle
+ * and the diagonal's real part are read, as in gat_array_weights.  Outputs, each optional (null: not written; at least one
+ * is given): eigenvalues double [n][Q], descending; vec_re / vec_im double [n][R][Q], row r the eigenvector of eigenvalue
+ * r, R = num_vectors in 0 .. Q (both planes or neither; R = 0: nothing is written to them) -- with R = 1 the [K][M]
+ * steering layout gat_array_weights reads --; status int32 [n]: >= 0 the sweeps used, -1 not converged within
+ * GAT_EIG_MAX_SWEEPS (the outputs as they stand), -2 a non-finite input or Frobenius sum (the outputs are NaN).
+ *   The method is cyclic Jacobi in the round-robin ordering.  n' = Q rounded up to even, idx = 0 .. n'-1; a round rotates
+ *   the pairs (idx[i], idx[n'-1-i]), i < n'/2, p the smaller index, pairs with the dummy index Q skipped; after a round
+ *   idx <- [idx[0], idx[n'-1], idx[1], .., idx[n'-2]]; n'-1 rounds make a sweep.  With b = A[p][q] a pair is rotated iff
+ *   br*br + bi*bi > 2^-104 * F, F = the sum of re*re + im*im over the input matrix in row-major order from +0.  Then
+ *       |b| = sqrt(br*br + bi*bi)   u = b / |b|   tau = (A[q][q] - A[p][p]) / (2 |b|)
+ *       t = sign(tau) / (|tau| + sqrt(1 + tau*tau)), sign(0) = +1     c = 1 / sqrt(1 + t*t)     s = t*c     g = s*u
+ *       J[p][p] = J[q][q] = c, J[p][q] = g, J[q][p] = -conj(g).
+ *   All rotations of a round come from the same A; then A <- A J and V <- V J (V starts as the identity):
+ *       x_p' = c x_p - conj(g) x_q:  re = c*xpr - (gr*xqr + gi*xqi)      im = c*xpi - (gr*xqi - gi*xqr)
+ *       x_q' = g x_p + c x_q:        re = (gr*xpr - gi*xpi) + c*xqr      im = (gr*xpi + gi*xpr) + c*xqi
+ *   then A <- J^H A:
+ *       y_p' = c y_p - g y_q:        re = c*ypr - (gr*yqr - gi*yqi)      im = c*ypi - (gr*yqi + gi*yqr)
+ *       y_q' = conj(g) y_p + c y_q:  re = (gr*ypr + gi*ypi) + c*yqr      im = (gr*ypi - gi*ypr) + c*yqi
+ *   with A[p][q] = A[q][p] = 0 and the imaginary parts of A[p][p] and A[q][q] set to +0.  A pair that is not rotated leaves
+ *   its rows and columns as they are.  A sweep that rotates nothing ends the iteration; the status counts the sweeps before
+ *   it.  The eigenvalues are the diagonal, sorted descending with ties to the lower index; eigenvector r is the column of V
+ *   of eigenvalue r times the unit factor conj(v_m) / |v_m| of its component of largest re*re + im*im (the lowest index of
+ *   the largest), which itself is written as (|v_m|, +0).
+ * Refusals, before any launch: GAT_ERR_ARG for a null input plane, every output null, n < 1, one vector plane without the
+ * other and an unknown flag; GAT_ERR_RANGE for Q outside 1 .. GAT_MAX_ARRAY_ANTS and num_vectors outside 0 .. Q.
+ * Both device calls enqueue on the context's stream and do not synchronise. */
+#define GAT_ACC_COV_CHUNK 256
+#define GAT_EIG_MAX_SWEEPS 60
+#define GAT_EIG_INPUT_F32 1u
+GAT_API int32_t gat_accumulator_covariance(gat_ctx *ctx, const float *acc_re_dev, const float *acc_im_dev, int64_t acc_block_stride,
+                                           int32_t num_blocks, int32_t num_channels, int32_t num_taps, int32_t num_ants,
+                                           int32_t tap_index, int32_t blocks_per_estimate, double *cov_re, double *cov_im);
+GAT_API int32_t gat_hermitian_eig(gat_ctx *ctx, const void *a_re_dev, const void *a_im_dev, int32_t num_matrices, int32_t order,
+                                  int32_t num_vectors, uint32_t flags, double *eigenvalues, double *vec_re, double *vec_im,
+                                  int32_t *status);
+/* The same rules in plain loops on the HOST (csrc/gat_eig.h, shared with the device): every pointer is host memory; no
+ * context and no device.  The bit-exact references of the device calls, with the same refusals. */
+GAT_API int32_t gat_accumulator_covariance_host(const float *acc_re_host, const float *acc_im_host, int64_t acc_block_stride,
+                                                int32_t num_blocks, int32_t num_channels, int32_t num_taps, int32_t num_ants,
+                                                int32_t tap_index, int32_t blocks_per_estimate, double *cov_re, double *cov_im);
+GAT_API int32_t gat_hermitian_eig_host(const void *a_re_host, const void *a_im_host, int32_t num_matrices, int32_t order,
+                                       int32_t num_vectors, uint32_t flags, double *eigenvalues, double *vec_re, double *vec_im,
+                                       int32_t *status);
+/* What the two calls would do (csrc/gat_eig_plan.h; no context, no device, nothing is read): num_blocks = 0 leaves the
+ * covariance out (its fields are 0), eig_matrices = 0 the eigensolver; one of them is planned.  cov_split = 1: one workgroup
+ * per (estimate, channel, chunk) writes chunk sums to the scratch and a second kernel adds them; 0: one workgroup per
+ * (estimate, channel) walks its chunks.  The eigensolver runs one workgroup per matrix.  The refusals are the calls'. */
+typedef struct gat_subspace_plan_info {
+    uint32_t struct_size; /* sizeof(gat_subspace_plan_info), set by the caller */
+    int32_t num_estimates;       /* E */
+    int32_t chunks_per_estimate; /* of a full estimate */
+    int32_t cov_split;
+    int32_t cov_workgroups, cov_threads, cov_lds_bytes, cov_reduce_workgroups;
+    int32_t eig_workgroups, eig_threads, eig_lds_bytes;
+    int32_t reserved;
+    int64_t scratch_bytes;
+} gat_subspace_plan_info;
+GAT_API int32_t gat_subspace_plan(int64_t acc_block_stride, int32_t num_blocks, int32_t num_channels, int32_t num_taps,
+                                  int32_t num_ants, int32_t tap_index, int32_t blocks_per_estimate, int32_t eig_matrices,
+                                  int32_t eig_order, int32_t eig_vectors, gat_subspace_plan_info *plan);
+
 #ifdef __cplusplus
 }
 #endif

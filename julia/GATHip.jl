@@ -1110,4 +1110,84 @@ function track_monitor_plan(acc_block_stride::Integer, num_blocks::Integer, num_
     plan[]
 end
 
+# ---- subspace: the accumulators' covariance, a batched Hermitian eigensolver, the steering estimate (include/gat.h) ----
+const GAT_ACC_COV_CHUNK = 256
+const GAT_EIG_MAX_SWEEPS = 60
+const GAT_EIG_INPUT_F32 = UInt32(1)
+# struct gat_subspace_plan_info (56 bytes)
+struct SubspacePlan
+    struct_size::UInt32
+    num_estimates::Int32
+    chunks_per_estimate::Int32
+    cov_split::Int32
+    cov_workgroups::Int32
+    cov_threads::Int32
+    cov_lds_bytes::Int32
+    cov_reduce_workgroups::Int32
+    eig_workgroups::Int32
+    eig_threads::Int32
+    eig_lds_bytes::Int32
+    reserved::Int32
+    scratch_bytes::Int64
+end
+# cov_re / cov_im: device pointers to [M x M x K x E] doubles in Julia's order, E = cld(B, blocks_per_estimate) (<= 0: one estimate);
+# tap_index is 0-based as in the loop configuration.  Enqueues only.
+function accumulator_covariance!(ctx::Context, acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, acc_block_stride::Integer, num_blocks::Integer,
+                                 num_channels::Integer, num_taps::Integer, num_ants::Integer, tap_index::Integer, cov_re::Ptr{Float64},
+                                 cov_im::Ptr{Float64}; blocks_per_estimate::Integer = 0)
+    check(ctx, ccall((:gat_accumulator_covariance, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Int32, Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+                     ctx.handle, acc_re, acc_im, Int64(acc_block_stride), Int32(num_blocks), Int32(num_channels), Int32(num_taps),
+                     Int32(num_ants), Int32(tap_index), Int32(blocks_per_estimate), cov_re, cov_im))
+end
+# the same rule on host memory, the bit-exact reference: acc [M, L, K, B] contiguous; returns (cov_re, cov_im) [M, M, K, E]
+# (Julia's order: element [j, i] of the C matrix [i][j] -- the transpose, i.e. the conjugate of a Hermitian matrix)
+function accumulator_covariance_host(acc_re::Array{Float32,4}, acc_im::Array{Float32,4}, tap_index::Integer; blocks_per_estimate::Integer = 0)
+    M, L, K, B = size(acc_re)
+    bpe = blocks_per_estimate <= 0 || blocks_per_estimate > B ? B : Int(blocks_per_estimate)
+    E = cld(B, bpe)
+    cov_re, cov_im = zeros(Float64, M, M, K, E), zeros(Float64, M, M, K, E)
+    rc = ccall((:gat_accumulator_covariance_host, libgat), Int32,
+               (Ptr{Cfloat}, Ptr{Cfloat}, Int64, Int32, Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+               acc_re, acc_im, Int64(M * L * K), Int32(B), Int32(K), Int32(L), Int32(M), Int32(tap_index), Int32(blocks_per_estimate), cov_re,
+               cov_im)
+    rc == GAT_OK || throw(GatError(rc, "gat_accumulator_covariance_host"))
+    cov_re, cov_im
+end
+# a_re / a_im: device pointers to n matrices [Q x Q] of doubles, or of floats with flags = GAT_EIG_INPUT_F32 (the lower triangle of the
+# C matrix is read); every output is a device pointer or C_NULL: eigenvalues [Q x n], vectors [Q x R x n], status [n].  Enqueues only.
+function hermitian_eig!(ctx::Context, a_re::Ptr{Cvoid}, a_im::Ptr{Cvoid}, num_matrices::Integer, order::Integer, num_vectors::Integer;
+                        flags::UInt32 = UInt32(0), eigenvalues::Ptr{Float64} = Ptr{Float64}(C_NULL), vec_re::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                        vec_im::Ptr{Float64} = Ptr{Float64}(C_NULL), status::Ptr{Int32} = Ptr{Int32}(C_NULL))
+    check(ctx, ccall((:gat_hermitian_eig, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                     ctx.handle, a_re, a_im, Int32(num_matrices), Int32(order), Int32(num_vectors), flags, eigenvalues, vec_re, vec_im, status))
+end
+# the same rule on host memory: a_re / a_im [Q, Q, n] as C wrote them (accumulator_covariance_host's planes go in as they are); returns
+# (eigenvalues [Q, n] descending, vec_re, vec_im [Q, R, n], status [n])
+function hermitian_eig_host(a_re::Array{Float64,3}, a_im::Array{Float64,3}; num_vectors::Integer = size(a_re, 1))
+    Q, _, n = size(a_re)
+    R = Int(num_vectors)
+    eigenvalues = zeros(Float64, Q, n)
+    vec_re, vec_im = zeros(Float64, Q, R, n), zeros(Float64, Q, R, n)
+    status = zeros(Int32, n)
+    rc = ccall((:gat_hermitian_eig_host, libgat), Int32,
+               (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, UInt32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+               a_re, a_im, Int32(n), Int32(Q), Int32(R), UInt32(0), eigenvalues, vec_re, vec_im, status)
+    rc == GAT_OK || throw(GatError(rc, "gat_hermitian_eig_host"))
+    eigenvalues, vec_re, vec_im, status
+end
+# what the two calls would do, without a device: num_blocks = 0 leaves the covariance out, eig_matrices = 0 the eigensolver
+function subspace_plan(; acc_block_stride::Integer = 0, num_blocks::Integer = 0, num_channels::Integer = 1, num_taps::Integer = 1,
+                       num_ants::Integer = 1, tap_index::Integer = 0, blocks_per_estimate::Integer = 0, eig_matrices::Integer = 0,
+                       eig_order::Integer = 1, eig_vectors::Integer = 0)
+    plan = Ref(SubspacePlan(UInt32(sizeof(SubspacePlan)), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_subspace_plan, libgat), Int32,
+               (Int64, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Ref{SubspacePlan}),
+               Int64(acc_block_stride), Int32(num_blocks), Int32(num_channels), Int32(num_taps), Int32(num_ants), Int32(tap_index),
+               Int32(blocks_per_estimate), Int32(eig_matrices), Int32(eig_order), Int32(eig_vectors), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_subspace_plan"))
+    plan[]
+end
+
 end # module
