@@ -24,6 +24,7 @@ SOURCES = ["gat_dc_f0.hip", "gat_dc_f1.hip", "gat_dc_f2.hip", "gat_dc_f3.hip", "
 HEADERS = [os.path.join(CSRC, "gat_internal.h"), os.path.join(CSRC, "gat_sig_plan.h"), os.path.join(CSRC, "gat_phase.h"), os.path.join(CSRC, "gat_dc.h"),
            os.path.join(CSRC, "gat_dc_body.inc"), os.path.join(CSRC, "gat_resident.h"), os.path.join(CSRC, "gat_ctx.h"),
            os.path.join(CSRC, "gat_acq.h"), os.path.join(CSRC, "gat_acq_kernels.h"), os.path.join(CSRC, "gat_loop.h"),
+           os.path.join(CSRC, "gat_est_plan.h"), os.path.join(CSRC, "gat_array_plan.h"),
            os.path.join(CSRC, "gat_array.h"), os.path.join(CSRC, "gat_array_kernels.h"), os.path.join(CSRC, "gat_beam_plan.h"),
            os.path.join(CSRC, "gat_beam_kernels.h"),
            os.path.join(CSRC, "gat_cond.h"), os.path.join(CSRC, "gat_cond_plan.h"), os.path.join(CSRC, "gat_cond_kernels.h"),

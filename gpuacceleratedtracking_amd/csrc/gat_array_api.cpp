@@ -1,7 +1,7 @@
 // gat_array_api.cpp -- host side of the antenna-array entry points (include/gat.h gat_spatial_covariance, gat_array_weights,
-// gat_beamform, gat_tracking_update_weighted, gat_tracking_run_weighted): validation, the covariance's work split, the launch
-// sequences.  The host-only twins (gat_array_weights_host, gat_tracking_update_host_weighted) live in gat_codes.cpp.
-#include <algorithm>
+// gat_beamform, gat_tracking_update_weighted, gat_tracking_run_weighted): validation and the launch sequences; the covariance's
+// refusals, kernel choice and work split are the pure plan of gat_array_plan.h.  The host-only twins (gat_array_weights_host,
+// gat_tracking_update_host_weighted) live in gat_codes.cpp.
 #include <cmath>
 #include <cstring>
 
@@ -10,68 +10,20 @@
 
 using namespace gat;
 
-namespace {
-
-constexpr size_t kMaxCovScratch = (size_t)256 << 20; // bytes of the workgroups' slices of one launch; more estimates go in batches
-
-// B blocks, E estimates of bpe blocks (the last one shorter), from `re` / `im`
-int32_t covariance_launches(gat_ctx *c, const gat_signal_desc *sig, const void *re, const void *im, int B, int bpe, int E, bool vec, float *cov_re,
-                            float *cov_im)
-{
-    const int M = sig->num_ants, layout = sig->layout;
-    const long long N = sig->num_samples;
-    const CovTileGeom geo = cov_tile_geom(M);
-    // the smallest piece of a block worth a work unit, and what a segment's length is rounded up to
-    const long long vs = layout_vec_samples(layout);
-    const long long round_to = vec ? vs * kCovSmallThreads : geo.chunk;
-    const long long min_seg = vec ? 4 * round_to : 8ll * geo.chunk;
-    const long long want = (long long)c->num_cus * (vec ? 8 : 4); // workgroups of the launch
-    const EstimateSplit sp = split_estimate(std::min(bpe, B), N, round_to, min_seg, std::max<long long>(1, want / E));
-    const size_t bytes = (size_t)E * (size_t)sp.G * 2 * M * M * sizeof(float);
-    const int32_t rc = ensure_partial(c, bytes);
-    if (rc != GAT_OK) return rc;
-    CovArgs a{};
-    a.re = re;
-    a.im = im;
-    a.M = M;
-    a.B = B;
-    a.bpe = bpe;
-    a.E = E;
-    a.G = (int)sp.G;
-    a.splits = (int)sp.splits;
-    a.N = N;
-    a.ant_stride = sig->ant_stride;
-    a.block_stride = sig->block_stride;
-    a.seg_len = sp.seg_len;
-    a.partial = c->d_partial;
-    GAT_HIP(c, vec ? launch_cov_small(a, layout, c->stream) : launch_cov_tiled(a, layout, c->stream));
-    GAT_HIP(c, launch_cov_finish(c->d_partial, M, E, (int)sp.G, cov_re, cov_im, c->stream));
-    return GAT_OK;
-}
-
-} // namespace
-
 GAT_API int32_t gat_spatial_covariance(gat_ctx *c, const gat_signal_desc *sig, int32_t B, int32_t bpe, float *cov_re, float *cov_im)
 {
     if (!c) return GAT_ERR_ARG;
-    if (!sig || !cov_re || !cov_im) return fail(c, GAT_ERR_ARG, "null argument");
-    if (B < 1 || bpe < 1) return fail(c, GAT_ERR_ARG, "num_blocks and blocks_per_estimate must be positive");
-    // (the antenna limit ahead of the shared check's strides, as this entry point always answered)
-    if (sig->num_ants > GAT_MAX_ARRAY_ANTS) return fail(c, GAT_ERR_RANGE, "more than 64 antennas");
-    const Refusal r = check_desc(sig, B, GAT_MAX_ARRAY_ANTS, signal_refusals({GAT_ERR_UNSUPPORTED, "chan_stride must be 0 (one signal, one covariance)"}));
+    CovPlan plan{};
+    const Refusal r = cov_plan(sig, B, bpe, cov_re, cov_im, c->num_cus, &plan);
     if (r.code != GAT_OK) return fail(c, r.code, r.msg);
-    const int M = sig->num_ants;
-    const bool vec = M <= kCovSmallMaxAnts && blocks_aligned(sig, B); // the streaming kernel's rule is the correlator's fast-path rule
     GAT_ENTER(c, "gat_spatial_covariance");
-    // estimates per launch: one workgroup each at least, within the scratch bound
-    for (EstimateBatches t(B, bpe, (size_t)2 * M * M * sizeof(float), kMaxCovScratch); t.next();) {
-        const size_t off = block_offset_bytes(sig, t.b0);
-        const void *re = static_cast<const char *>(sig->re) + off;
-        const void *im = sig->im ? static_cast<const char *>(sig->im) + off : nullptr;
-        const int32_t rc = covariance_launches(c, sig, re, im, t.bn, bpe, t.en, vec, cov_re + (size_t)t.e0 * M * M, cov_im + (size_t)t.e0 * M * M);
-        if (rc != GAT_OK) return rc;
-    }
-    return GAT_OK;
+    const int M = sig->num_ants, layout = sig->layout;
+    return enqueue_estimates<CovArgs>(c, sig, plan.est, [&](CovArgs a, const EstimateLaunches &t) -> int32_t {
+        a.partial = c->d_partial;
+        GAT_HIP(c, plan.vec ? launch_cov_small(a, layout, c->stream) : launch_cov_tiled(a, layout, c->stream));
+        GAT_HIP(c, launch_cov_finish(c->d_partial, M, t.en, (int)t.G, cov_re + (size_t)t.e0 * M * M, cov_im + (size_t)t.e0 * M * M, c->stream));
+        return GAT_OK;
+    });
 }
 
 GAT_API int32_t gat_array_weights(gat_ctx *c, const float *cov_re, const float *cov_im, int32_t M, const double *steer_re, const double *steer_im,

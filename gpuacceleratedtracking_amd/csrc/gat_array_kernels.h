@@ -1,5 +1,5 @@
-// gat_array_kernels.h -- what the array kernels (gat_array.hip) and their host side (gat_array_api.cpp) share: the covariance
-// kernels' geometry, their arguments and the launchers.
+// gat_array_kernels.h -- what the array kernels (gat_array.hip) and their host side (gat_array_api.cpp) share: the kernels'
+// arguments and the launchers.  The covariance kernels' geometry and the work split are gat_array_plan.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,37 +7,9 @@
 #include <stdint.h>
 
 #include "gat.h"
+#include "gat_array_plan.h"
 
 namespace gat {
-
-constexpr int kCovSmallMaxAnts = 8;  // the streaming kernel keeps the whole upper triangle in registers up to here
-constexpr int kCovSmallThreads = 256;
-constexpr int kCovTileThreads = 512; // the LDS-tiled kernel: 4 x 4 antenna tiles x sample phases
-constexpr int kCovTile = 4;
-constexpr int kCovFinishLanes = 64;  // the finishing kernel adds a (estimate, element)'s slices in this many interleaved runs
-
-// Geometry of the LDS-tiled kernel for M antennas: nt x nt tiles of 4 x 4, the upper ones (tiles) spread over the
-// workgroup's threads with `phases` sample phases each; a chunk of `chunk` = phases * per_phase samples is staged per step
-// in rows of `row` float2 (the antennas padded to whole tiles, plus two: consecutive samples start 16 bytes further round
-// the banks).
-struct CovTileGeom {
-    int nt, tiles, phases, per_phase, chunk, row;
-    size_t lds_bytes;
-};
-inline CovTileGeom cov_tile_geom(int M)
-{
-    CovTileGeom g{};
-    g.nt = (M + kCovTile - 1) / kCovTile;
-    g.tiles = g.nt * (g.nt + 1) / 2;
-    g.phases = kCovTileThreads / g.tiles;
-    g.row = g.nt * kCovTile + 2;
-    const int budget = 32768 / (g.row * 8); // samples 32 KB hold
-    g.per_phase = budget / g.phases < 1 ? 1 : (budget / g.phases > 8 ? 8 : budget / g.phases);
-    g.chunk = g.phases * g.per_phase;
-    const size_t stage = (size_t)g.chunk * g.row * 8, reduce = (size_t)kCovTileThreads * 16 * sizeof(float);
-    g.lds_bytes = stage > reduce ? stage : reduce;
-    return g;
-}
 
 // One covariance call.  Work units are (block, segment of seg_len samples): estimate e owns blocks [e * bpe, min(B, (e+1) * bpe))
 // and G workgroups (workgroup e * G + g of the grid); workgroup g of e takes its units g, g + G, ... and writes its sums to slice

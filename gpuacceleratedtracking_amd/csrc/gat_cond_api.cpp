@@ -1,5 +1,5 @@
 // gat_cond_api.cpp -- host side of the sample conditioner (include/gat.h gat_condition_samples, gat_sample_stats,
-// gat_agc_update): the launches behind the pure plan of gat_cond_plan.h and the shared splits of gat_sig_plan.h, and the host twins
+// gat_agc_update): the launches behind the pure plans of gat_cond_plan.h, and the host twins
 // (gat_condition_samples_host, gat_agc_update_host), which run the arithmetic of gat_cond.h in plain loops.
 #include <algorithm>
 #include <cmath>
@@ -11,8 +11,6 @@
 using namespace gat;
 
 namespace {
-
-constexpr size_t kMaxStatsScratch = (size_t)64 << 20; // bytes of the workgroups' slices of one launch; more estimates go in batches
 
 bool agc_config_ok(const gat_agc_config *cfg)
 {
@@ -112,54 +110,31 @@ GAT_API int32_t gat_sample_stats(gat_ctx *c, const gat_signal_desc *sig, int32_t
                                  gat_sample_stats_t *stats)
 {
     if (!c) return GAT_ERR_ARG;
-    if (!stats) return fail(c, GAT_ERR_ARG, "null argument");
-    if (bpe < 1) return fail(c, GAT_ERR_ARG, "blocks_per_estimate must be positive");
-    if (flags & ~(uint32_t)GAT_COND_BLANK_ALL_ANTS) return fail(c, GAT_ERR_ARG, "unknown flags");
-    const Refusal r = cond_check_signal(sig, B);
+    StatsPlan plan{};
+    const Refusal r = stats_plan(sig, B, bpe, flags, stats, c->num_cus, &plan);
     if (r.code != GAT_OK) return fail(c, r.code, r.msg);
-    const int M = sig->num_ants, layout = sig->layout;
-    const long long N = sig->num_samples;
-    const bool vec = M <= kStatsTile && blocks_aligned(sig, B);
     GAT_ENTER(c, "gat_sample_stats");
-    // the work split of one batch of estimates, as the covariance's: (block, segment) units, G workgroups an estimate
-    const long long round_to = (long long)kStatsThreads * (vec ? layout_vec_samples(layout) : 1);
-    const long long want = (long long)c->num_cus * 8;
+    const int M = sig->num_ants;
     long long grid_all = 0, splits_all = 1;
-    for (EstimateBatches t(B, bpe, M * sizeof(gat_sample_stats_t), kMaxStatsScratch); t.next();) {
-        const EstimateSplit sp = split_estimate(std::min(bpe, t.bn), N, round_to, 4 * round_to, std::max<long long>(1, want / t.en));
-        const long long G = sp.G, splits = sp.splits;
-        const int32_t rc = ensure_partial(c, (size_t)t.en * (size_t)G * M * sizeof(gat_sample_stats_t));
-        if (rc != GAT_OK) return rc;
-        const size_t off = block_offset_bytes(sig, t.b0);
-        StatsArgs a{};
-        a.re = static_cast<const char *>(sig->re) + off;
-        a.im = sig->im ? static_cast<const char *>(sig->im) + off : nullptr;
-        a.M = M;
-        a.B = t.bn;
-        a.bpe = bpe;
-        a.E = t.en;
-        a.G = (int)G;
-        a.splits = (int)splits;
+    const int32_t rc = enqueue_estimates<StatsArgs>(c, sig, plan.est, [&](StatsArgs a, const EstimateLaunches &t) -> int32_t {
         a.blank_all = (flags & GAT_COND_BLANK_ALL_ANTS) ? 1 : 0;
-        a.N = N;
-        a.ant_stride = sig->ant_stride;
-        a.block_stride = sig->block_stride;
-        a.seg_len = sp.seg_len;
         a.prm = params;
         a.partial = reinterpret_cast<gat_sample_stats_t *>(c->d_partial);
-        GAT_HIP(c, launch_stats(a, layout, vec, c->stream));
-        GAT_HIP(c, launch_stats_finish(a.partial, M, t.en, (int)G, stats + (size_t)t.e0 * M, c->stream));
+        GAT_HIP(c, launch_stats(a, sig->layout, plan.vec, c->stream));
+        GAT_HIP(c, launch_stats_finish(a.partial, M, t.en, (int)t.G, stats + (size_t)t.e0 * M, c->stream));
         // gat_last_launch_info describes the whole call: the workgroups of every batch, the largest split
-        grid_all += (long long)t.en * G * (M <= kStatsTile ? 1 : (M + kStatsTile - 1) / kStatsTile);
-        splits_all = std::max(splits_all, splits);
-    }
+        grid_all += (long long)t.en * t.G * plan.tiles;
+        splits_all = std::max(splits_all, t.splits);
+        return GAT_OK;
+    });
+    if (rc != GAT_OK) return rc;
     c->last = gat_launch_info{};
     c->last.workgroups = (int32_t)std::min<long long>(grid_all, 0x7fffffff);
     c->last.threads = kStatsThreads;
     c->last.splits = (int32_t)splits_all;
-    c->last.ant_tile = std::min(M, kStatsTile);
-    c->last.vec = vec ? 4 : 1;
-    c->last.lds_bytes = (int32_t)((kStatsThreads / 64) * std::min(M, kStatsTile) * sizeof(gat_sample_stats_t));
+    c->last.ant_tile = plan.ant_tile;
+    c->last.vec = plan.vec ? 4 : 1;
+    c->last.lds_bytes = (int32_t)((kStatsThreads / 64) * plan.ant_tile * sizeof(gat_sample_stats_t));
     c->last.finalize_launched = 1;
     return GAT_OK;
 }

@@ -24,8 +24,6 @@ hipError_t launch_cond_stream(const CondArgs &a, int fmt_in, int fmt_out, const 
 // any M <= 64, any alignment
 hipError_t launch_cond_general(const CondArgs &a, int fmt_in, int fmt_out, const gat_cond_params *prm, int grid, hipStream_t st);
 
-constexpr int kStatsThreads = 256;
-constexpr int kStatsTile = 8; // antennas whose sums a lane keeps in registers; more antennas run in tiles (blockIdx.y)
 // One gat_sample_stats launch.  Estimate e owns blocks [e * bpe, min(B, (e + 1) * bpe)) and G workgroups (blockIdx.x = e * G + g);
 // workgroup g of e takes its (block, segment of seg_len samples) units g, g + G, ... and writes one record per antenna of its
 // tile to partial[(e * G + g) * M + m].

@@ -1,9 +1,10 @@
-// gat_cond_plan.h -- the pure part of gat_condition_samples (include/gat.h): its refusals, the choice between the streaming and
-// the general kernel and the work split, as a function of the two descriptors alone.  No HIP call and no HIP header: the
-// device entry point, the host twin and a stand-alone test program (tests/condplan) compile the same text.
+// gat_cond_plan.h -- the pure part of gat_condition_samples and gat_sample_stats (include/gat.h): their refusals, the choice
+// between the streaming and the general kernel and the work split, as a function of the call's arguments alone.  No HIP call
+// and no HIP header: the device entry points, the host twin and the stand-alone test programs (tests/condplan, tests/estplan)
+// compile the same text.
 #pragma once
 
-#include "gat_sig_plan.h"
+#include "gat_est_plan.h"
 
 namespace gat {
 
@@ -73,6 +74,40 @@ inline Refusal cond_plan(const gat_signal_desc *sig, int32_t B, const void *para
     p.group = p.stream ? cond_group_samples(sig->layout, out->layout) : 1;
     const ChunkSplit s = split_chunks(B, sig->num_samples, (long long)kCondThreads * p.group, workgroups_wanted);
     p.chunk = s.chunk, p.chunks = s.chunks, p.units = s.units, p.grid = s.grid;
+    *plan = p;
+    return {GAT_OK, nullptr};
+}
+
+// ---- the statistics -----------------------------------------------------------------------------------------------------------------
+constexpr int kStatsThreads = 256;
+constexpr int kStatsTile = 8; // antennas whose sums a lane keeps in registers; more antennas run in tiles (blockIdx.y)
+constexpr size_t kStatsScratchCap = (size_t)64 << 20; // bytes of the workgroups' slices of one launch; more estimates go in batches
+
+// vec: M <= 8 and the fast-path rule (16-byte loads); else scalar loads.  A launch's grid is its estimates x their workgroups x
+// `tiles` tiles of ant_tile antennas (the last tile the rest); a slice is one record per antenna.
+struct StatsPlan {
+    bool vec;
+    int tiles, ant_tile;
+    EstimatePlan est;
+};
+
+// The whole gat_sample_stats call (the records may be null: no blanking).  *plan is written only with GAT_OK.
+inline Refusal stats_plan(const gat_signal_desc *sig, int32_t B, int32_t bpe, uint32_t flags, const gat_sample_stats_t *stats, int num_cus,
+                          StatsPlan *plan)
+{
+    if (!stats || !plan) return {GAT_ERR_ARG, "null argument"};
+    if (bpe < 1) return {GAT_ERR_ARG, "blocks_per_estimate must be positive"};
+    if (flags & ~(uint32_t)GAT_COND_BLANK_ALL_ANTS) return {GAT_ERR_ARG, "unknown flags"};
+    const Refusal r = cond_check_signal(sig, B);
+    if (r.code != GAT_OK) return r;
+    const int M = sig->num_ants;
+    StatsPlan p{};
+    p.vec = M <= kStatsTile && blocks_aligned(sig, B);
+    p.tiles = (M + kStatsTile - 1) / kStatsTile;
+    p.ant_tile = M < kStatsTile ? M : kStatsTile;
+    // the covariance's split: (block, segment) units, G workgroups an estimate
+    const long long round_to = (long long)kStatsThreads * (p.vec ? layout_vec_samples(sig->layout) : 1);
+    p.est = {B, bpe, sig->num_samples, round_to, 4 * round_to, (long long)num_cus * 8, M * sizeof(gat_sample_stats_t), kStatsScratchCap};
     *plan = p;
     return {GAT_OK, nullptr};
 }

@@ -2,7 +2,10 @@
 // graph housekeeping, the planner's entry points.  The layer: gat_api.cpp (contexts, operators, options, the closed loop),
 // gat_planner.cpp (the correlator call's launch planning), gat_group.cpp (device groups), gat_resident_api.cpp (the resident
 // correlator's host side), gat_acq_api.cpp (acquisition), gat_array_api.cpp (antenna arrays), gat_beam_api.cpp (beams of the raw
-// samples), gat_cond_api.cpp (sample conditioning).  What the operators over raw samples share is gat_sig_plan.h (through gat_internal.h).
+// samples), gat_cond_api.cpp (sample conditioning), gat_st_api.cpp (space-time processing).  What the operators over raw samples
+// share is gat_sig_plan.h (through gat_internal.h); the work split of those that reduce blocks to estimates is gat_est_plan.h, filled
+// in by the pure plans cov_plan (gat_array_plan.h), stats_plan (gat_cond_plan.h) and st_cov_plan (gat_st_plan.h) and walked by
+// enqueue_estimates below.
 #pragma once
 
 #include <cmath>
@@ -11,6 +14,7 @@
 #include <vector>
 
 #include "gat_acq_check.h" // code_span_ok: the host mirror of the kernels' code_span_bad
+#include "gat_est_plan.h"  // the launches that enqueue_estimates walks
 #include "gat_internal.h"
 
 struct gat_ctx;
@@ -154,6 +158,40 @@ int32_t grow_scratch(gat_ctx *c, void **buf, size_t *cap_bytes, size_t bytes, bo
 inline int32_t ensure_partial(gat_ctx *c, size_t bytes) { return grow_scratch(c, reinterpret_cast<void **>(&c->d_partial), &c->partial_bytes, bytes, true); }
 inline int32_t ensure_params(gat_ctx *c, size_t bytes) { return grow_scratch(c, reinterpret_cast<void **>(&c->d_params), &c->params_bytes, bytes, false); }
 int32_t upload_params(gat_ctx *c, const gat_channel_params *params_host, size_t n);
+
+// The enqueue loop of the operators that reduce blocks to estimates (gat_spatial_covariance, gat_sample_stats,
+// gat_spacetime_covariance).  What CovArgs and StatsArgs share, for launch t of a plan over sig: the planes from the launch's first block on.
+template <class Args>
+Args estimate_args(const gat_signal_desc *sig, const EstimateLaunches &t)
+{
+    const size_t off = block_offset_bytes(sig, t.b0);
+    Args a{};
+    a.re = static_cast<const char *>(sig->re) + off;
+    a.im = sig->im ? static_cast<const char *>(sig->im) + off : nullptr;
+    a.M = sig->num_ants;
+    a.B = t.bn;
+    a.bpe = t.bpe;
+    a.E = t.en;
+    a.G = (int)t.G;
+    a.splits = (int)t.splits;
+    a.N = t.plan.N;
+    a.ant_stride = sig->ant_stride;
+    a.block_stride = sig->block_stride;
+    a.seg_len = t.seg_len;
+    return a;
+}
+// Walks the plan's launches: room for each one's slices in c->d_partial, then launch(args, t) enqueues its kernel and its finish
+// (what it returns but GAT_OK ends the walk).
+template <class Args, class F>
+int32_t enqueue_estimates(gat_ctx *c, const gat_signal_desc *sig, const EstimatePlan &plan, F &&launch)
+{
+    for (EstimateLaunches t(plan); t.next();) {
+        int32_t rc = ensure_partial(c, t.scratch_bytes);
+        if (rc == GAT_OK) rc = launch(estimate_args<Args>(sig, t), t);
+        if (rc != GAT_OK) return rc;
+    }
+    return GAT_OK;
+}
 // validation of a loop configuration (gat_tracking_update and the weighted update)
 int32_t check_loop_config(gat_ctx *c, const gat_loop_config *cfg);
 

@@ -140,25 +140,7 @@ inline ChunkSplit split_chunks(long long B, long long N, long long round_to, lon
     return {s.seg_len, s.splits, B * s.splits, s.G}; // chunks > 1 only where B < want: units below 2^31 either way
 }
 
-// The estimates of a call -- ceil(B / bpe), of bpe blocks each, the last one shorter -- in batches whose slices (slice_bytes an estimate
-// and workgroup) fit cap_bytes of scratch with one workgroup an estimate at least: after next(), estimates [e0, e0 + en) own blocks [b0, b0 + bn).
-struct EstimateBatches {
-    const int B, bpe, E, e_max;
-    int e0 = 0, en = 0, b0 = 0, bn = 0;
-    EstimateBatches(int B_, int bpe_, size_t slice_bytes, size_t cap_bytes)
-        : B(B_), bpe(bpe_), E((int)(((long long)B_ + bpe_ - 1) / bpe_)),
-          e_max(cap_bytes / slice_bytes < 1 ? 1 : cap_bytes / slice_bytes > ((size_t)1 << 20) ? 1 << 20 : (int)(cap_bytes / slice_bytes)) {}
-    bool next()
-    {
-        if ((e0 += en) >= E) return false;
-        en = e_max < E - e0 ? e_max : E - e0;
-        const long long first = (long long)e0 * bpe, most = (long long)en * bpe;
-        b0 = (int)first;
-        bn = (int)(B - first < most ? B - first : most);
-        return true;
-    }
-};
-// bytes from a plane's start to block b0 of a descriptor
+// bytes from a plane's start to block b0 of a descriptor (a batch of an estimating call's launches: gat_est_plan.h)
 inline size_t block_offset_bytes(const gat_signal_desc *d, int b0)
 {
     return (size_t)b0 * (size_t)d->block_stride * (size_t)layout_sample_bytes(d->layout);

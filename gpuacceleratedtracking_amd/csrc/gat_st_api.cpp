@@ -10,48 +10,21 @@
 
 using namespace gat;
 
-namespace {
-
-constexpr size_t kMaxStCovScratch = (size_t)256 << 20; // bytes of the workgroups' slices of one launch; more estimates go in batches
-
-} // namespace
-
 GAT_API int32_t gat_spacetime_covariance(gat_ctx *c, const gat_signal_desc *sig, int32_t B, int32_t bpe, int32_t T, float *cov_re, float *cov_im)
 {
     if (!c) return GAT_ERR_ARG;
-    const Refusal r = st_cov_plan(sig, B, bpe, T, cov_re, cov_im);
+    StCovPlan plan{};
+    const Refusal r = st_cov_plan(sig, B, bpe, T, cov_re, cov_im, c->num_cus, &plan);
     if (r.code != GAT_OK) return fail(c, r.code, r.msg);
     if (T == 1) return gat_spatial_covariance(c, sig, B, bpe, cov_re, cov_im); // one tap: the spatial covariance, and its bits
     GAT_ENTER(c, "gat_spacetime_covariance");
-    const int M = sig->num_ants, Q = M * T;
-    const long long Ns = sig->num_samples - T + 1; // snapshots of a block
-    const StCovGeom geo = st_cov_geom(M, T);
-    const size_t slice = (size_t)2 * Q * Q * sizeof(float);
-    // estimates per launch: one workgroup each at least, within the scratch bound
-    for (EstimateBatches t(B, bpe, slice, kMaxStCovScratch); t.next();) {
-        const long long want = (long long)c->num_cus * 4; // workgroups of the launch
-        const EstimateSplit sp = split_estimate(std::min<long long>(bpe, t.bn), Ns, geo.chunk, 8ll * geo.chunk, std::max<long long>(1, want / t.en));
-        const int32_t rc = ensure_partial(c, (size_t)t.en * (size_t)sp.G * slice);
-        if (rc != GAT_OK) return rc;
-        const size_t off = block_offset_bytes(sig, t.b0);
-        CovArgs a{};
-        a.re = static_cast<const char *>(sig->re) + off;
-        a.im = sig->im ? static_cast<const char *>(sig->im) + off : nullptr;
-        a.M = M;
-        a.B = t.bn;
-        a.bpe = bpe;
-        a.E = t.en;
-        a.G = (int)sp.G;
-        a.splits = (int)sp.splits;
-        a.N = Ns;
-        a.ant_stride = sig->ant_stride;
-        a.block_stride = sig->block_stride;
-        a.seg_len = sp.seg_len;
+    const int Q = plan.Q;
+    return enqueue_estimates<CovArgs>(c, sig, plan.est, [&](CovArgs a, const EstimateLaunches &t) -> int32_t {
         a.partial = c->d_partial;
         GAT_HIP(c, launch_st_cov(a, T, sig->layout, c->stream));
-        GAT_HIP(c, launch_cov_finish(c->d_partial, Q, t.en, (int)sp.G, cov_re + (size_t)t.e0 * Q * Q, cov_im + (size_t)t.e0 * Q * Q, c->stream));
-    }
-    return GAT_OK;
+        GAT_HIP(c, launch_cov_finish(c->d_partial, Q, t.en, (int)t.G, cov_re + (size_t)t.e0 * Q * Q, cov_im + (size_t)t.e0 * Q * Q, c->stream));
+        return GAT_OK;
+    });
 }
 
 GAT_API int32_t gat_spacetime_filter(gat_ctx *c, const gat_signal_desc *sig, int32_t B, const double *w_re, const double *w_im, int32_t T, int32_t J,

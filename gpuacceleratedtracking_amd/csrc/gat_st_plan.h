@@ -1,10 +1,10 @@
 // gat_st_plan.h -- the pure part of gat_spacetime_covariance and gat_spacetime_filter (include/gat.h): their refusals, the
 // filter's choice between the tiled and the general kernel, the geometry of both and the work split, as a function of the call's
-// arguments alone.  No HIP call and no HIP header: the device entry points, the host twin and a stand-alone test program
-// (tests/stplan) compile the same text.
+// arguments alone.  No HIP call and no HIP header: the device entry points, the host twin and the stand-alone test programs
+// (tests/stplan; the covariance's split: tests/estplan) compile the same text.
 #pragma once
 
-#include "gat_sig_plan.h"
+#include "gat_est_plan.h"
 
 namespace gat {
 
@@ -111,12 +111,34 @@ inline StCovGeom st_cov_geom(int M, int T)
     return g;
 }
 
-// The covariance call's refusals (num_taps == 1 is forwarded to gat_spatial_covariance after them).
+constexpr size_t kStCovScratchCap = (size_t)256 << 20; // bytes of the workgroups' slices of one launch; more estimates go in batches
+
+// The covariance call's refusals alone
 inline Refusal st_cov_plan(const gat_signal_desc *sig, int32_t B, int32_t bpe, int32_t T, const float *cov_re, const float *cov_im)
 {
     if (!sig || !cov_re || !cov_im) return {GAT_ERR_ARG, "null argument"};
     if (B < 1 || bpe < 1) return {GAT_ERR_ARG, "num_blocks and blocks_per_estimate must be positive"};
     return st_check_signal(sig, B, T, {GAT_ERR_UNSUPPORTED, "chan_stride must be 0 (one signal, one covariance)"});
+}
+
+// The split is over a block's snapshots (est.N = N - T + 1); a slice is [2][Q][Q] floats, Q = M * T.
+struct StCovPlan {
+    int Q;
+    EstimatePlan est;
+};
+
+// The whole covariance call (num_taps == 1 is forwarded to gat_spatial_covariance after the refusals: its plan is cov_plan's).
+// *plan is written only with GAT_OK.
+inline Refusal st_cov_plan(const gat_signal_desc *sig, int32_t B, int32_t bpe, int32_t T, const float *cov_re, const float *cov_im, int num_cus,
+                           StCovPlan *plan)
+{
+    if (!plan) return {GAT_ERR_ARG, "null argument"};
+    const Refusal r = st_cov_plan(sig, B, bpe, T, cov_re, cov_im);
+    if (r.code != GAT_OK) return r;
+    const int Q = sig->num_ants * T;
+    const long long chunk = st_cov_geom(sig->num_ants, T).chunk;
+    *plan = {Q, {B, bpe, sig->num_samples - T + 1, chunk, 8 * chunk, (long long)num_cus * 4, (size_t)2 * Q * Q * sizeof(float), kStCovScratchCap}};
+    return {GAT_OK, nullptr};
 }
 
 } // namespace gat

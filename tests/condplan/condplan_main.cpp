@@ -1,9 +1,8 @@
 // Stand-alone check of the pure plans of the operators over raw samples: the sample conditioner's (csrc/gat_cond_plan.h), the
-// sample beamformer's (csrc/gat_beam_plan.h) and the pieces they share with the covariance and the statistics
-// (csrc/gat_sig_plan.h), over a few thousand random cases each.  Every planned call must cover each (block, sample) exactly once
-// through the units the kernels walk, dealt to the grid exactly once, with the streaming kernel chosen exactly under its rule;
-// every documented refusal must return its code with nothing planned; the estimate batches must tile the estimates and every
-// estimate's workgroups its (block, sample) pairs.  Built with -fsanitize=address,undefined by
+// sample beamformer's (csrc/gat_beam_plan.h) and the pieces they share (csrc/gat_sig_plan.h), over a few thousand random cases
+// each.  Every planned call must cover each (block, sample) exactly once through the units the kernels walk, dealt to the grid
+// exactly once, with the streaming kernel chosen exactly under its rule; every documented refusal must return its code with
+// nothing planned.  (The estimating operators' split and batches: tests/estplan.)  Built with -fsanitize=address,undefined by
 // tests/test_condition_plan_host.py.  No memory behind the descriptors is ever touched: the plans read addresses, not data.
 #include <cstdint>
 #include <cstdio>
@@ -234,69 +233,6 @@ int sweep_beam_plans(std::mt19937_64 &rng)
     return streamed;
 }
 
-// The estimating operators' split (gat_spatial_covariance, gat_sample_stats): the batches must tile the estimates, and inside a
-// batch the kernels' walk -- estimate e owns blocks [e * bpe, min(B, (e + 1) * bpe)) of its launch and G workgroups; its unit u
-// is (block u / splits, segment u % splits); workgroup g takes units g, g + G, ... -- must cover every (block, sample) once.
-void sweep_estimate_splits(std::mt19937_64 &rng)
-{
-    auto pick = [&](long long lo, long long hi) { return (long long)(rng() % (uint64_t)(hi - lo + 1)) + lo; };
-    long batches = 0, batched_calls = 0, split_calls = 0;
-    for (int it = 0; it < 3000; ++it) {
-        const int B = (int)(it % 3 == 0 ? pick(1, 400) : pick(1, 12));
-        const int bpe = (int)(it % 4 == 0 ? B + pick(1, 5) : it % 4 == 1 ? 1 : pick(1, B)); // beyond B; one block; a last estimate that may be short
-        const long long round_to = pick(0, 2) == 0 ? pick(1, 9) : 64 * pick(1, 32);
-        const long long N = it % 5 == 0 ? pick(1, round_to) : pick(1, 3000); // N < round_to among them
-        const long long min_seg = round_to * pick(1, 8);
-        const long long want = pick(0, 3) == 0 ? pick(1, 16) : 64 * pick(1, 64);
-        const size_t slice = (size_t)pick(1, 40000);
-        const int E = (B + bpe - 1) / bpe;
-        // a cap that holds every estimate, some of them (E above e_max), or not even one slice
-        const size_t cap = it % 3 == 0 ? slice * (size_t)pick(1, E) + (size_t)pick(0, (long long)slice - 1) : it % 3 == 1 ? slice * (size_t)E * 4 : (size_t)pick(1, (long long)slice);
-        std::vector<unsigned char> hits((size_t)B * (size_t)N, 0);
-        int next_e = 0;
-        long here = 0;
-        bool split = false;
-        for (EstimateBatches t(B, bpe, slice, cap); t.next(); ++here) {
-            CHECK(t.e0 == next_e && t.en >= 1 && t.e0 + t.en <= E, "batch [%d, +%d) after %d of %d estimates", t.e0, t.en, next_e, E);
-            CHECK((size_t)t.en * slice <= cap || t.en == 1, "a batch of %d estimates beyond the cap", t.en);
-            CHECK(t.b0 == t.e0 * bpe && t.bn >= 1 && t.b0 + t.bn <= B && (t.e0 + t.en == E ? t.b0 + t.bn == B : t.bn == t.en * bpe), "batch blocks [%d, +%d)", t.b0, t.bn);
-            if (!(t.e0 == next_e && t.en >= 1 && t.b0 >= 0 && t.bn >= 1 && t.b0 + t.bn <= B)) break;
-            next_e = t.e0 + t.en;
-            const long long per_est = want / t.en < 1 ? 1 : want / t.en;
-            const EstimateSplit sp = split_estimate(bpe < t.bn ? bpe : t.bn, N, round_to, min_seg, per_est);
-            CHECK(sp.seg_len > 0 && sp.seg_len % round_to == 0, "seg_len %lld for round_to %lld", sp.seg_len, round_to);
-            CHECK(sp.splits >= 1 && (sp.splits - 1) * sp.seg_len < N && sp.splits * sp.seg_len >= N, "splits %lld of %lld samples for N %lld", sp.splits, sp.seg_len, N);
-            CHECK(sp.splits == 1 || sp.splits <= N / min_seg, "segments below min_seg: %lld splits of N %lld, min_seg %lld", sp.splits, N, min_seg);
-            const long long blocks = bpe < t.bn ? bpe : t.bn; // of every estimate but a short last one, whose spare workgroups find no unit
-            CHECK(sp.G >= 1 && sp.G <= per_est && sp.G <= blocks * sp.splits, "G %lld for per_est %lld, %lld blocks", sp.G, per_est, blocks);
-            if (!(sp.seg_len > 0 && sp.splits >= 1 && sp.G >= 1)) break;
-            split |= sp.splits > 1;
-            for (int e = 0; e < t.en; ++e) { // the launch sees blocks [0, bn) from the batch's offset
-                const int b0 = e * bpe, nb = t.bn - b0 < bpe ? t.bn - b0 : bpe;
-                CHECK(nb >= 1, "an estimate without blocks");
-                const long long units = (long long)nb * sp.splits;
-                for (long long g = 0; g < sp.G; ++g)
-                    for (long long u = g; u < units; u += sp.G) {
-                        const int b = t.b0 + b0 + (int)(u / sp.splits);
-                        const long long n0 = (u % sp.splits) * sp.seg_len, n1 = n0 + sp.seg_len < N ? n0 + sp.seg_len : N;
-                        CHECK(b < B && n0 < n1, "unit %lld: block %d samples [%lld, %lld)", u, b, n0, n1);
-                        if (!(b < B && n0 < n1)) continue;
-                        for (long long n = n0; n < n1; ++n) ++hits[(size_t)b * (size_t)N + (size_t)n];
-                    }
-            }
-        }
-        CHECK(next_e == E, "the batches end at estimate %d of %d", next_e, E);
-        for (size_t i = 0; i < hits.size(); ++i)
-            if (hits[i] != 1) {
-                CHECK(false, "estimates: block %zu sample %zu covered %d times", i / (size_t)N, i % (size_t)N, (int)hits[i]);
-                break;
-            }
-        batches += here, batched_calls += here > 1, split_calls += split;
-    }
-    std::printf("split 3000 estimating calls (%ld in several batches, %ld with split blocks)\n", batched_calls, split_calls);
-    CHECK(batches >= 3000 && batched_calls > 300 && split_calls > 300, "the estimate sweep lost its balance");
-}
-
 } // namespace
 
 int main()
@@ -412,7 +348,6 @@ int main()
     }
     CHECK(planned == 4000 && streamed > 1000 && streamed < 3000, "the sweep lost its balance");
     sweep_beam_plans(rng);
-    sweep_estimate_splits(rng);
     std::printf("planned %d calls (%d streaming, %d in place), %d failures\n", planned, streamed, in_place, failures);
     return failures ? 1 : 0;
 }

@@ -1,4 +1,4 @@
-"""GPU tests of the antenna-array path over its whole domain and work split (csrc/gat_array.hip, csrc/gat_array_api.cpp):
+"""GPU tests of the antenna-array path over its whole domain and work split (csrc/gat_array.hip, csrc/gat_array_plan.h):
 every antenna count, every regime of the covariance's work split, the edges of the value domain, the device weights and
 weighted loop update against their host twins and the FP64 numpy reference (tests/array_ref.py), and the beamformer under
 cancellation.
@@ -8,15 +8,16 @@ max(helpers.RTOL, 3 x f32ref), where f32ref is the same metric of numpy's comple
 (array_ref.covariance_f32) against the FP64 reference -- the float32 reference's own error, printed by every check --, and
 the factor 3 is room for another summation order.  Integer layouts whose sums stay below 2^24 are compared exactly.
 
-The work split (csrc/gat_array_kernels.h, CovArgs; csrc/gat_array_api.cpp): a launch wants W = 8 CUs workgroups for the
-streaming kernel (M <= 8, aligned) and W = 4 CUs for the tiled one, per_est = max(1, W / E) of them for each of its E
-estimates.  With blocks = min(bpe, B) < per_est a block is cut into splits = min(ceil(per_est / blocks), max(1, N / min_seg))
-segments, of a length rounded up to `round_to` (splits is then ceil(N / seg_len)); min_seg = 4 round_to with round_to =
-256 loads of 16 bytes (1024 / 512 / 1024 / 2048 samples by layout) for the streaming kernel, min_seg = 8 round_to with
-round_to = the tile geometry's chunk for the tiled one.  G = min(blocks x splits, per_est) workgroups share an estimate's
-blocks x splits units.  An entry call takes at most e_max = min(2^20, 256 MB / (8 M^2 bytes)) estimates per launch.  The
-regime tests below state their arithmetic for any CU count from 64 to 512, that is W in 256 .. 2048 (tiled) and
-512 .. 4096 (streaming)."""
+The work split is the covariance's pure plan: cov_plan (csrc/gat_array_plan.h) states the call's rule, and the walk over
+its launches is csrc/gat_est_plan.h.  A launch wants W = 8 CUs workgroups for the streaming kernel (M <= 8, aligned) and
+W = 4 CUs for the tiled one, per_est = max(1, W / E) of them for each of its E estimates.  With blocks = min(bpe, B) <
+per_est a block is cut into splits = min(ceil(per_est / blocks), max(1, N / min_seg)) segments, of a length rounded up to
+`round_to` (splits is then ceil(N / seg_len)); min_seg = 4 round_to with round_to = 256 loads of 16 bytes (1024 / 512 /
+1024 / 2048 samples by layout) for the streaming kernel, min_seg = 8 round_to with round_to = the tile geometry's chunk for
+the tiled one.  G = min(blocks x splits, per_est) workgroups share an estimate's blocks x splits units.  An entry call
+takes at most e_max = min(2^20, 256 MB / (8 M^2 bytes)) estimates per launch.  The regime tests below state their
+arithmetic for any CU count from 64 to 512, that is W in 256 .. 2048 (tiled) and 512 .. 4096 (streaming); the plan's own
+host test (tests/estplan) pins the same numbers for each of those device sizes."""
 import ctypes as C
 
 import numpy as np

@@ -1,8 +1,9 @@
 """The pure plans of the operators over raw samples -- gat_condition_samples (csrc/gat_cond_plan.h), gat_beamform_samples
-(csrc/gat_beam_plan.h) and what they share with the covariance and the statistics (csrc/gat_sig_plan.h: descriptor check, fast-path
-rule, overlap test, work splits, estimate batches) -- compiled stand-alone with their own main (tests/condplan/condplan_main.cpp)
-under AddressSanitizer and UBSan, and run: a few thousand random cases each, every (block, sample) covered exactly once, every
-documented refusal with nothing planned.  The program stands alone; nothing is loaded into Python."""
+(csrc/gat_beam_plan.h) and what they share (csrc/gat_sig_plan.h: descriptor check, fast-path rule, overlap test, the chunk split)
+-- compiled stand-alone with their own main (tests/condplan/condplan_main.cpp) under AddressSanitizer and UBSan, and run: a few
+thousand random cases each, every (block, sample) covered exactly once, every documented refusal with nothing planned.  The
+estimating operators' split and batches are tests/test_estimate_plan_host.py's.  The program stands alone; nothing is loaded
+into Python."""
 import os
 import shutil
 import subprocess
