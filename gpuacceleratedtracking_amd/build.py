@@ -30,7 +30,8 @@ HEADERS = [os.path.join(CSRC, "gat_internal.h"), os.path.join(CSRC, "gat_sig_pla
            os.path.join(CSRC, "gat_cond.h"), os.path.join(CSRC, "gat_cond_plan.h"), os.path.join(CSRC, "gat_cond_kernels.h"),
            os.path.join(CSRC, "gat_fir.h"), os.path.join(CSRC, "gat_fir_plan.h"), os.path.join(CSRC, "gat_fir_kernels.h"),
            os.path.join(CSRC, "gat_sample_load.h"), os.path.join(CSRC, "gat_spec.h"), os.path.join(CSRC, "gat_spec_plan.h"),
-           os.path.join(CSRC, "gat_spec_kernels.h"), os.path.join(CSRC, "gat_acq_check.h"), os.path.join(CSRC, "gat_acq_fft.h"),
+           os.path.join(CSRC, "gat_spec_kernels.h"), os.path.join(CSRC, "gat_acq_check.h"), os.path.join(CSRC, "gat_acq_plan.h"),
+           os.path.join(CSRC, "gat_acq_frame.h"), os.path.join(CSRC, "gat_acq_fft.h"),
            os.path.join(CSRC, "gat_acq_fft_plan.h"), os.path.join(CSRC, "gat_acq_fft_kernels.h"),
            os.path.join(CSRC, "gat_st.h"), os.path.join(CSRC, "gat_st_plan.h"), os.path.join(CSRC, "gat_st_kernels.h"),
            os.path.join(CSRC, "gat_mon.h"), os.path.join(CSRC, "gat_mon_plan.h"), os.path.join(CSRC, "gat_mon_kernels.h"),

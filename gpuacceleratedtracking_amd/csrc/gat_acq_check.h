@@ -1,6 +1,6 @@
-// gat_acq_check.h -- the refusals that both acquisition entry points (gat_acquire: gat_acq_api.cpp, gat_acquire_fft:
-// gat_acq_fft_api.cpp through gat_acq_fft_plan.h) and gat_acq_stats_host make about a gat_acq_config, stated once.  No HIP call
-// and no HIP header.
+// gat_acq_check.h -- the refusals that both acquisition entry points (through the call check of gat_acq_plan.h), the FFT search's
+// plan (gat_acq_fft_plan.h, which is also called bare) and gat_acq_stats_host make about a gat_acq_config, stated once.  No HIP
+// call and no HIP header.
 #pragma once
 
 #include <cmath>

@@ -1,13 +1,13 @@
 // gat_acq_fft_api.cpp -- host side of the FFT acquisition search (include/gat.h gat_acquire_fft, gat_acquire_fft_plan,
 // gat_acquire_fft_host): the launch sequence behind the pure plan of gat_acq_fft_plan.h -- {twiddles; per unit batch: replica
-// spectra; per Doppler batch: signal spectra; per step: products into the grid} then {group sum, statistics} of gat_acq.hip --
-// and the host twin, which runs the loops of gat_acq_fft.h.  The kernels are gat_acq_fft.hip.
+// spectra; per Doppler batch: signal spectra; per step: products into the grid}, inside the frame both searches share
+// (gat_acq_frame.h: its tail is {group sum, statistics} of gat_acq.hip) -- and the host twin, which runs the loops of gat_acq_fft.h.
+// The kernels are gat_acq_fft.hip.
 #include <algorithm>
 
 #include "gat_acq_fft.h"
 #include "gat_acq_fft_kernels.h"
-#include "gat_acq_kernels.h"
-#include "gat_ctx.h"
+#include "gat_acq_frame.h"
 
 using namespace gat;
 
@@ -45,91 +45,42 @@ GAT_API int32_t gat_acquire_fft_host(const gat_signal_desc *sig, int32_t B, cons
 GAT_API int32_t gat_acquire_fft(gat_ctx *c, const gat_signal_desc *sig, int32_t B, const int32_t *prns, int32_t P, double fs,
                                 const gat_acq_config *cfg_in, float *power_dev, gat_acq_result *res)
 {
-    if (!c) return GAT_ERR_ARG;
-    if (!sig || !prns || !res) return fail(c, GAT_ERR_ARG, "null argument");
-    if (!c->d_codes) return fail(c, GAT_ERR_STATE, "gat_set_codes has not been called");
-    if (!cfg_in) return fail(c, GAT_ERR_ARG, "null config");
-    {
-        const Refusal r = acq_check_config(cfg_in, P, cfg_in->num_doppler_bins, cfg_in->num_code_bins, fs);
-        if (r.code != GAT_OK) return fail(c, r.code, r.msg);
-    }
-    gat_acq_config cfg = *cfg_in;
-    cfg.struct_size = sizeof(gat_acq_config);
-    if (cfg.code_length == 0) cfg.code_length = c->Lc;
-    if (cfg.code_length != c->Lc) return fail(c, GAT_ERR_ARG, "config.code_length differs from the bound code table");
-    if (B < 1) return fail(c, GAT_ERR_ARG, "num_blocks must be positive");
-    for (int p = 0; p < P; ++p)
-        if (prns[p] < 0 || prns[p] >= c->P) return fail(c, GAT_ERR_RANGE, "prn outside the code table");
+    gat_acq_config cfg;
+    int32_t rc = acq_check_entry(c, sig, B, prns, P, fs, cfg_in, res, &cfg);
+    if (rc != GAT_OK) return rc;
     AcqFftPlan pl{};
-    {
-        const Refusal r = acq_fft_plan(sig, B, P, fs, &cfg, AcqFftOptions{c->acq_fft_log2, c->acq_fft_dbatch, c->acq_fft_ubatch, 0}, c->num_cus,
-                                       power_dev == nullptr, &pl);
-        if (r.code != GAT_OK) return fail(c, r.code, r.msg);
-    }
-    GAT_ENTER(c, "gat_acquire_fft");
-    {
-        const int32_t rc = ensure_partial(c, pl.bytes);
-        if (rc != GAT_OK) return rc;
-    }
-    unsigned char *scr = reinterpret_cast<unsigned char *>(c->d_partial);
-    int *d_prns = reinterpret_cast<int *>(scr + pl.off_prn);
-    gat_acq_result *d_res = reinterpret_cast<gat_acq_result *>(scr + pl.off_res);
-    float *power = power_dev ? power_dev : reinterpret_cast<float *>(scr + pl.off_pow);
-    GAT_HIP(c, hipMemcpyAsync(d_prns, prns, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-
-    const long long cells = (long long)P * pl.D * pl.J;
-    AcqFftArgs a{};
-    a.re = sig->re;
-    a.im = sig->im;
-    a.M = pl.M;
-    a.B = B;
-    a.N = pl.N;
-    a.ant_stride = sig->ant_stride;
-    a.block_stride = sig->block_stride;
-    a.codes = c->d_codes;
-    a.code_row_stride = c->code_row_stride;
-    a.Lc = c->Lc;
-    a.prns = d_prns;
-    a.P = P;
-    a.D = pl.D;
-    a.J = pl.J;
-    a.s = pl.s;
-    a.ratio = cfg.code_freq_hz / fs;
-    a.fs = fs;
-    a.if_hz = cfg.if_hz;
-    a.f_first = cfg.doppler_first_hz;
-    a.f_step = cfg.doppler_step_hz;
-    a.first_shift = cfg.first_shift;
-    a.L = pl.L, a.L1 = pl.L1, a.L2 = pl.L2, a.tiles = pl.tiles, a.G = pl.G, a.Db = pl.Db, a.Gu = pl.Gu, a.Bb = pl.Bb;
-    a.Jseg = pl.Jseg, a.units = pl.units, a.cells = cells;
-    a.scale = acq_fft_scale(pl.L);
-    a.tw = reinterpret_cast<float2 *>(scr + pl.off_tw);
-    a.C = reinterpret_cast<float2 *>(scr + pl.off_C);
-    a.W = reinterpret_cast<float2 *>(scr + pl.off_W);
-    a.Y = pl.passes == 2 ? reinterpret_cast<float2 *>(scr + pl.off_Y) : nullptr;
-    a.out = pl.Gu > 1 ? reinterpret_cast<float *>(scr + pl.off_part) : power;
-    GAT_HIP(c, launch_acq_fft_twiddles(a, c->stream));
-    for (long long ub = 0; ub < pl.units; ub += pl.Ub) {
-        a.u0 = (int)ub;
-        a.un = (int)std::min<long long>(pl.Ub, pl.units - ub);
-        a.b0 = a.u0 / pl.M;
-        a.bn = (a.u0 + a.un - 1) / pl.M - a.b0 + 1;
-        a.i0 = 0, a.dn = std::min(pl.Db, pl.D);
-        GAT_HIP(c, launch_acq_fft_replica(a, c->stream));
-        for (int i0 = 0; i0 < pl.D; i0 += pl.Db) {
-            a.i0 = i0;
-            a.dn = std::min(pl.Db, pl.D - i0);
-            GAT_HIP(c, launch_acq_fft_signal(a, sig->layout, c->stream));
-            for (int us = a.u0; us < a.u0 + a.un; us += pl.Gu) {
-                a.us = us;
-                GAT_HIP(c, launch_acq_fft_correlate(a, c->stream));
+    const Refusal r = acq_fft_plan(sig, B, P, fs, &cfg, AcqFftOptions{c->acq_fft_log2, c->acq_fft_dbatch, c->acq_fft_ubatch, 0}, c->num_cus,
+                                   power_dev == nullptr, &pl);
+    if (r.code != GAT_OK) return fail(c, r.code, r.msg);
+    rc = acq_run<AcqFftArgs>(c, "gat_acquire_fft", sig, B, prns, P, fs, cfg, pl, pl.Gu, power_dev, res, [&](AcqFftArgs &a, unsigned char *scr) -> int32_t {
+        a.L = pl.L, a.L1 = pl.L1, a.L2 = pl.L2, a.tiles = pl.tiles, a.G = pl.G, a.Db = pl.Db, a.Gu = pl.Gu, a.Bb = pl.Bb;
+        a.Jseg = pl.Jseg, a.units = pl.units, a.cells = (long long)P * pl.D * pl.J;
+        a.scale = acq_fft_scale(pl.L);
+        a.tw = reinterpret_cast<float2 *>(scr + pl.off_tw);
+        a.C = reinterpret_cast<float2 *>(scr + pl.off_C);
+        a.W = reinterpret_cast<float2 *>(scr + pl.off_W);
+        a.Y = pl.passes == 2 ? reinterpret_cast<float2 *>(scr + pl.off_Y) : nullptr;
+        GAT_HIP(c, launch_acq_fft_twiddles(a, c->stream));
+        for (long long ub = 0; ub < pl.units; ub += pl.Ub) {
+            a.u0 = (int)ub;
+            a.un = (int)std::min<long long>(pl.Ub, pl.units - ub);
+            a.b0 = a.u0 / pl.M;
+            a.bn = (a.u0 + a.un - 1) / pl.M - a.b0 + 1;
+            a.i0 = 0, a.dn = std::min(pl.Db, pl.D);
+            GAT_HIP(c, launch_acq_fft_replica(a, c->stream));
+            for (int i0 = 0; i0 < pl.D; i0 += pl.Db) {
+                a.i0 = i0;
+                a.dn = std::min(pl.Db, pl.D - i0);
+                GAT_HIP(c, launch_acq_fft_signal(a, sig->layout, c->stream));
+                for (int us = a.u0; us < a.u0 + a.un; us += pl.Gu) {
+                    a.us = us;
+                    GAT_HIP(c, launch_acq_fft_correlate(a, c->stream));
+                }
             }
         }
-    }
-    if (pl.Gu > 1) GAT_HIP(c, launch_acq_sum_groups(a.out, power, cells, pl.Gu, c->stream));
-    GAT_HIP(c, launch_acq_stats(power, P, pl.D, pl.J, cfg, fs, pl.N, d_prns, d_res, c->stream));
-    GAT_HIP(c, hipMemcpyAsync(res, d_res, (size_t)P * sizeof(gat_acq_result), hipMemcpyDeviceToHost, c->stream));
-    GAT_HIP(c, hipStreamSynchronize(c->stream));
+        return GAT_OK;
+    });
+    if (rc != GAT_OK) return rc;
     c->last = gat_launch_info{};
     c->last.workgroups = (int32_t)std::min<long long>((long long)pl.Gu * P * pl.Db * pl.G * pl.tiles, 2147483647ll);
     c->last.threads = kAcqFftThreads;

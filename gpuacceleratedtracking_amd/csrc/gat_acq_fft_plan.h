@@ -9,7 +9,7 @@
 // (o = s j) lies in segment o / Jseg at lag o mod Jseg -- exactly one (segment, lag) per bin (acq_fft_lag_bin is the inverse).
 #pragma once
 
-#include "gat_acq_check.h"
+#include "gat_acq_plan.h" // AcqScratch; the configuration's refusals (gat_acq_check.h)
 
 #ifndef GAT_HD
 #if defined(__HIPCC__)
@@ -52,14 +52,15 @@ struct AcqFftOptions {
 // Units u = b M + m; unit group k (< Gu) owns the units u = k, k + Gu, ... in order and a slice of its own (Gu > 1), the slices are
 // added in group order; a step is Gu consecutive units from a multiple of Gu on, one to a group.  A unit batch is Ub units (whole
 // steps) whose W spectra are held at once, with the C spectra of the Bb blocks they can span; a Doppler batch is Db bins.
-struct AcqFftPlan {
+struct AcqFftPlan : AcqScratch {
     int L, L1, L2, passes, tiles;
     long long F, N, Jseg;
     int G, P, D, J, s, B, M;
     long long units;
     int Db, Ub, Gu, Bb;
-    // scratch, 256-byte aligned: [results | power (no caller buffer) | twiddles | C | W | Y (two passes) | slices (Gu > 1) | prns]
-    size_t off_res, off_pow, off_tw, off_C, off_W, off_Y, off_part, off_prn, bytes;
+    // scratch, 256-byte aligned: [results | power (no caller buffer) | twiddles | C | W | Y (two passes) | slices (Gu > 1) | prns];
+    // the four regions the tail reads and the total are AcqScratch's (gat_acq_plan.h)
+    size_t off_tw, off_C, off_W, off_Y;
 };
 
 inline size_t acq_fft_align(size_t v) { return (v + 255) & ~(size_t)255; }

@@ -1,5 +1,5 @@
 // gat_acq_kernels.h -- what the acquisition kernels (gat_acq.hip) and their host side (gat_acq_api.cpp) share: the grid
-// kernel's geometry, its arguments and the launchers.
+// kernel's arguments and the launchers.  The geometry is the plan's (gat_acq_plan.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,16 +7,9 @@
 #include <stdint.h>
 
 #include "gat.h"
-#include "gat_acq_check.h" // kAcqMaxCodeStep
+#include "gat_acq_plan.h" // the grid's tile constants; kAcqMaxCodeStep (gat_acq_check.h)
 
 namespace gat {
-
-constexpr int kAcqThreads = 256;    // four wave64
-constexpr int kAcqDopPerWave = 8;   // Doppler bins of one wave's register tile
-constexpr int kAcqCodePerLane = 4;  // code bins of one lane's register tile (lane + 64 r)
-constexpr int kAcqDopTile = kAcqDopPerWave * (kAcqThreads / 64); // 32 Doppler bins per workgroup
-constexpr int kAcqCodeTile = kAcqCodePerLane * 64;               // 256 code bins per workgroup
-constexpr int kAcqChunk = 128;      // samples staged per step (a power of two dividing kAcqThreads)
 
 struct AcqArgs {
     const void *re, *im;

@@ -5,7 +5,9 @@
 // samples), gat_cond_api.cpp (sample conditioning), gat_st_api.cpp (space-time processing).  What the operators over raw samples
 // share is gat_sig_plan.h (through gat_internal.h); the work split of those that reduce blocks to estimates is gat_est_plan.h, filled
 // in by the pure plans cov_plan (gat_array_plan.h), stats_plan (gat_cond_plan.h) and st_cov_plan (gat_st_plan.h) and walked by
-// enqueue_estimates below.
+// enqueue_estimates below.  What the two acquisition searches (gat_acq_api.cpp, gat_acq_fft_api.cpp) share is a header of its own,
+// gat_acq_frame.h: the checks before planning, the common kernel arguments and the frame around each search's launches, over the
+// pure plans of gat_acq_plan.h and gat_acq_fft_plan.h.
 #pragma once
 
 #include <cmath>
