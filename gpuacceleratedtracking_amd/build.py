@@ -5,6 +5,7 @@ that it travels with the repo snapshot to the GPU box (it is git-ignored, not gp
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -21,22 +22,8 @@ SOURCES = ["gat_dc_f0.hip", "gat_dc_f1.hip", "gat_dc_f2.hip", "gat_dc_f3.hip", "
            "gat_spec.hip", "gat_spec_api.cpp", "gat_acq_fft.hip", "gat_acq_fft_api.cpp", "gat_st.hip", "gat_st_api.cpp",
            "gat_mon.hip", "gat_mon_api.cpp", "gat_eig.hip", "gat_eig_api.cpp"]
 # gat_version.cpp is not in SOURCES: it is compiled at every link with the build's identity (git commit, flags)
-HEADERS = [os.path.join(CSRC, "gat_internal.h"), os.path.join(CSRC, "gat_sig_plan.h"), os.path.join(CSRC, "gat_phase.h"), os.path.join(CSRC, "gat_dc.h"),
-           os.path.join(CSRC, "gat_dc_body.inc"), os.path.join(CSRC, "gat_resident.h"), os.path.join(CSRC, "gat_ctx.h"),
-           os.path.join(CSRC, "gat_acq.h"), os.path.join(CSRC, "gat_acq_kernels.h"), os.path.join(CSRC, "gat_loop.h"),
-           os.path.join(CSRC, "gat_est_plan.h"), os.path.join(CSRC, "gat_array_plan.h"),
-           os.path.join(CSRC, "gat_array.h"), os.path.join(CSRC, "gat_array_kernels.h"), os.path.join(CSRC, "gat_beam_plan.h"),
-           os.path.join(CSRC, "gat_beam_kernels.h"),
-           os.path.join(CSRC, "gat_cond.h"), os.path.join(CSRC, "gat_cond_plan.h"), os.path.join(CSRC, "gat_cond_kernels.h"),
-           os.path.join(CSRC, "gat_fir.h"), os.path.join(CSRC, "gat_fir_plan.h"), os.path.join(CSRC, "gat_fir_kernels.h"),
-           os.path.join(CSRC, "gat_sample_load.h"), os.path.join(CSRC, "gat_spec.h"), os.path.join(CSRC, "gat_spec_plan.h"),
-           os.path.join(CSRC, "gat_spec_kernels.h"), os.path.join(CSRC, "gat_acq_check.h"), os.path.join(CSRC, "gat_acq_plan.h"),
-           os.path.join(CSRC, "gat_acq_frame.h"), os.path.join(CSRC, "gat_acq_fft.h"),
-           os.path.join(CSRC, "gat_acq_fft_plan.h"), os.path.join(CSRC, "gat_acq_fft_kernels.h"),
-           os.path.join(CSRC, "gat_st.h"), os.path.join(CSRC, "gat_st_plan.h"), os.path.join(CSRC, "gat_st_kernels.h"),
-           os.path.join(CSRC, "gat_mon.h"), os.path.join(CSRC, "gat_mon_plan.h"), os.path.join(CSRC, "gat_mon_kernels.h"),
-           os.path.join(CSRC, "gat_eig.h"), os.path.join(CSRC, "gat_eig_plan.h"), os.path.join(CSRC, "gat_eig_kernels.h"),
-           os.path.join(ROOT, "include", "gat.h")]
+# every header a source may include (csrc/*.h, csrc/*.inc, the public header): a newer one rebuilds every object
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc"))) + [os.path.join(ROOT, "include", "gat.h")]
 
 
 def hipcc_path() -> str:
@@ -130,7 +117,7 @@ def build_libgat(force: bool = False, verbose: bool = False, extra_flags: tuple[
         sp = os.path.join(CSRC, src)
         # flags that only touch the fused vector kernel (-DGAT_DC_*): every other object is shared with the main build
         vector_tu = src.startswith("gat_dc_f") or src.startswith("gat_resident_f")  # both are made of gat_dc_body.inc
-        shared = dc_only and not vector_tu and src not in ("gat_api.cpp", "gat_planner.cpp", "gat_resident_api.cpp")  # the planner shares gat_internal.h
+        shared = dc_only and not vector_tu and src not in ("gat_api.cpp", "gat_planner.cpp", "gat_resident_api.cpp")  # the planner shares gat_corr_plan.h
         obj = os.path.join(base_objdir if shared else objdir, os.path.splitext(src)[0] + ".o")
         objs.append(obj)
         extra_here = () if shared else extra_flags

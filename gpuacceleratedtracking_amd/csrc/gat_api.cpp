@@ -200,13 +200,21 @@ void key_put_sig(std::vector<unsigned char> &key, const gat_signal_desc *sig)
     key_put(key, sig->num_samples); key_put(key, sig->ant_stride); key_put(key, sig->block_stride); key_put(key, sig->chan_stride);
 }
 // The context: kernel-selection knobs and library-owned buffers.  This is the one place that knows which members of the
-// context a recorded launch bakes in (gat_ctx.h, LoopGraph).
+// context a recorded launch bakes in (gat_ctx.h, LoopGraph): everything the correlator's plan reads (CorrKnobs and CorrTables of
+// gat_corr_plan.h, field by field: padding) and the scratch.  A field added to either struct fails the build here until it is keyed.
+static_assert(sizeof(CorrKnobs) == sizeof(long long) + 18 * sizeof(int) && sizeof(CorrTables) == 3 * sizeof(void *) + 6 * sizeof(int),
+              "CorrKnobs / CorrTables changed: key the new field in key_put_ctx");
 void key_put_ctx(std::vector<unsigned char> &key, const gat_ctx *c)
 {
-    key_put(key, c->mc_mode); key_put(key, c->mc_i16_terms); key_put(key, c->mc_nct); key_put(key, c->max_aw); key_put(key, c->max_kt); key_put(key, c->max_bpw); key_put(key, c->force_bpw);
-    key_put(key, c->wgs_per_cu); key_put(key, c->max_depth); key_put(key, c->one_wave); key_put(key, c->keep_l2); key_put(key, c->align_head);
-    key_put(key, c->aw2); key_put(key, c->quads); key_put(key, c->bit_tables); key_put(key, c->seg_cap);
-    key_put(key, c->d_codes); key_put(key, c->d_code_bits); key_put(key, c->Lc); key_put(key, c->P);
+    const CorrKnobs &k = c->knobs;
+    key_put(key, k.one_wave_min); key_put(key, k.mc_mode); key_put(key, k.mc_nct); key_put(key, k.mc_i16_terms); key_put(key, k.max_ant_tile);
+    key_put(key, k.max_aw); key_put(key, k.max_kt); key_put(key, k.max_bpw); key_put(key, k.force_bpw); key_put(key, k.wgs_per_cu);
+    key_put(key, k.one_wave); key_put(key, k.one_wave_seg); key_put(key, k.max_depth); key_put(key, k.keep_l2); key_put(key, k.quads);
+    key_put(key, k.bit_tables); key_put(key, k.aw2); key_put(key, k.seg_cap); key_put(key, k.align_head);
+    // (CorrTables ends in four bytes of padding that a new int would fill unseen by sizeof: the binding counts its fields)
+    const auto [d_codes, d_code_bits, d_zeros, Lc, P, code_row_stride, code_bits_stride, num_cus] = corr_tables(*c);
+    key_put(key, d_codes); key_put(key, d_code_bits); key_put(key, d_zeros); key_put(key, Lc); key_put(key, P);
+    key_put(key, code_row_stride); key_put(key, code_bits_stride); key_put(key, num_cus);
     key_put(key, c->d_partial); key_put(key, c->partial_bytes);
 }
 
@@ -221,26 +229,26 @@ struct OptionDesc {
 #define GAT_OPT_INT(member) [](gat_ctx &c, long long v) { c.member = (int)v; }
 constexpr OptionDesc kOptions[] = {
     {"sync_flag_wgs", 0, 1 << 20, GAT_OPT_INT(flag_max_wgs)},  // largest launch (workgroups) that carries the completion flag; 0: never
-    {"max_ant_tile", 1, kMaxAntTile, GAT_OPT_INT(max_ant_tile)}, // antennas per wave
-    {"dc_aw", 1, 4, GAT_OPT_INT(max_aw)},                      // antenna tiles (waves) per workgroup, cap
-    {"dc_kt", 1, 4, GAT_OPT_INT(max_kt)},                      // channels per workgroup, cap
-    {"dc_bpw", 1, 1 << 20, GAT_OPT_INT(max_bpw)},              // consecutive blocks per workgroup, cap
-    {"dc_bpw_force", 0, 1 << 20, GAT_OPT_INT(force_bpw)},      // blocks per workgroup whatever the planner's rule says (0: planner; A/B runs)
-    {"dc_wgs_per_cu", 0, 1024, GAT_OPT_INT(wgs_per_cu)},       // workgroups per CU the split planner aims for (0: by instance)
-    {"dc_one_wave", 0, 1, GAT_OPT_INT(one_wave)},              // one-wave workgroups allowed (0: never)
+    {"max_ant_tile", 1, kMaxAntTile, GAT_OPT_INT(knobs.max_ant_tile)}, // antennas per wave
+    {"dc_aw", 1, 4, GAT_OPT_INT(knobs.max_aw)},                      // antenna tiles (waves) per workgroup, cap
+    {"dc_kt", 1, 4, GAT_OPT_INT(knobs.max_kt)},                      // channels per workgroup, cap
+    {"dc_bpw", 1, 1 << 20, GAT_OPT_INT(knobs.max_bpw)},              // consecutive blocks per workgroup, cap
+    {"dc_bpw_force", 0, 1 << 20, GAT_OPT_INT(knobs.force_bpw)},      // blocks per workgroup whatever the planner's rule says (0: planner; A/B runs)
+    {"dc_wgs_per_cu", 0, 1024, GAT_OPT_INT(knobs.wgs_per_cu)},       // workgroups per CU the split planner aims for (0: by instance)
+    {"dc_one_wave", 0, 1, GAT_OPT_INT(knobs.one_wave)},              // one-wave workgroups allowed (0: never)
     // (the one member that is no int)
-    {"dc_one_wave_min", -1, 1ll << 40, [](gat_ctx &c, long long v) { c.one_wave_min = v; }}, // fewest (block, channel, tile) groups for them (-1: 32 per CU)
-    {"dc_ow_seg", 1, kUcarSteps, GAT_OPT_INT(one_wave_seg)},   // steps per replica segment of a one-wave workgroup
-    {"dc_depth", 1, 2, GAT_OPT_INT(max_depth)},                // cap of the sample prefetch depth (register sets per wave)
-    {"dc_keep_l2", -1, 1, GAT_OPT_INT(keep_l2)},               // sample loads: -1 by rule (plain when channel groups share a tile through L2), 0 non-temporal, 1 plain
-    {"dc_quads", -1, 1, GAT_OPT_INT(quads)},                   // replica fill four entries at a time: -1 by rule (the two-channel 2 x 2 tile), 0 never, 1 wherever the code rate allows
-    {"dc_bits", 0, 2, GAT_OPT_INT(bit_tables)},                // chip tables in LDS as sign bits: 0 never, 1 long codes (> 2 KB per PRN), 2 whenever every chip is +-1
-    {"dc_aw2", -1, 1, GAT_OPT_INT(aw2)},                       // the two-channel 2 x 2 tile (two waves of two antennas, two channels each): -1 by rule, 0 never, 1 wherever an instance exists
-    {"dc_seg", 0, kUcarSteps, GAT_OPT_INT(seg_cap)},           // cap of the steps per replica segment of a four-wave workgroup (0: by instance)
+    {"dc_one_wave_min", -1, 1ll << 40, [](gat_ctx &c, long long v) { c.knobs.one_wave_min = v; }}, // fewest (block, channel, tile) groups for them (-1: 32 per CU)
+    {"dc_ow_seg", 1, kUcarSteps, GAT_OPT_INT(knobs.one_wave_seg)},   // steps per replica segment of a one-wave workgroup
+    {"dc_depth", 1, 2, GAT_OPT_INT(knobs.max_depth)},                // cap of the sample prefetch depth (register sets per wave)
+    {"dc_keep_l2", -1, 1, GAT_OPT_INT(knobs.keep_l2)},               // sample loads: -1 by rule (plain when channel groups share a tile through L2), 0 non-temporal, 1 plain
+    {"dc_quads", -1, 1, GAT_OPT_INT(knobs.quads)},                   // replica fill four entries at a time: -1 by rule (the two-channel 2 x 2 tile), 0 never, 1 wherever the code rate allows
+    {"dc_bits", 0, 2, GAT_OPT_INT(knobs.bit_tables)},                // chip tables in LDS as sign bits: 0 never, 1 long codes (> 2 KB per PRN), 2 whenever every chip is +-1
+    {"dc_aw2", -1, 1, GAT_OPT_INT(knobs.aw2)},                       // the two-channel 2 x 2 tile (two waves of two antennas, two channels each): -1 by rule, 0 never, 1 wherever an instance exists
+    {"dc_seg", 0, kUcarSteps, GAT_OPT_INT(knobs.seg_cap)},           // cap of the steps per replica segment of a four-wave workgroup (0: by instance)
     // (the one value that is not stored as given: the tiles per workgroup are 1, 2 or 4, and 3 means 2)
-    {"mc_nct", 0, 4, [](gat_ctx &c, long long v) { c.mc_nct = v == 3 ? 2 : (int)v; }}, // split-bf16 kernel: 32-column channel tiles per workgroup to try first (0 = by rule; A/B runs)
-    {"mc_i16_terms", 2, 3, GAT_OPT_INT(mc_i16_terms)},         // split-bf16 kernel, int16 samples: 2 = the exact two-term split (5 products per sample), 3 = the float path's three terms (8)
-    {"dc_align", 0, 1, GAT_OPT_INT(align_head)},               // blocks walked from the 128-byte line their first sample lies in (1) or from the sample itself (0)
+    {"mc_nct", 0, 4, [](gat_ctx &c, long long v) { c.knobs.mc_nct = v == 3 ? 2 : (int)v; }}, // split-bf16 kernel: 32-column channel tiles per workgroup to try first (0 = by rule; A/B runs)
+    {"mc_i16_terms", 2, 3, GAT_OPT_INT(knobs.mc_i16_terms)},         // split-bf16 kernel, int16 samples: 2 = the exact two-term split (5 products per sample), 3 = the float path's three terms (8)
+    {"dc_align", 0, 1, GAT_OPT_INT(knobs.align_head)},               // blocks walked from the 128-byte line their first sample lies in (1) or from the sample itself (0)
     {"acq_fft_log2", 0, 18, GAT_OPT_INT(acq_fft_log2)},        // gat_acquire_fft: log2 of the transform length, 10 .. 18 (0: the plan's choice; 1 .. 9 and 2^v <= N are refused at the call)
     {"acq_fft_doppler_batch", 0, 1 << 20, GAT_OPT_INT(acq_fft_dbatch)}, // gat_acquire_fft: Doppler bins transformed at a time (0: the plan's choice); changes no bit
     {"acq_fft_unit_batch", 0, 1 << 20, GAT_OPT_INT(acq_fft_ubatch)},    // gat_acquire_fft: (block, antenna) units whose spectra are held at a time (0: the plan's choice); changes no bit
@@ -352,8 +360,8 @@ GAT_API int32_t gat_create(int32_t device, void *hip_stream, gat_ctx **out_ctx)
         for (const char *p = o.name; *p; ++p) env += (char)std::toupper((unsigned char)*p);
         if (const char *v = std::getenv(env.c_str())) (void)set_option(c, o.name, std::atoll(v));
     }
-    if (const char *v = std::getenv("GAT_NO_MFMA")) c->mc_mode = v[0] == '1' ? 0 : 1;
-    if (const char *v = std::getenv("GAT_MC_MODE")) c->mc_mode = (v[0] >= '0' && v[0] <= '3') ? v[0] - '0' : 1;
+    if (const char *v = std::getenv("GAT_NO_MFMA")) c->knobs.mc_mode = v[0] == '1' ? 0 : 1;
+    if (const char *v = std::getenv("GAT_MC_MODE")) c->knobs.mc_mode = (v[0] >= '0' && v[0] <= '3') ? v[0] - '0' : 1;
 #endif
     if ((e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess) {
         delete c;
@@ -848,7 +856,7 @@ GAT_API int32_t gat_set_matrix_core(gat_ctx *c, int32_t enable)
 {
     if (!c) return GAT_ERR_ARG;
     if (enable < GAT_MC_VECTOR || enable > GAT_MC_BF16_SPLIT) return fail(c, GAT_ERR_ARG, "unknown matrix-core mode");
-    c->mc_mode = enable;
+    c->knobs.mc_mode = enable;
     drop_loop_graphs(c);
     return GAT_OK;
 }
@@ -857,9 +865,9 @@ GAT_API int32_t gat_set_vector_tiling(gat_ctx *c, int32_t max_antenna_tiles, int
 {
     if (!c) return GAT_ERR_ARG;
     if (max_antenna_tiles < 0 || max_channels < 0 || max_blocks < 0) return fail(c, GAT_ERR_ARG, "negative cap");
-    if (max_antenna_tiles) c->max_aw = max_antenna_tiles >= 4 ? 4 : (max_antenna_tiles >= 2 ? 2 : 1);
-    if (max_channels) c->max_kt = max_channels >= 4 ? 4 : (max_channels >= 2 ? 2 : 1);
-    if (max_blocks) c->max_bpw = max_blocks;
+    if (max_antenna_tiles) c->knobs.max_aw = max_antenna_tiles >= 4 ? 4 : (max_antenna_tiles >= 2 ? 2 : 1);
+    if (max_channels) c->knobs.max_kt = max_channels >= 4 ? 4 : (max_channels >= 2 ? 2 : 1);
+    if (max_blocks) c->knobs.max_bpw = max_blocks;
     drop_loop_graphs(c);
     return GAT_OK;
 }

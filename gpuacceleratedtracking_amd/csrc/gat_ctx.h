@@ -1,6 +1,7 @@
 // gat_ctx.h -- what the translation units of the C-ABI layer share: the context, error helpers, the entry preamble, scratch and
 // graph housekeeping, the planner's entry points.  The layer: gat_api.cpp (contexts, operators, options, the closed loop),
-// gat_planner.cpp (the correlator call's launch planning), gat_group.cpp (device groups), gat_resident_api.cpp (the resident
+// gat_planner.cpp (the correlator call: the enqueue of what the pure plan of gat_corr_plan.h plans from the context's knobs
+// -- gat_ctx::knobs -- and tables -- corr_tables), gat_group.cpp (device groups), gat_resident_api.cpp (the resident
 // correlator's host side), gat_acq_api.cpp (acquisition), gat_array_api.cpp (antenna arrays), gat_beam_api.cpp (beams of the raw
 // samples), gat_cond_api.cpp (sample conditioning), gat_st_api.cpp (space-time processing).  What the operators over raw samples
 // share is gat_sig_plan.h (through gat_internal.h); the work split of those that reduce blocks to estimates is gat_est_plan.h, filled
@@ -87,24 +88,7 @@ struct gat_ctx {
     std::vector<hipEvent_t> lap_events; // gat_timer_lap: pool, grows to the most laps ever outstanding
     size_t laps = 0;                    // laps recorded since the last gat_timer_laps
     int num_cus = 256;
-    // launch-geometry options: what each means, and its range, is the table kOptions of gat_api.cpp
-    int max_ant_tile = gat::kMaxAntTile;      // option max_ant_tile
-    int max_aw = 4, max_kt = 4, max_bpw = 16; // options dc_aw / dc_kt / dc_bpw (and gat_set_vector_tiling)
-    int force_bpw = 0;                        // option dc_bpw_force
-    int wgs_per_cu = 0;                       // option dc_wgs_per_cu
-    int one_wave = 1;                         // option dc_one_wave
-    long long one_wave_min = -1;              // option dc_one_wave_min
-    int one_wave_seg = gat::kOneWaveSegSteps; // option dc_ow_seg
-    int max_depth = 2;                        // option dc_depth
-    int keep_l2 = -1;                         // option dc_keep_l2
-    int quads = -1;                           // option dc_quads
-    int bit_tables = 1;                       // option dc_bits
-    int aw2 = -1;                             // option dc_aw2
-    int seg_cap = 0;                          // option dc_seg
-    int align_head = 1;                       // option dc_align
-    int mc_mode = 1;                          // GAT_MC_* kernel selection (gat_set_matrix_core)
-    int mc_nct = 0;                           // option mc_nct
-    int mc_i16_terms = 2;                     // option mc_i16_terms
+    gat::CorrKnobs knobs; // the correlator plan's kernel-selection and launch-geometry options (gat_corr_plan.h; kOptions of gat_api.cpp)
     int acq_fft_log2 = 0, acq_fft_dbatch = 0, acq_fft_ubatch = 0; // options acq_fft_log2 / acq_fft_doppler_batch / acq_fft_unit_batch (0: the plan's choice)
     std::string err;
     gat_launch_info last{};
@@ -211,12 +195,11 @@ int32_t tracking_run_shared(gat_ctx *c, const gat_signal_desc *sig, int32_t num_
 int32_t correlate_impl(gat_ctx *c, const gat_signal_desc *sig, const gat_channel_params *params_dev, int32_t B, int32_t K, int32_t L,
                        const int32_t *shifts, double fs, float *out_re, float *out_im, uint32_t flags,
                        const gat_channel_params *params_inline = nullptr);
-// The resident correlator's launch plan (gat_resident_open): the call's validation and every restriction of a resident
-// launch.  a, cfg: the arguments and geometry of the ONE vector launch that would serve the call -- one block, 16-byte
-// aligned, no tail; four-wave workgroups, one antenna tile and one channel each (the resident instances), about max_wgs
-// of them.  GAT_ERR_UNSUPPORTED where the call is no such launch.
-Refusal plan_resident(const gat_ctx &c, const gat_signal_desc *sig, int32_t K, int32_t L, const int32_t *shifts, double fs,
-                      long long max_wgs, DcArgs *a, DcLaunch *cfg);
+// what the correlator plans (corr_plan, corr_plan_resident: gat_corr_plan.h) read of the context besides its knobs, built per call
+inline CorrTables corr_tables(const gat_ctx &c)
+{
+    return {c.d_codes, c.d_code_bits, c.d_zeros, c.Lc, c.P, c.code_row_stride, c.code_bits_stride, c.num_cus};
+}
 // host mirror of the kernels' `bad` predicate for host-resident records: what passes here is not poisoned there
 int32_t validate_params(gat_ctx *c, const gat_channel_params *params_host, size_t n, double reach, double fs);
 // the context's resident correlators (gat_resident_api.cpp): asked to leave before anything that waits for the whole device

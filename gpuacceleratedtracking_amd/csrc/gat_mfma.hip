@@ -45,6 +45,7 @@ struct ChanInfo { // per channel slot of the workgroup, in LDS
     double ratio, tau, step, phi;
     int prn, valid, bad, pad;
 };
+static_assert(sizeof(ChanInfo) * 20 <= 1024, "channel table must fit its 1 KB slot");
 
 } // namespace
 
@@ -378,12 +379,6 @@ hipError_t launch_mfma(const MfArgs &a, int nct, unsigned grid, unsigned lds_byt
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
-}
-
-size_t mfma_lds_bytes(int nct, int ct, int rep_stride, int code_row_stride, int codes_in_lds)
-{
-    static_assert(sizeof(ChanInfo) * 20 <= 1024, "channel table must fit its 1 KB slot");
-    return mf_lds_bytes(nct, ct, rep_stride, code_row_stride, codes_in_lds);
 }
 
 } // namespace gat

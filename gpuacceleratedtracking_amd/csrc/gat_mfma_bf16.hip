@@ -343,6 +343,7 @@ struct ChanInfoB { // per channel slot of the workgroup, in LDS
     int prn, valid, bad;
     int inc_ok;     // fewer than Lc chips per step: the code index can be advanced by floor differences
 };
+static_assert(sizeof(ChanInfoB) * kMbMaxSlots <= kHeader, "channel table must fit the header");
 static_assert(sizeof(ChanInfoB) == 64, "ChanInfoB layout");
 
 constexpr int tile_samples(int RT, int NCT) { return mb_tile_samples(RT, NCT); }
@@ -945,21 +946,6 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
         }
     }
 }
-
-int mfma_bf16_tile_samples(int rt, int nct) { return tile_samples(rt, nct); }
-int mfma_bf16_max_chain() { return kMaxChain; }
-int mfma_bf16_max_slots() { return kMbMaxSlots; }
-int mfma_bf16_threads(int rt, int nct) { return mb_threads(rt, nct); }
-int mfma_bf16_producer_threads(int rt, int nct) { return mb_threads(rt, nct) - 64 * consumer_waves(rt, nct); }
-
-int mfma_bf16_slots(int nct, int L, int K) { return mb_slots(nct, L, K); }
-
-size_t mfma_bf16_lds_bytes(int rt, int nct, int fmt, int nslots, int rep_stride, int code_bits_stride, int mode)
-{
-    static_assert(sizeof(ChanInfoB) * kMbMaxSlots <= kHeader, "channel table must fit the header");
-    return mb_lds_bytes(rt, nct, fmt, nslots, rep_stride, code_bits_stride, mode);
-}
-int mfma_bf16_mode(int rt, int nct, int fmt, bool force_three) { return mb_mode(rt, nct, fmt, force_three); }
 
 namespace {
 // the operand split of the launch: the host's a.mb_mode, which for int16 may be the three-term path on request

@@ -40,8 +40,6 @@
 
 namespace gat {
 
-constexpr bool dc_resident_instance(int mt, int l) { return dc_instance(mt, l, 4, 1, 1, 4, 1); }
-
 struct ResidentEnv {
     const unsigned *line; // LDS: the call's doorbell lines
     float *stage;         // LDS: the workgroup's sums, in the order of the body's output loop (value o = 2 * (l * MT + m) + comp)

@@ -152,8 +152,8 @@ GAT_API int32_t gat_resident_open(gat_ctx *c, const gat_signal_desc *sig, int32_
     // lengthen the host's (two or three result lines each): best around 128 (profiles/r04/resident/v10_*); behind a
     // forwarded host doorbell 64
     // (the body posts its sums through LDS: the plan leaves the outputs, the scratch and the completion flag null)
-    const Refusal why = plan_resident(*c, sig, K, L, shifts, fs, cf.max_workgroups ? cf.max_workgroups : std::min(c->num_cus, bell_on_device ? 128 : 64),
-                                      &res->a, &res->cfg);
+    const Refusal why = corr_plan_resident(c->knobs, corr_tables(*c), sig, K, L, shifts, fs,
+                                           cf.max_workgroups ? cf.max_workgroups : std::min(c->num_cus, bell_on_device ? 128 : 64), &res->a, &res->cfg);
     if (why.code != GAT_OK) return bail(fail(c, why.code, why.msg));
     res->K = K;
     res->L = L;

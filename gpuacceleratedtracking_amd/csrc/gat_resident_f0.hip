@@ -8,14 +8,9 @@ extern template hipError_t launch_dc_resident_fmt<GAT_LAYOUT_INTERLEAVED>(const 
 extern template hipError_t launch_dc_resident_fmt<GAT_LAYOUT_INTERLEAVED_I16>(const DcArgs &, const DcLaunch &, const ResidentArgs &, hipStream_t, int *);
 extern template hipError_t launch_dc_resident_fmt<GAT_LAYOUT_INTERLEAVED_I8>(const DcArgs &, const DcLaunch &, const ResidentArgs &, hipStream_t, int *);
 
-bool dc_has_resident_instance(int ant_tile, int taps, int format)
-{
-    return format >= GAT_LAYOUT_PLANAR && format <= GAT_LAYOUT_INTERLEAVED_I8 && dc_resident_instance(ant_tile, taps);
-}
-
 static hipError_t resident_dispatch(const DcArgs &a, const DcLaunch &cfg, const ResidentArgs &r, hipStream_t s, int *blocks_per_cu)
 {
-    if (!dc_has_resident_instance(cfg.ant_tile, cfg.taps, cfg.format)) return hipErrorInvalidValue;
+    if (cfg.format < GAT_LAYOUT_PLANAR || cfg.format > GAT_LAYOUT_INTERLEAVED_I8 || !dc_resident_instance(cfg.ant_tile, cfg.taps)) return hipErrorInvalidValue;
     switch (cfg.format) {
     case GAT_LAYOUT_PLANAR: return launch_dc_resident_fmt<GAT_LAYOUT_PLANAR>(a, cfg, r, s, blocks_per_cu);
     case GAT_LAYOUT_INTERLEAVED: return launch_dc_resident_fmt<GAT_LAYOUT_INTERLEAVED>(a, cfg, r, s, blocks_per_cu);
