@@ -1,10 +1,12 @@
 // gat_acq_check.h -- the refusals that both acquisition entry points (through the call check of gat_acq_plan.h), the FFT search's
 // plan (gat_acq_fft_plan.h, which is also called bare) and gat_acq_stats_host make about a gat_acq_config, stated once.  No HIP
-// call and no HIP header.
+// call and no HIP header.  (The searches' bound on the code span is the kernels' own predicate, code_span_bad of gat_chan_rules.h,
+// which the plans call directly.)
 #pragma once
 
 #include <cmath>
 
+#include "gat_chan_rules.h"
 #include "gat_sig_plan.h"
 
 namespace gat {
@@ -30,13 +32,6 @@ inline Refusal acq_check_config(const gat_acq_config *cfg, int32_t P, int32_t D,
     const double fmax = std::fabs(cfg->if_hz) + std::fabs(cfg->doppler_first_hz) + std::fabs(cfg->doppler_step_hz) * (double)D;
     if (!(fmax / fs < 1.0e6)) return {GAT_ERR_RANGE, "carrier frequency out of range"};
     return {GAT_OK, nullptr};
-}
-
-// host mirror of the kernels' code_span_bad (gat_phase.h): what passes here is not poisoned there
-inline bool code_span_ok(double ratio, double tau, double reach, int Lc)
-{
-    const double span = std::fabs(tau) + std::fabs(ratio) * reach + 1.0;
-    return span < 1073741824.0 && (Lc <= 0 || span < 2097152.0 * (double)Lc) && ratio >= 0.0;
 }
 
 } // namespace gat

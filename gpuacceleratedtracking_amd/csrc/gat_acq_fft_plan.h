@@ -10,14 +10,7 @@
 #pragma once
 
 #include "gat_acq_plan.h" // AcqScratch; the configuration's refusals (gat_acq_check.h)
-
-#ifndef GAT_HD
-#if defined(__HIPCC__)
-#define GAT_HD __host__ __device__
-#else
-#define GAT_HD
-#endif
-#endif
+#include "gat_hd.h"
 
 namespace gat {
 
@@ -128,7 +121,7 @@ inline Refusal acq_fft_plan(const gat_signal_desc *sig, int32_t B, int32_t P, do
     }
     const double reach = (double)p.F + (double)(cfg->first_shift < 0 ? -cfg->first_shift : cfg->first_shift) + (double)p.G * (double)p.Jseg;
     if (!(reach < 1073741824.0)) return {GAT_ERR_RANGE, "N + |first_shift| + s * J must stay below 2^30 samples"};
-    if (!code_span_ok(cfg->code_freq_hz / fs, (double)cfg->code_length, reach, cfg->code_length)) return {GAT_ERR_RANGE, "code phase span too large"};
+    if (code_span_bad(cfg->code_freq_hz / fs, (double)cfg->code_length, reach, cfg->code_length)) return {GAT_ERR_RANGE, "code phase span too large"};
     p.passes = p.L <= kAcqFftOnePassLog2 ? 1 : 2;
     p.L1 = p.passes == 1 ? p.L : (p.L + 1) / 2;
     p.L2 = p.L - p.L1;

@@ -73,7 +73,7 @@ inline Refusal acq_plan(const gat_signal_desc *sig, int32_t B, int32_t P, double
     p.jtiles = (J + kAcqCodeTile - 1) / kAcqCodeTile, p.dtiles = (D + kAcqDopTile - 1) / kAcqDopTile;
     p.reach = (double)sig->num_samples + kAcqChunk + std::fabs((double)cfg->first_shift) + (double)s * p.jtiles * kAcqCodeTile;
     if (!(p.reach < 1073741824.0)) return {GAT_ERR_RANGE, "N + |first_shift| + s * J must stay below 2^30 samples"};
-    if (!code_span_ok(cfg->code_freq_hz / fs, (double)cfg->code_length, p.reach, cfg->code_length)) return {GAT_ERR_RANGE, "code phase span too large"};
+    if (code_span_bad(cfg->code_freq_hz / fs, (double)cfg->code_length, p.reach, cfg->code_length)) return {GAT_ERR_RANGE, "code phase span too large"};
 
     // groups of (antenna, block) units: enough workgroups for two per compute unit, within the scratch bound and the grid's z axis
     p.cells = (long long)P * D * J;

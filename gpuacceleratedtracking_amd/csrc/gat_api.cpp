@@ -462,9 +462,7 @@ GAT_API int32_t gat_device_info(gat_ctx *c, char *name_buf, size_t name_len, int
 GAT_API int32_t gat_set_codes(gat_ctx *c, const int8_t *codes_host, int32_t code_length, int32_t num_prns)
 {
     if (!c || !codes_host) return fail(c, GAT_ERR_ARG, "null argument");
-    if (code_length < 1 || num_prns < 1) return fail(c, GAT_ERR_ARG, "sizes must be positive");
-    // the vector kernel keeps a workgroup's chip table in LDS next to one replica segment (~40 KB): 160 KB - that
-    if (code_length > 120000) return fail(c, GAT_ERR_RANGE, "code table does not fit in LDS (max 120000 chips)");
+    if (const Refusal r = check_code_table(code_length, num_prns); r.code != GAT_OK) return fail(c, r.code, r.msg);
     GAT_HIP(c, hipSetDevice(c->device));
     park_residents(c); // their kernels hold the old tables (and hipFree waits for the whole device)
     for (gat_resident *r : c->residents) r->stale = true;
@@ -478,38 +476,22 @@ GAT_API int32_t gat_set_codes(gat_ctx *c, const int8_t *codes_host, int32_t code
         GAT_HIP(c, hipFree(c->d_code_bits));
         c->d_code_bits = nullptr;
     }
-    // 16-byte rows (dc_kernel stages them with 16-byte copies) with room for one more chip: every row carries its FIRST chip
-    // again at index code_length, so that "this chip and the next" are two reads without a wrap (the replica fill by quads)
-    const int stride = (code_length + 16) & ~15;
-    const size_t bytes = (size_t)stride * num_prns;
+    // the layout of both tables: gat_code_tables.h
     {
-        std::vector<int8_t> rows(bytes, 0);
-        for (int p = 0; p < num_prns; ++p) {
-            std::memcpy(&rows[(size_t)p * stride], codes_host + (size_t)p * code_length, (size_t)code_length);
-            rows[(size_t)p * stride + code_length] = codes_host[(size_t)p * code_length];
-        }
-        GAT_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_codes), bytes));
-        GAT_HIP(c, hipMemcpy(c->d_codes, rows.data(), bytes, hipMemcpyHostToDevice));
+        std::vector<int8_t> rows((size_t)code_row_stride(code_length) * num_prns);
+        pack_code_rows(codes_host, code_length, num_prns, rows.data());
+        GAT_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_codes), rows.size()));
+        GAT_HIP(c, hipMemcpy(c->d_codes, rows.data(), rows.size(), hipMemcpyHostToDevice));
     }
-    c->code_row_stride = stride;
+    c->code_row_stride = code_row_stride(code_length);
     c->Lc = code_length;
     c->P = num_prns;
-    // sign-bit tables for the split-bf16 matrix kernel (a chip only flips signs there): 1/8 of the LDS
-    bool pm1 = true;
-    for (size_t i = 0; i < (size_t)code_length * num_prns && pm1; ++i) pm1 = codes_host[i] == 1 || codes_host[i] == -1;
-    if (pm1) {
-        // (rows: chip code_length repeats chip 0 -- see above --, and one whole dword of slack behind the last chip, so that the
-        // two dwords holding "this chip and the next" can always be read together)
-        const int bstride = (((code_length + 1 + 32 + 31) / 32) + 3) & ~3;
-        std::vector<uint32_t> bits((size_t)bstride * num_prns, 0u);
-        for (int p = 0; p < num_prns; ++p)
-            for (int i = 0; i < code_length; ++i)
-                if (codes_host[(size_t)p * code_length + i] < 0) bits[(size_t)p * bstride + (i >> 5)] |= 1u << (i & 31);
-        for (int p = 0; p < num_prns; ++p)
-            if (codes_host[(size_t)p * code_length] < 0) bits[(size_t)p * bstride + (code_length >> 5)] |= 1u << (code_length & 31);
+    if (codes_all_pm1(codes_host, code_length, num_prns)) {
+        std::vector<uint32_t> bits((size_t)code_bits_stride(code_length) * num_prns);
+        pack_code_bits(codes_host, code_length, num_prns, bits.data());
         GAT_HIP(c, hipMalloc(reinterpret_cast<void **>(&c->d_code_bits), bits.size() * sizeof(uint32_t)));
         GAT_HIP(c, hipMemcpy(c->d_code_bits, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        c->code_bits_stride = bstride;
+        c->code_bits_stride = code_bits_stride(code_length);
     }
     return GAT_OK;
 }
@@ -555,10 +537,8 @@ GAT_API int32_t gat_downconvert_and_correlate(gat_ctx *c, const gat_signal_desc 
     const size_t n = (size_t)B * K;
     if (!c->d_codes) return fail(c, GAT_ERR_STATE, "gat_set_codes has not been called");
     if (!(fs > 0.0) || !std::isfinite(fs)) return fail(c, GAT_ERR_ARG, "sampling frequency must be positive");
-    {
-        const int32_t rcv = validate_params(c, params_host, n, (double)(sig->num_samples + max_shift), fs);
-        if (rcv != GAT_OK) return rcv;
-    }
+    if (const Refusal r = check_channel_records(params_host, n, c->P, c->Lc, (double)(sig->num_samples + max_shift), fs); r.code != GAT_OK)
+        return fail(c, r.code, r.msg);
     if (n <= (size_t)kInlineParams) // no upload: the records ride in the kernel arguments
         return correlate_impl(c, sig, nullptr, B, K, L, shifts, fs, out_re, out_im, flags, params_host);
     const int32_t rc = upload_params(c, params_host, n);
@@ -566,26 +546,22 @@ GAT_API int32_t gat_downconvert_and_correlate(gat_ctx *c, const gat_signal_desc 
     return correlate_impl(c, sig, c->d_params, B, K, L, shifts, fs, out_re, out_im, flags);
 }
 
-// what the one-channel replica generators check alike; each adds its own checks behind these
+// what the one-channel replica generators check alike (the values: check_replica_call, gat_chan_rules.h); the texture-address
+// variant adds its own checks behind these
 static int32_t check_gen_code_replica(gat_ctx *c, const float *rep, int64_t count, int32_t prn, double fc, double fs, double tau,
-                                      int64_t first_shift)
+                                      int64_t first_shift, bool exact_span)
 {
     if (!c || !rep) return fail(c, GAT_ERR_ARG, "null argument");
     if (!c->d_codes) return fail(c, GAT_ERR_STATE, "gat_set_codes has not been called");
-    if (count < 1) return fail(c, GAT_ERR_ARG, "count must be positive");
-    if (prn < 0 || prn >= c->P) return fail(c, GAT_ERR_RANGE, "prn outside the code table");
-    if (!(fs > 0.0) || !std::isfinite(fc) || !std::isfinite(tau)) return fail(c, GAT_ERR_ARG, "bad frequency / phase");
-    if (count + std::llabs((long long)first_shift) >= (1ll << 30)) return fail(c, GAT_ERR_RANGE, "replica too long");
-    return GAT_OK;
+    const Refusal r = check_replica_call(count, prn, c->P, c->Lc, fc, fs, tau, first_shift, exact_span);
+    return r.code == GAT_OK ? GAT_OK : fail(c, r.code, r.msg);
 }
 
 static int32_t gen_code_replica_impl(gat_ctx *c, float *rep, int64_t count, int32_t prn, double fc, double fs,
                                      double tau, int64_t first_shift, bool f32_coordinates)
 {
-    const int32_t rc = check_gen_code_replica(c, rep, count, prn, fc, fs, tau, first_shift);
+    const int32_t rc = check_gen_code_replica(c, rep, count, prn, fc, fs, tau, first_shift, !f32_coordinates);
     if (rc != GAT_OK) return rc;
-    if (!f32_coordinates && !code_span_ok(fc / fs, tau, (double)count + (double)std::llabs((long long)first_shift), c->Lc))
-        return fail(c, GAT_ERR_RANGE, "code phase span too large");
     GAT_ENTER(c, "gat_gen_code_replica");
     GAT_HIP(c, launch_gen_code_replica(rep, count, c->d_codes + (size_t)prn * c->code_row_stride, c->Lc, fc, fs, tau,
                                        first_shift, f32_coordinates, c->stream));
@@ -607,7 +583,7 @@ GAT_API int32_t gat_gen_code_replica_f32coord(gat_ctx *c, float *rep, int64_t co
 GAT_API int32_t gat_gen_code_replica_texaddr(gat_ctx *c, float *rep, int64_t count, int32_t prn, double fc, double fs, double tau,
                                              int64_t first_shift, int32_t coord_frac_bits, int32_t texel_frac_bits)
 {
-    const int32_t rc = check_gen_code_replica(c, rep, count, prn, fc, fs, tau, first_shift);
+    const int32_t rc = check_gen_code_replica(c, rep, count, prn, fc, fs, tau, first_shift, false);
     if (rc != GAT_OK) return rc;
     if (coord_frac_bits < 0 || coord_frac_bits > 32 || texel_frac_bits < -1 || texel_frac_bits > 24)
         return fail(c, GAT_ERR_RANGE, "coord_frac_bits 0 .. 32, texel_frac_bits -1 .. 24");
@@ -639,15 +615,9 @@ GAT_API int32_t gat_downconvert_and_accumulate(gat_ctx *c, const gat_signal_desc
     if (sig->layout != GAT_LAYOUT_PLANAR || !sig->re || !sig->im) return fail(c, GAT_ERR_UNSUPPORTED, "planar float signal only");
     if (L < 1 || L > GAT_MAX_TAPS || sig->num_ants < 1 || sig->num_samples < 1 || sig->num_samples >= (1ll << 30))
         return fail(c, GAT_ERR_RANGE, "size out of range");
-    if (p->prn < 0 || p->prn >= c->P) return fail(c, GAT_ERR_RANGE, "prn outside the code table");
-    if (!(fs > 0.0) || !std::isfinite(p->code_freq_hz) || !(p->code_freq_hz >= 0.0) || !std::isfinite(p->carrier_freq_hz) ||
-        !std::isfinite(p->code_phase_chips) || !std::isfinite(p->carrier_phase_cycles))
-        return fail(c, GAT_ERR_ARG, "bad frequency / phase");
     long long max_shift = 0;
     for (int l = 0; l < L; ++l) max_shift = std::max<long long>(max_shift, std::llabs((long long)shifts[l]));
-    if (sig->num_samples + max_shift >= (1ll << 30)) return fail(c, GAT_ERR_RANGE, "num_samples + |shift| must stay below 2^30");
-    if (!code_span_ok(p->code_freq_hz / fs, p->code_phase_chips, (double)(sig->num_samples + max_shift), c->Lc))
-        return fail(c, GAT_ERR_RANGE, "code phase span too large");
+    if (const Refusal r = check_accumulate_record(*p, c->P, c->Lc, sig->num_samples, max_shift, fs); r.code != GAT_OK) return fail(c, r.code, r.msg);
     GAT_ENTER(c, "gat_downconvert_and_accumulate");
     // the tap list goes through the library's parameter scratch (device memory the kernel can read), in whole records
     const size_t need = ((size_t)L * sizeof(int32_t) + sizeof(gat_channel_params) - 1) / sizeof(gat_channel_params);

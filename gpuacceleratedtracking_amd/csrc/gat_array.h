@@ -13,12 +13,7 @@
 #include <stddef.h>
 
 #include "gat.h"
-
-#if defined(__HIPCC__)
-#define GAT_HD __host__ __device__
-#else
-#define GAT_HD
-#endif
+#include "gat_hd.h"
 
 namespace gat {
 

@@ -26,6 +26,7 @@
 #include <cstring>
 
 #include "gat.h"
+#include "gat_chan_rules.h" // mfma_wrap_bad: the matrix kernels' wrap rule, as they evaluate it
 #include "gat_sig_plan.h" // the layout arithmetic (layout_sample_bytes, layout_vec_samples), blocks_aligned, Refusal
 
 namespace gat {
@@ -537,12 +538,12 @@ inline Refusal plan_matrix(const CorrKnobs &c, const CorrTables &t, const CorrCa
     const int *sorted = taps.sorted;
     const int CT = L <= kMfmaMaxTaps ? 16 / L : 0;
     // Both matrix-core kernels fill a lane's replica entries from one floored modulo and at most one wrap of the table
-    // per 32 samples, and poison (NaN) a channel whose code rate breaks that: ratio * 32 >= Lc.  Tables of fewer than 64
+    // per 32 samples, and poison (NaN) a channel whose code rate breaks that (mfma_wrap_bad).  Tables of fewer than 64
     // chips (where a rate below two chips per sample can break it), and host-side records that break it, take the vector
     // kernel instead (a one-chip table under GAT_MC_F32 returned NaN for a valid call).
     bool wraps_ok = t.Lc >= 64;
     if (call.params_inline)
-        for (long long i = 0; i < (long long)B * K && wraps_ok; ++i) wraps_ok = call.params_inline[i].code_freq_hz / call.fs * 32.0 < (double)t.Lc;
+        for (long long i = 0; i < (long long)B * K && wraps_ok; ++i) wraps_ok = !mfma_wrap_bad(call.params_inline[i].code_freq_hz / call.fs, t.Lc);
     const bool shape_any = c.mc_mode != 0 && vec == 4 && N % spv == 0 /* whole load groups */ && M % 16 == 0 && sig->chan_stride == 0 && CT >= 1 &&
                            span <= kMfmaMaxSpan && 2 * std::min(K, CT) * L >= 12 /* >= 3/8 of the columns */ && wraps_ok;
     const bool shape_ok = shape_any && fmt == GAT_LAYOUT_PLANAR; // the f32-MFMA kernel reads planar f32 only

@@ -8,7 +8,8 @@
 // in by the pure plans cov_plan (gat_array_plan.h), stats_plan (gat_cond_plan.h) and st_cov_plan (gat_st_plan.h) and walked by
 // enqueue_estimates below.  What the two acquisition searches (gat_acq_api.cpp, gat_acq_fft_api.cpp) share is a header of its own,
 // gat_acq_frame.h: the checks before planning, the common kernel arguments and the frame around each search's launches, over the
-// pure plans of gat_acq_plan.h and gat_acq_fft_plan.h.
+// pure plans of gat_acq_plan.h and gat_acq_fft_plan.h.  Which host-resident channel record an entry point accepts is gat_chan_rules.h
+// (pure: the negation of the predicates the kernels poison with); how gat_set_codes lays a table out is gat_code_tables.h.
 #pragma once
 
 #include <cmath>
@@ -16,7 +17,8 @@
 #include <string>
 #include <vector>
 
-#include "gat_acq_check.h" // code_span_ok: the host mirror of the kernels' code_span_bad
+#include "gat_chan_rules.h"  // the host's checks of channel records: the negation of the kernels' predicates
+#include "gat_code_tables.h" // the layout behind d_codes and d_code_bits
 #include "gat_est_plan.h"  // the launches that enqueue_estimates walks
 #include "gat_internal.h"
 
@@ -200,8 +202,6 @@ inline CorrTables corr_tables(const gat_ctx &c)
 {
     return {c.d_codes, c.d_code_bits, c.d_zeros, c.Lc, c.P, c.code_row_stride, c.code_bits_stride, c.num_cus};
 }
-// host mirror of the kernels' `bad` predicate for host-resident records: what passes here is not poisoned there
-int32_t validate_params(gat_ctx *c, const gat_channel_params *params_host, size_t n, double reach, double fs);
 // the context's resident correlators (gat_resident_api.cpp): asked to leave before anything that waits for the whole device
 // (hipFree, a new code table, the context's end); freed with the context
 void park_residents(gat_ctx *c);

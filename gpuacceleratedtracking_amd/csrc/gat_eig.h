@@ -10,14 +10,7 @@
 #include <stdint.h>
 
 #include "gat.h"
-
-#ifndef GAT_HD
-#if defined(__HIPCC__)
-#define GAT_HD __host__ __device__
-#else
-#define GAT_HD
-#endif
-#endif
+#include "gat_hd.h"
 
 namespace gat {
 

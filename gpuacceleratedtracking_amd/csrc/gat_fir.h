@@ -13,14 +13,7 @@
 
 #include "gat.h"
 #include "gat_sig_plan.h" // host_load_sample
-
-#ifndef GAT_HD
-#if defined(__HIPCC__)
-#define GAT_HD __host__ __device__
-#else
-#define GAT_HD
-#endif
-#endif
+#include "gat_hd.h"
 
 namespace gat {
 

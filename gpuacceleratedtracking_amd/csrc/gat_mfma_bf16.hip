@@ -452,9 +452,11 @@ __global__ void __launch_bounds__(mb_threads(RT, NCT)) mfma_bf16_kernel(const Mf
             ci.step = P.carrier_freq_hz / a.fs;
             ci.tau = P.code_phase_chips;
             ci.phi = P.carrier_phase_cycles;
+            // code_span_bad || mfma_wrap_bad (gat_chan_rules.h) written out term by term, over that header's constants: with the
+            // two calls in its place this kernel compiles to other code
             const double sp = __builtin_fabs(ci.tau) + __builtin_fabs(ci.ratio) * (double)(N + a.max_abs_shift) + 1.0;
-            ci.bad = P.prn < 0 || P.prn >= a.num_prns || !(sp < 1073741824.0) || !(sp < 2097152.0 * (double)Lc) ||
-                     !(ci.ratio >= 0.0) || !(ci.ratio * 32.0 < (double)Lc) || carrier_bad(ci.step, ci.phi);
+            ci.bad = P.prn < 0 || P.prn >= a.num_prns || !(sp < kCodeSpanMax) || !(sp < kCodeSpanLaps * (double)Lc) ||
+                     !(ci.ratio >= 0.0) || !(ci.ratio * kMfmaWrapSamples < (double)Lc) || carrier_bad(ci.step, ci.phi);
             ci.prn = (P.prn < 0 || P.prn >= a.num_prns) ? 0 : P.prn;
             if (ci.bad) { ci.ratio = 0.0; ci.tau = 0.0; ci.step = 0.0; ci.phi = 0.0; }
             carrier_reduce(ci.step, ci.phi);

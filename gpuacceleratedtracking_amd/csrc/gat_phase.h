@@ -1,13 +1,16 @@
 // gat_phase.h -- the phase arithmetic every kernel of libgat shares (device code only).
 //
 // Bit-exact parity between the three correlator kernels (gat_kernels.hip, gat_mfma.hip, gat_mfma_bf16.hip), the
-// stand-alone replica / signal generators and the CPU oracle rests on these few functions, so they exist ONCE.
+// stand-alone replica / signal generators and the CPU oracle rests on these few functions, so they exist ONCE.  The records they
+// cannot evaluate exactly (code_span_bad, carrier_bad) are stated for host and device in gat_chan_rules.h, included here.
 // Files that include this header must be built with -ffp-contract=off (the double-precision code phase of the
 // reference, src/algorithms.jl:179-182, is a multiply followed by an add, not an fma).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "gat_chan_rules.h" // code_span_bad, carrier_bad, mfma_wrap_bad: the records the kernels poison, shared with the host's checks
 
 namespace gat {
 
@@ -37,7 +40,7 @@ __device__ __forceinline__ void sincos_cycles(double theta, float &c, float &s)
 }
 
 // floor(p) mod Lc with floored (Julia) semantics; valid for |ip| < 2^30 and |ip| / Lc < 2^21
-// (checked on the host and again per workgroup by the correlator kernels; other callers clamp).
+// (code_span_bad, gat_chan_rules.h: checked on the host and again per workgroup by the correlator kernels; other callers clamp).
 __device__ __forceinline__ int floormod_fast(int ip, int Lc, float inv_lc)
 {
     const float q = __builtin_floorf((float)ip * inv_lc);
@@ -45,23 +48,6 @@ __device__ __forceinline__ int floormod_fast(int ip, int Lc, float inv_lc)
     r += (r < 0) ? Lc : 0;
     r -= (r >= Lc) ? Lc : 0;
     return r;
-}
-
-// Parameters floormod_fast / chip_index cannot evaluate exactly: `reach` = the largest |sample + shift| of the call.  The
-// correlator kernels, the stand-alone replica and the materialising debug kernel all use this ONE predicate (they write
-// NaN instead of indexing outside the chip table); the host entry points with host-resident parameters reject the same set.
-__device__ __forceinline__ bool code_span_bad(double ratio, double tau, double reach, int Lc)
-{
-    const double span = __builtin_fabs(tau) + __builtin_fabs(ratio) * reach + 1.0;
-    return !(span < 1073741824.0) || !(span < 2097152.0 * (double)Lc) || !(ratio >= 0.0);
-}
-
-// The carrier part of the same predicate: a carrier step f / fs or a carrier phase of 10^15 cycles or more, NaN or inf.
-// Every correlator kernel poisons such a device-resident record with it; the host entry points reject the same records
-// (validate_params).  (Below the bound carrier_reduce makes every record exact.)
-__device__ __forceinline__ bool carrier_bad(double step, double phi)
-{
-    return !(__builtin_fabs(step) < 1.0e15) || !(__builtin_fabs(phi) < 1.0e15);
 }
 
 // Exact reduction of a channel's carrier, once where its record is read: the phase to [0, 1] (phi - floor(phi)), the

@@ -27,24 +27,6 @@ static double mono_us()
     return t.tv_sec * 1e6 + t.tv_nsec * 1e-3;
 }
 
-// host mirror of the kernels' `bad` predicate for host-resident records: what passes here is not poisoned there
-int32_t validate_params(gat_ctx *c, const gat_channel_params *params_host, size_t n, double reach, double fs)
-{
-    for (size_t i = 0; i < n; ++i) {
-        const gat_channel_params &p = params_host[i];
-        if (p.prn < 0 || p.prn >= c->P) return fail(c, GAT_ERR_RANGE, "prn outside the code table");
-        if (!std::isfinite(p.code_freq_hz) || !std::isfinite(p.carrier_freq_hz) ||
-            !std::isfinite(p.code_phase_chips) || !std::isfinite(p.carrier_phase_cycles))
-            return fail(c, GAT_ERR_ARG, "non-finite channel parameter");
-        if (p.code_freq_hz < 0.0) return fail(c, GAT_ERR_RANGE, "negative code frequency");
-        if (std::fabs(p.carrier_freq_hz / fs) >= 1.0e15 || std::fabs(p.carrier_phase_cycles) >= 1.0e15)
-            return fail(c, GAT_ERR_RANGE, "carrier frequency / phase out of range");
-        if (!code_span_ok(p.code_freq_hz / fs, p.code_phase_chips, reach, c->Lc))
-            return fail(c, GAT_ERR_RANGE, "code phase span too large");
-    }
-    return GAT_OK;
-}
-
 // the doorbell may live behind the PCIe BAR (write-combining): stores are pushed out of the core's buffers before anybody waits
 static inline void bell_flush(const gat_resident *res)
 {
@@ -247,8 +229,9 @@ GAT_API int32_t gat_resident_correlate(gat_resident *res, const gat_channel_para
     if (res->stale) return fail(c, GAT_ERR_STATE, "the code table changed: open the resident correlator again");
     if (block_offset < 0 || block_offset % res->spv != 0 || block_offset >= (1ll << 40))
         return fail(c, GAT_ERR_ARG, "block offset must be a non-negative multiple of the samples one 16-byte load holds");
-    int32_t rc = validate_params(c, params_host, (size_t)res->K, (double)(res->N + res->a.max_abs_shift), res->fs);
-    if (rc != GAT_OK) return rc;
+    if (const Refusal r = check_channel_records(params_host, (size_t)res->K, c->P, c->Lc, (double)(res->N + res->a.max_abs_shift), res->fs); r.code != GAT_OK)
+        return fail(c, r.code, r.msg);
+    int32_t rc = GAT_OK;
 
     // ring: one line per channel, line 0 last; inside a line the two sequence words last
     unsigned prev = res->seq, seq = prev + 1;

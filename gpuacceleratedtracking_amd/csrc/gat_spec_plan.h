@@ -5,14 +5,7 @@
 #pragma once
 
 #include "gat_sig_plan.h"
-
-#ifndef GAT_HD
-#if defined(__HIPCC__)
-#define GAT_HD __host__ __device__
-#else
-#define GAT_HD
-#endif
-#endif
+#include "gat_hd.h"
 
 namespace gat {
 

@@ -4,7 +4,8 @@
 // records, both flag values, every knob drawn from its option range, devices of 8 .. 304 CUs -- must plan launches that keep what the
 // kernels assume (tests/corr_launch_contract.h, shared with the host simulator's stand-in launchers) and that own every tap of the
 // call exactly once, with the caller's index; every refusal that a call can reach must come with its code and message; every branch
-// of the plan listed in `Branch` must be reached; and the geometry of the benchmark's shapes at 256 CUs is pinned as literal
+// of the plan listed in `Branch` must be reached; inline host records that break the matrix kernels' wrap rule (mfma_wrap_bad) must keep a
+// call away from them, and only those; and the geometry of the benchmark's shapes at 256 CUs is pinned as literal
 // numbers, taken from the planner this header replaced.  Built with -fsanitize=address,undefined by
 // tests/test_correlator_plan_host.py.  No memory behind the descriptors is ever touched: the plan reads addresses, not data.
 #include <cstdarg>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "../corr_launch_contract.h"
+#include "gat_code_tables.h"
 
 using namespace gat;
 
@@ -51,12 +53,11 @@ template <class T> T pick(std::initializer_list<T> l) { return *(l.begin() + uni
 template <class T> T *addr(uintptr_t a) { return reinterpret_cast<T *>(a); }
 constexpr uintptr_t kRe = 0x100000000000ull, kIm = 0x300000000000ull;
 
-// A bound code table as gat_set_codes leaves it: rows padded to 16 bytes with room for one more chip, sign-bit rows (where every
-// chip is +-1) padded to four dwords
+// A bound code table as gat_set_codes leaves it (gat_code_tables.h): chip rows, and sign-bit rows where every chip is +-1
 CorrTables tables(int Lc, bool bits, int cus)
 {
     return {addr<const int8_t>(0x500000000000ull), bits ? addr<const uint32_t>(0x600000000000ull) : nullptr, addr<const void>(0x700000000000ull), Lc, 32,
-            (Lc + 16) & ~15, bits ? (((Lc + 1 + 32 + 31) / 32) + 3) & ~3 : 0, cus};
+            code_row_stride(Lc), bits ? code_bits_stride(Lc) : 0, cus};
 }
 
 // One call with everything it points to
@@ -117,6 +118,8 @@ Case random_case()
     c.tab = tables(Lc, uni(0, 1) != 0, (int)pick<long long>({8, 64, 104, 256, 304}));
     c.host = uni(0, 1) != 0;
     c.recs.assign((size_t)std::min<long long>((long long)c.B * c.K, kInlineParams), gat_channel_params{(int32_t)uni(0, 31), 0, tbl == 1 ? 10.23e6 : 1.023e6, 1000.0, 0.5, 0.25});
+    // (now and then one host record beyond the matrix kernels' wrap rule, at its edge or past it: check_plan)
+    if (c.host && uni(0, 7) == 0) c.recs[(size_t)uni(0, (long long)c.recs.size() - 1)].code_freq_hz = c.fs * Lc / 32.0 * pick<double>({1.0, 1.5});
     c.flags = uni(0, 5) == 0 ? GAT_FLAG_ATOMIC : 0u;
     // every knob: its default, or any value of its range (kOptions of gat_api.cpp; gat_set_matrix_core)
     CorrKnobs &k = c.knobs;
@@ -154,6 +157,7 @@ const char *const kBranchName[kBranches] = {"kind 0", "kind 1", "kind 2", "nw ==
                                             "several tap groups", "the shifted replica copy", "align_head", "sign-bit tables in the vector kernel",
                                             "the two-term int16 mode", "a split with finalize", "bpw > 1"};
 long reached[kBranches];
+long matrix_records_checked = 0; // inline host records of calls that a matrix kernel took
 
 void count_branches(const CorrPlan &p)
 {
@@ -199,6 +203,13 @@ void check_plan(const Case &c, CorrPlan &p, const char *what)
         else check_mfma(p.m, p.nct, p.grid, p.lds, broken);
         for (int l = 0; l < p.m.L && l < kMfmaMaxTaps; ++l) own(p.m.tap_index[l], p.m.shifts[l]);
         CHECK(p.splits == p.m.splits && p.info.matrix_core == p.kind && p.info.workgroups == (int32_t)p.grid, "%s: matrix plan and launch info", what);
+        // host records that a matrix kernel would poison for its own wrap rule never reach one
+        if (const CorrCall call = c.call(); call.params_inline)
+            for (long long i = 0; i < (long long)c.B * c.K; ++i) {
+                const double ratio = call.params_inline[i].code_freq_hz / c.fs;
+                CHECK(!mfma_wrap_bad(ratio, c.tab.Lc), "%s: record %lld (ratio %g, %d chips) given to matrix kernel %d", what, i, ratio, c.tab.Lc, p.kind);
+                matrix_records_checked += 1;
+            }
     } else {
         CHECK(p.groups >= 1 && p.groups <= c.L, "%s: %d tap groups", what, p.groups);
         for (int g = 0; g < p.groups; ++g) {
@@ -315,6 +326,25 @@ void sweep(int calls)
     }
 }
 
+// ---- the matrix kernels' wrap rule: a call with inline host records goes to a matrix kernel only if none breaks mfma_wrap_bad --------
+void wrap_rule()
+{
+    for (int mode : {(int)GAT_MC_F32, (int)GAT_MC_BF16_SPLIT})
+        for (int K : {1, 2, 4})
+            for (int L : {6, 8, 16}) {
+                Case c = bench_case(GAT_LAYOUT_PLANAR, 1023, 1.023e6, 20000, 16, L, K, 1, mode, true);
+                const double edge = c.fs * 1023.0 / 32.0; // code frequency at which 32 samples span the table
+                for (double f : {1.023e6, std::nextafter(edge, 0.0), edge, std::nextafter(edge, INFINITY), 1.5 * edge}) {
+                    c.recs[(size_t)K - 1].code_freq_hz = f;
+                    CorrPlan p;
+                    const Refusal r = plan_case(c, p);
+                    const bool bad = mfma_wrap_bad(f / c.fs, 1023);
+                    CHECK(r.code == GAT_OK && (p.kind != 0) == !bad, "wrap rule: mode %d, %d channels, %d taps, code frequency %.17g: status %d, kind %d", mode, K, L, f, r.code, p.kind);
+                    if (r.code == GAT_OK) check_plan(c, p, "wrap rule");
+                }
+            }
+}
+
 // ---- pinned rows: the benchmark's shapes at 256 CUs ------------------------------------------------------------------------------
 struct Row {
     int kind, MT, aw, kt, nw, depth, vec, splits, bpw, seg_steps, lds;
@@ -379,10 +409,13 @@ int main()
     refusals();
     pinned();
     sweep(6000);
+    wrap_rule();
     for (int b = 0; b < kBranches; ++b) {
         std::printf("  %-40s %ld\n", kBranchName[b], reached[b]);
         CHECK(reached[b] > 0, "no call of the sweep reached: %s", kBranchName[b]);
     }
+    std::printf("  %-40s %ld\n", "host records given to a matrix kernel", matrix_records_checked);
+    CHECK(matrix_records_checked > 0, "no call gave inline host records to a matrix kernel");
     std::printf("pinned %d plans\n", kPinned);
     std::printf("planned %ld calls (%ld refused, %ld resident plans), %ld refusals provoked, %d failures\n", planned, refused_calls, resident_planned, refusals_seen, failures);
     return failures ? 1 : 0;

@@ -131,7 +131,7 @@ hipError_t launch_acq_grid(const AcqArgs &a, int fmt, hipStream_t)
     const long long x_lo = a.first_shift, x_hi = last_n0 + a.first_shift + (long long)a.s * (jt - 1) * kAcqCodeTile + rep_len - 1;
     const double reach = (double)std::max(std::llabs(x_lo), std::llabs(x_hi));
     REQUIRE(x_lo > INT32_MIN && x_hi < INT32_MAX, "acq: window index %lld .. %lld", x_lo, x_hi);
-    REQUIRE(code_span_ok(a.ratio, (double)a.Lc, reach, a.Lc), "acq: code span for ratio %g over %g samples", a.ratio, reach);
+    REQUIRE(!code_span_bad(a.ratio, (double)a.Lc, reach, a.Lc), "acq: code span for ratio %g over %g samples", a.ratio, reach);
     REQUIRE(a.ratio > 0.0 && std::isfinite(a.fs) && a.fs > 0.0, "acq: ratio %g fs %g", a.ratio, a.fs);
     // the PRNs' code rows, the signal's first and last sample of every (antenna, block) unit, the output slices
     volatile long sink = 0;

@@ -66,14 +66,14 @@ static std::vector<int8_t> chip_table(int Lc, int P, int kind)
         for (int i = 0; i < std::max(1, Lc / 50); ++i) t[(size_t)uni(0, (long long)t.size() - 1)] = 0;
     return t;
 }
-static bool all_pm1(const std::vector<int8_t> &t) { return std::all_of(t.begin(), t.end(), [](int8_t v) { return v == 1 || v == -1; }); }
-// the one refusal a correlate call with valid records may meet: the code-span bound (gat_ctx.h), evaluated here
+static bool all_pm1(const std::vector<int8_t> &t) { return gat::codes_all_pm1(t.data(), (int)t.size(), 1); }
+// the one refusal a correlate call with valid records may meet: the code-span bound (gat_chan_rules.h), evaluated here
 static bool span_refused(const std::vector<gat_channel_params> &prm, double fs, long long N, const std::vector<int32_t> &sh, int Lc)
 {
     long long ms = 0;
     for (int32_t s : sh) ms = std::max<long long>(ms, std::llabs((long long)s));
     for (const auto &p : prm)
-        if (!gat::code_span_ok(p.code_freq_hz / fs, p.code_phase_chips, (double)(N + ms), Lc)) return true;
+        if (gat::code_span_bad(p.code_freq_hz / fs, p.code_phase_chips, (double)(N + ms), Lc)) return true;
     return false;
 }
 
