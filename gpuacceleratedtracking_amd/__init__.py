@@ -27,6 +27,8 @@ from .filtering import (channelize, filter_samples, filter_samples_host, filter_
 from .gen_signal import StructSignal, gen_blank_signal, gen_signal, gen_signal_stream, make_params  # noqa: F401
 from .loop import ResidentTrackingLoop, TrackingLoop  # noqa: F401
 from .monitor import (TrackMonitor, monitor_accumulators, monitor_accumulators_host, monitor_plan, overlay_for)  # noqa: F401
+from .navigation import (NavResult, cnav_fec_encode, cnav_message, crc24q, decode_navigation, decode_navigation_host,  # noqa: F401
+                         lnav_subframe, nav_format_for, nav_plan)
 from .sharding import DeviceGroup, ShardPlan, gather_outputs, shard_channels, shard_params  # noqa: F401
 from .spectrum import (auto_notch, find_tones, sample_spectrum, sample_spectrum_host, spectrum_stream)  # noqa: F401
 from .spacetime import (spacetime_covariance, spacetime_delay, spacetime_filter, spacetime_filter_host, spacetime_steering,  # noqa: F401

@@ -38,6 +38,8 @@ GAT_MAX_ST_TAPS = 16
 GAT_MAX_SYMBOL_BLOCKS, GAT_MAX_MONITOR_BLOCKS, GAT_MAX_MONITOR_CHANNELS = 128, 1 << 20, 4096
 # subspace (gat_accumulator_covariance's chunk, gat_hermitian_eig's sweep limit and input flag)
 GAT_ACC_COV_CHUNK, GAT_EIG_MAX_SWEEPS, GAT_EIG_INPUT_F32 = 256, 60, 1
+# navigation data (gat_nav_decode formats, the frame length and CNAV's unsearched traceback tail)
+GAT_NAV_LNAV, GAT_NAV_CNAV, GAT_NAV_FRAME_BITS, GAT_NAV_TAIL_BITS = 0, 1, 300, 32
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -74,6 +76,8 @@ EXPORTS = [
     # subspace: the accumulators' covariance, the batched Hermitian eigensolver and their plan
     "gat_accumulator_covariance", "gat_accumulator_covariance_host", "gat_hermitian_eig", "gat_hermitian_eig_host",
     "gat_subspace_plan",
+    # navigation data: frame synchronisation, LNAV parity, CNAV Viterbi decoding and CRC-24Q
+    "gat_nav_decode", "gat_nav_decode_host", "gat_nav_decode_plan",
 ]
 
 
@@ -236,6 +240,29 @@ assert C.sizeof(MonitorConfig) == 160 and C.sizeof(MonitorPlan) == 48
 assert MONITOR_WINDOW_DTYPE.itemsize == 48 and MONITOR_CHANNEL_DTYPE.itemsize == 32
 
 
+class NavConfig(C.Structure):
+    """gat_nav_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_int32), ("symbol_capacity", C.c_int32), ("max_frames", C.c_int32),
+                ("min_frames", C.c_int32)]
+
+
+class NavPlan(C.Structure):
+    """gat_nav_plan (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("num_phases", C.c_int32), ("bit_capacity", C.c_int32), ("num_candidates", C.c_int32),
+                ("slice_workgroups", C.c_int32), ("quantise_workgroups", C.c_int32), ("trellis_workgroups", C.c_int32),
+                ("score_workgroups", C.c_int32), ("pick_workgroups", C.c_int32), ("frame_workgroups", C.c_int32),
+                ("scratch_bytes", C.c_int64)]
+
+
+# gat_nav_channel and gat_nav_frame (include/gat.h)
+NAV_CHANNEL_DTYPE = np.dtype([(n, "<i4") for n in ("frame_offset", "symbol_phase", "inverted", "score", "second_score", "num_frames",
+                                                    "num_bits", "tow_steps")])
+NAV_FRAME_DTYPE = np.dtype([("status", "<i4"), ("tow", "<i4"), ("id", "<i4"), ("prn", "<i4"), ("words", "<u4", (10,))])
+assert C.sizeof(NavConfig) == 20 and C.sizeof(NavPlan) == 48 and NAV_CHANNEL_DTYPE.itemsize == 32 and NAV_FRAME_DTYPE.itemsize == 56
+
+
 _LIB = None
 
 
@@ -352,6 +379,9 @@ def load(build_if_missing: bool = True):
         "gat_hermitian_eig": (i32, [vp, vp, vp, i32, i32, i32, u32, vp, vp, vp, vp]),
         "gat_hermitian_eig_host": (i32, [vp, vp, i32, i32, i32, u32, vp, vp, vp, vp]),
         "gat_subspace_plan": (i32, [i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(SubspacePlan)]),
+        "gat_nav_decode": (i32, [vp, vp, vp, i32, C.POINTER(NavConfig), vp, vp, vp, vp]),
+        "gat_nav_decode_host": (i32, [vp, vp, i32, C.POINTER(NavConfig), vp, vp, vp, vp]),
+        "gat_nav_decode_plan": (i32, [i32, C.POINTER(NavConfig), C.POINTER(NavPlan)]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

@@ -152,6 +152,15 @@ class TrackingLoop:
             kw.setdefault("weights", (self._w_re, self._w_im))
         return monitor_accumulators(acc_re, acc_im, **kw)
 
+    def navigation(self, mon, **kw):
+        """``navigation.decode_navigation`` over a monitor of this loop (``monitor``) with the loop's system's message format
+        filled in: frame synchronisation, polarity and the checked words; every keyword of that function may be given."""
+        from .navigation import decode_navigation, nav_format_for
+
+        kw.setdefault("format", nav_format_for(self.system))
+        kw.setdefault("ctx", self.ctx)
+        return decode_navigation(mon, **kw)
+
     def steering(self, acc_re: torch.Tensor, acc_im: torch.Tensor, **kw):
         """``subspace.steering_from_accumulators`` over accumulators of this loop (``run(keep=True)``) with the loop's prompt tap
         filled in: ``(steering [E, K, M], eigenvalues)`` on the device; every keyword of that function may be given."""

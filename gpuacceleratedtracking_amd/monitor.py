@@ -13,7 +13,8 @@ the decibels are made here, in numpy, from the raw sums.  A ``TrackMonitor`` of 
 them back (after ``ctx.sync()``) at the first look at a value.
 
 The bits carry the Costas loop's half-cycle ambiguity: the arctan discriminator locks to the carrier or to its negative, so all
-bits of a channel may be inverted.  Frame synchronisation (a preamble) resolves it and is not part of this layer."""
+bits of a channel may be inverted.  Frame synchronisation (a preamble) resolves it and is not part of this layer: it is
+``navigation.decode_navigation`` / ``TrackingLoop.navigation``, which take a ``TrackMonitor`` as it is."""
 from __future__ import annotations
 
 import ctypes as C

@@ -1175,6 +1175,106 @@ GAT_API int32_t gat_subspace_plan(int64_t acc_block_stride, int32_t num_blocks, 
                                   int32_t num_ants, int32_t tap_index, int32_t blocks_per_estimate, int32_t eig_matrices,
                                   int32_t eig_order, int32_t eig_vectors, gat_subspace_plan_info *plan);
 
+/* ---- navigation data: frame synchronisation, LNAV parity, CNAV Viterbi decoding and CRC-24Q ------------------------------
+ * What a receiver makes of the monitor's data symbols: where a subframe begins, whether the Costas loop locked to the
+ * carrier or to its negative, and which words passed their check.  The input is gat_track_monitor's sym_re, double
+ * [K][symbol_capacity], with the monitor's channel records (null: every row is full) telling how many symbols n_k =
+ * clamp(num_symbols, 0, symbol_capacity) of a row count; the records are read on the device.  A positive symbol is a 0
+ * bit, a non-finite symbol counts as 0.  Everything is integer arithmetic but for the quantiser's scale, every sum is
+ * sequential in the stated order and every expression is evaluated as written (csrc/gat_nav.h, shared by the kernels and
+ * the host twin: the same bits).  The yardstick is IS-GPS-200 (LNAV, CNAV, CRC-24Q) and IS-GPS-705 (L5).
+ *   bits     GAT_NAV_LNAV: one phase (P = 1), bit j = sym_re[j] < 0, n_k bits.  GAT_NAV_CNAV: two phases (P = 2), the
+ *            symbols quantised and decoded by a Viterbi decoder from either symbol of a pair, T = floor((n_k - ph) / 2)
+ *            bits of phase ph.  bit_capacity = symbol_capacity / P.
+ *   quantise partial sum l < 64 adds |x[l]|, |x[l + 64]|, .. in that order from +0, S adds the 64 partials in l order from
+ *            +0, unit = S / n_k; unit not finite or not > 0: every q = 0; else v = (x * 16.0) / unit, q = 127 for v >= 127,
+ *            -127 for v <= -127, else (int) rint(v).
+ *   decode   G1 = 171, G2 = 133 (octal; the MSB is the current input: G1 taps delays 0 1 2 3 6, G2 delays 0 2 3 5 6),
+ *            G1's symbol first, neither inverted.  The state holds the six previous inputs, the newest in bit 5: s' =
+ *            (u << 5) | (s >> 1), the predecessors of s' are ((s' & 31) << 1) | b.  Step t of phase ph reads q[ph + 2t] and
+ *            q[ph + 2t + 1]; the metrics are int32, 0 in every state at the start, the branch metric is (1 - 2 c1) q0 +
+ *            (1 - 2 c2) q1, the larger sum survives and a tie keeps b = 0; nothing is normalised (at most 254 a step).
+ *            The traceback starts at the final state of the largest metric (the lowest on a tie), which is
+ *            path_metric[k][ph]; the bit of step t is bit 5 of the state after step t.
+ *   frames   a candidate is (ph, o, p): phase, offset o in 0 .. 299, polarity p XORed to every bit.  Frame f covers bits
+ *            o + 300 f .. o + 300 f + 299; only frames wholly inside the n_k bits (LNAV) or inside bits [0, T -
+ *            GAT_NAV_TAIL_BITS) (CNAV) count.  LNAV: a word is held in 32 bits, D29* in bit 31, D30* in bit 30, d1 .. d24
+ *            in bits 29 .. 6, D25 .. D30 in bits 5 .. 0; with bit 30 set it is XORed with 0x3FFFFFC0; parity bit i = the
+ *            parity of word & mask[i], masks 0xBB1F3480 0x5D8F9A40 0xAEC7CD00 0x5763E680 0x6BB1F340 0x8B7A89C0.  Word 1
+ *            is checked with D29* = D30* = 0, word w > 1 with bits 29 and 30 of word w - 1.  A frame hits when its first
+ *            eight bits are 10001011, words 1 and 2 pass, bits 29 and 30 of word 2 are 0 and the subframe ID (d20 .. d22 of
+ *            word 2) is in 1 .. 5.  CNAV: a frame hits when its first eight bits are 10001011 and CRC-24Q (polynomial
+ *            0x1864CFB, initial value 0, MSB first, not reflected) over its 300 bits is 0.
+ *   choice   score = the hitting frames of a candidate; the largest score wins, ties to the lowest ph, then the lowest o,
+ *            then p = 0; second_score = the largest score of any other candidate.  score < min_frames: no sync --
+ *            frame_offset = -1, symbol_phase = inverted = num_frames = tow_steps = 0, num_bits of phase 0.
+ *   record   every whole frame of the chosen candidate, up to max_frames, hit or not; rows from num_frames on are zero.
+ *            status bit 0: the preamble; LNAV bits 1 .. 10: the parity of words 1 .. 10; CNAV bit 1: the CRC.  words:
+ *            LNAV d1 .. d24 (D30* removed) in bits 29 .. 6 and the received parity in bits 5 .. 0; CNAV message bits
+ *            30 i + 1 .. 30 i + 30 in bits 29 .. 0 of word i.  LNAV: tow = d1 .. d17 of word 2, id = the subframe ID, prn =
+ *            0; CNAV: prn = bits 9 .. 14, id = bits 15 .. 20 (the message type), tow = bits 21 .. 37.  tow_steps counts the
+ *            neighbouring pairs of written frames with every status bit set and tow[f + 1] = (tow[f] + 1) mod 100800.
+ * Outputs, every one optional (null: not written; at least one is given): channels [K]; frames [K][max_frames]; decoded
+ * uint8 [K][P][bit_capacity], the bits of every phase before the polarity, 0 from a row's count on; path_metric int32
+ * [K][P] (LNAV: 0).  symbol_capacity = 0 and n_k = 0 are legal: no sync, zeros.  There is no state between calls.
+ * The call enqueues on the context's stream, does not synchronise and allocates nothing but the context's scratch; the
+ * choice is made on the device and read there by the kernel that writes the frames.  No atomics: the same bits every call.
+ * Refusals, all before any launch (the host twin: before any write): GAT_ERR_ARG for a null sym_re or config, a wrong
+ * struct_size, num_channels < 1, symbol_capacity < 0, max_frames or min_frames < 1, an unknown format and a call with
+ * every output null; GAT_ERR_RANGE for num_channels above GAT_MAX_MONITOR_CHANNELS, symbol_capacity above
+ * GAT_MAX_MONITOR_BLOCKS, num_channels * max_frames above 2^31 - 1 workgroups of 256 and a call whose scratch would exceed
+ * 1 GiB (CNAV: about 10 bytes for every symbol of the capacity). */
+#define GAT_NAV_LNAV 0        /* GPS L1 C/A legacy message: hard bits, 300-bit subframes of ten 30-bit words, (32,26) parity */
+#define GAT_NAV_CNAV 1        /* GPS L5 I5 (and L2C) CNAV: rate-1/2 K=7 FEC symbols, 300-bit messages, CRC-24Q */
+#define GAT_NAV_FRAME_BITS 300
+#define GAT_NAV_TAIL_BITS 32  /* CNAV: decoded bits this close to the end of the traceback are not searched for frames */
+typedef struct gat_nav_config {
+    uint32_t struct_size;     /* sizeof(gat_nav_config) */
+    int32_t format;           /* GAT_NAV_LNAV or GAT_NAV_CNAV */
+    int32_t symbol_capacity;  /* row stride of sym_re: the monitor's floor(B / Pd) */
+    int32_t max_frames;       /* rows of `frames` per channel, >= 1 */
+    int32_t min_frames;       /* >= 1: a score below it means no sync */
+} gat_nav_config;
+typedef struct gat_nav_channel {
+    int32_t frame_offset;     /* decoded-bit index of bit 1 of frame 0, or -1 */
+    int32_t symbol_phase;     /* CNAV: 0 / 1, which symbol starts a pair; LNAV: 0 */
+    int32_t inverted;         /* 1: every bit of this channel was inverted */
+    int32_t score;
+    int32_t second_score;     /* the best score of any other (phase, offset, polarity) */
+    int32_t num_frames;
+    int32_t num_bits;         /* decoded bits of the chosen phase */
+    int32_t tow_steps;
+} gat_nav_channel;
+typedef struct gat_nav_frame {
+    int32_t status;
+    int32_t tow;
+    int32_t id;
+    int32_t prn;
+    uint32_t words[10];
+} gat_nav_frame;
+GAT_API int32_t gat_nav_decode(gat_ctx *ctx, const double *sym_re_dev, const gat_monitor_channel *mon_channels_dev,
+                               int32_t num_channels, const gat_nav_config *config, gat_nav_channel *channels,
+                               gat_nav_frame *frames, uint8_t *decoded, int32_t *path_metric);
+/* The same rule in plain loops on the HOST (csrc/gat_nav.h, shared with the device): every pointer is host memory; needs
+ * no context and no device.  The bit-exact reference of the device call, with the same refusals. */
+GAT_API int32_t gat_nav_decode_host(const double *sym_re_host, const gat_monitor_channel *mon_channels_host, int32_t num_channels,
+                                    const gat_nav_config *config, gat_nav_channel *channels, gat_nav_frame *frames,
+                                    uint8_t *decoded, int32_t *path_metric);
+/* What gat_nav_decode would do with a call (csrc/gat_nav_plan.h; no context, no device, nothing is read but config; sized
+ * by symbol_capacity): the counts, the bytes of context scratch and the workgroups of each kernel -- slice (LNAV), score
+ * and frames 256 threads a workgroup, quantise (one channel) and trellis (one channel and phase) one wave of 64 lanes a
+ * workgroup, the choice one wave a channel, four to a workgroup.  The plan is that of a call with every output given (a
+ * call without `decoded` keeps the bits in the scratch besides: K * P * bit_capacity bytes more).  The refusals are the call's. */
+typedef struct gat_nav_plan {
+    uint32_t struct_size; /* sizeof(gat_nav_plan), set by the caller */
+    int32_t num_phases;       /* P */
+    int32_t bit_capacity;     /* symbol_capacity / P */
+    int32_t num_candidates;   /* P * 300 * 2 a channel */
+    int32_t slice_workgroups, quantise_workgroups, trellis_workgroups, score_workgroups, pick_workgroups, frame_workgroups;
+    int64_t scratch_bytes;
+} gat_nav_plan;
+GAT_API int32_t gat_nav_decode_plan(int32_t num_channels, const gat_nav_config *config, gat_nav_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

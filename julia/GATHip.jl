@@ -1190,4 +1190,87 @@ function subspace_plan(; acc_block_stride::Integer = 0, num_blocks::Integer = 0,
     plan[]
 end
 
+# ---- navigation data: frame synchronisation, LNAV parity, CNAV Viterbi decoding and CRC-24Q (include/gat.h) ----
+const GAT_NAV_LNAV = Int32(0)   # GPS L1 C/A: hard bits, ten words of (32,26) parity to a 300-bit subframe
+const GAT_NAV_CNAV = Int32(1)   # GPS L5 I5: rate-1/2 K = 7 symbols, 300-bit messages with CRC-24Q
+const GAT_NAV_FRAME_BITS = 300
+const GAT_NAV_TAIL_BITS = 32
+# struct gat_nav_config (20 bytes)
+struct NavConfig
+    struct_size::UInt32
+    format::Int32
+    symbol_capacity::Int32    # row stride of sym_re: the monitor's floor(B / Pd)
+    max_frames::Int32
+    min_frames::Int32
+end
+NavConfig(format::Integer, symbol_capacity::Integer; max_frames::Integer = max(1, symbol_capacity ÷ (format == GAT_NAV_CNAV ? 600 : 300)),
+          min_frames::Integer = 1) = NavConfig(UInt32(sizeof(NavConfig)), Int32(format), Int32(symbol_capacity), Int32(max_frames), Int32(min_frames))
+struct NavChannel
+    frame_offset::Int32       # decoded-bit index of bit 1 of frame 0, or -1
+    symbol_phase::Int32
+    inverted::Int32
+    score::Int32
+    second_score::Int32
+    num_frames::Int32
+    num_bits::Int32
+    tow_steps::Int32
+end
+struct NavFrame
+    status::Int32
+    tow::Int32
+    id::Int32
+    prn::Int32
+    words::NTuple{10,UInt32}
+end
+struct NavPlan
+    struct_size::UInt32
+    num_phases::Int32
+    bit_capacity::Int32
+    num_candidates::Int32
+    slice_workgroups::Int32
+    quantise_workgroups::Int32
+    trellis_workgroups::Int32
+    score_workgroups::Int32
+    pick_workgroups::Int32
+    frame_workgroups::Int32
+    scratch_bytes::Int64
+end
+nav_phases(cfg::NavConfig) = cfg.format == GAT_NAV_CNAV ? 2 : 1
+# Every pointer is a device pointer; an output may be C_NULL (not written); sym_re: [capacity x K] in Julia's order, mon_channels:
+# the monitor's records (C_NULL: every row is full); frames [max_frames x K], decoded [bit_capacity x P x K], path_metric [P x K].
+# Enqueues only.
+function nav_decode!(ctx::Context, sym_re::Ptr{Float64}, num_channels::Integer, cfg::NavConfig;
+                     mon_channels::Ptr{MonitorChannel} = Ptr{MonitorChannel}(C_NULL), channels::Ptr{NavChannel} = Ptr{NavChannel}(C_NULL),
+                     frames::Ptr{NavFrame} = Ptr{NavFrame}(C_NULL), decoded::Ptr{UInt8} = Ptr{UInt8}(C_NULL),
+                     path_metric::Ptr{Int32} = Ptr{Int32}(C_NULL))
+    check(ctx, ccall((:gat_nav_decode, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Float64}, Ptr{MonitorChannel}, Int32, Ref{NavConfig}, Ptr{NavChannel}, Ptr{NavFrame}, Ptr{UInt8}, Ptr{Int32}),
+                     ctx.handle, sym_re, mon_channels, Int32(num_channels), Ref(cfg), channels, frames, decoded, path_metric))
+end
+# the same rule on host memory, the bit-exact reference of the device call: sym_re [capacity, K]; returns
+# (channels [K], frames [max_frames, K], decoded [bit_capacity, P, K], path_metric [P, K])
+function nav_decode_host(sym_re::Matrix{Float64}, format::Integer; mon_channels::Union{Nothing,Vector{MonitorChannel}} = nothing,
+                         max_frames::Integer = max(1, size(sym_re, 1) ÷ (format == GAT_NAV_CNAV ? 600 : 300)), min_frames::Integer = 1)
+    cap, K = size(sym_re)
+    cfg = NavConfig(format, cap; max_frames = max_frames, min_frames = min_frames)
+    P = nav_phases(cfg)
+    channels = Vector{NavChannel}(undef, K)
+    frames = Matrix{NavFrame}(undef, Int(max_frames), K)
+    decoded = zeros(UInt8, cap ÷ P, P, K)
+    path_metric = zeros(Int32, P, K)
+    rc = ccall((:gat_nav_decode_host, libgat), Int32,
+               (Ptr{Float64}, Ptr{MonitorChannel}, Int32, Ref{NavConfig}, Ptr{NavChannel}, Ptr{NavFrame}, Ptr{UInt8}, Ptr{Int32}),
+               sym_re, mon_channels === nothing ? Ptr{MonitorChannel}(C_NULL) : pointer(mon_channels), Int32(K), Ref(cfg), channels, frames,
+               decoded, path_metric)
+    rc == GAT_OK || throw(GatError(rc, "gat_nav_decode_host"))
+    channels, frames, decoded, path_metric
+end
+# what nav_decode! would do with a call that asks for every output, without a device
+function nav_decode_plan(num_channels::Integer, cfg::NavConfig)
+    plan = Ref(NavPlan(UInt32(sizeof(NavPlan)), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_nav_decode_plan, libgat), Int32, (Int32, Ref{NavConfig}, Ref{NavPlan}), Int32(num_channels), Ref(cfg), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_nav_decode_plan"))
+    plan[]
+end
+
 end # module
