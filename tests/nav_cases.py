@@ -25,6 +25,11 @@ def junk(rng, n):
     return b
 
 
+def junk_runs(rng, n):
+    """junk by its runs, for many rows at once: runs of one or two equal bits"""
+    return np.repeat(np.arange(n, dtype=np.uint8) & 1, rng.integers(1, 3, n))[:n]
+
+
 def lnav_frames(rng, F, tow0=1000, break_frame=None):
     out = []
     for f in range(F):
@@ -120,8 +125,9 @@ def host_call(g, sym, mon, cfg, want=OUTPUTS, K=None):
     return rc, buf, at
 
 
-def device_call(g, ctx, sym_t, mon_t, cfg, want=OUTPUTS):
-    """the same call on the device: sym_t float64 [K, cap] and mon_t (uint8 view of the records, or None) are device tensors"""
+def device_enqueue(g, ctx, sym_t, mon_t, cfg, want=OUTPUTS):
+    """the same call on the device, enqueued and not synchronised: (status, device buffer, layout); sym_t float64 [K, cap] and mon_t
+    (uint8 view of the records, or None) are device tensors"""
     import torch
 
     K = sym_t.shape[0]
@@ -130,14 +136,21 @@ def device_call(g, ctx, sym_t, mon_t, cfg, want=OUTPUTS):
     ptr = {n: (C.c_void_p(buf.data_ptr() + at[n][0]) if n in want else None) for n in OUTPUTS}
     rc = ctx.lib.gat_nav_decode(ctx._h, C.c_void_p(sym_t.data_ptr()), None if mon_t is None else C.c_void_p(mon_t.data_ptr()), K, C.byref(cfg),
                                 ptr["channels"], ptr["frames"], ptr["decoded"], ptr["path_metric"])
+    return rc, buf, at
+
+
+def device_call(g, ctx, sym_t, mon_t, cfg, want=OUTPUTS):
+    """device_enqueue, synchronised and read back: (status, buffer, layout)"""
+    rc, buf, at = device_enqueue(g, ctx, sym_t, mon_t, cfg, want)
     ctx.sync()
     return rc, buf.cpu().numpy(), at
 
 
-def check_against_ref(buf, at, fmt, sym, counts, max_frames, min_frames, what=""):
-    """every output of a call, as integers, against the restatement; returns the restatement's records"""
+def check_against_ref(buf, at, fmt, sym, counts, max_frames, min_frames, what="", decoded=None):
+    """every output of a call, as integers, against the restatement; returns the restatement's records.  decoded: what
+    ref.decode_bits gave for these symbols and counts in an earlier check, so that one stream is decoded once"""
     K = sym.shape[0]
-    dec, pm = ref.decode_bits(fmt, sym, counts)
+    dec, pm = ref.decode_bits(fmt, sym, counts) if decoded is None else decoded
     assert np.array_equal(take(buf, at, "decoded", K, fmt), dec), (what, "decoded")
     assert np.array_equal(take(buf, at, "path_metric", K, fmt), pm), (what, "path_metric")
     chans, frames = take(buf, at, "channels", K, fmt), take(buf, at, "frames", K, fmt)
@@ -151,3 +164,19 @@ def check_against_ref(buf, at, fmt, sym, counts, max_frames, min_frames, what=""
             assert (int(got["status"]), int(got["tow"]), int(got["id"]), int(got["prn"]), [int(w) for w in got["words"]]) == tuple(want), (what, k, f)
         recs.append(rec)
     return recs
+
+
+def check_certificate(buf, at, sym, counts, sent_phase=None, rows=None):
+    """CNAV: the path metric of every (channel, phase) is the metric of the decoded bits (ref.path_certificate); sent_phase[k]:
+    the phase at which row k is a code word, where that metric is then no smaller than the sent symbols' own; rows: all, or these"""
+    K = sym.shape[0]
+    dec, pm = take(buf, at, "decoded", K, ref.CNAV), take(buf, at, "path_metric", K, ref.CNAV)
+    for k in range(K) if rows is None else rows:
+        n = int(counts[k])
+        q = ref.quantise(sym[k], n).astype(np.int64)
+        for ph in (0, 1):
+            T = max(n - ph, 0) // 2
+            window = q[ph:ph + 2 * T]
+            assert ref.path_certificate(window, dec[k, ph, :T]) == pm[k, ph], (k, ph, "the metric is not the returned path's")
+            if sent_phase is not None and sent_phase[k] == ph:
+                assert pm[k, ph] >= int((window * np.sign(sym[k, ph:ph + 2 * T])).sum()), (k, ph, "the sent path scores higher")

@@ -1,7 +1,9 @@
 """Independent numpy restatement of the navigation data layer (include/gat.h, "navigation data"), written from the equations of
 the signal specifications and not from the package's code or its parity masks: the LNAV parity by the six equations of IS-GPS-200
 over the source bits, CRC-24Q by long division, the convolutional code by its delays, the quantiser, a Viterbi decoder batched
-over rows of one length, the frame search, the choice and the frame records.  Everything is compared as integers."""
+over rows of one length, the frame search, the choice and the frame records.  Everything is compared as integers.  Beside the
+Viterbi decoder stand two oracles that hold no trellis: every path of a short stream by the code's definition (exhaustive_ml),
+and the metric of a returned path at any length (path_certificate)."""
 import numpy as np
 
 LNAV, CNAV = 0, 1
@@ -114,12 +116,52 @@ def cnav_frame(b):
     return status, value(b[20:37]), value(b[14:20]), value(b[8:14]), [value(b[30 * w:30 * w + 30]) for w in range(10)]
 
 
-def fec_encode(bits):
-    u = np.concatenate([np.zeros(6, np.uint8), np.asarray(bits, np.uint8)])
-    t = np.arange(6, len(u))
-    c1 = u[t] ^ u[t - 1] ^ u[t - 2] ^ u[t - 3] ^ u[t - 6]
-    c2 = u[t] ^ u[t - 2] ^ u[t - 3] ^ u[t - 5] ^ u[t - 6]
-    return np.stack([c1, c2], axis=1).reshape(-1)
+def fec_encode(bits, state=0):
+    """the code of bits [..., T] (two symbols a bit, G1's first) from a register that holds `state` (an int, or ints that
+    broadcast over the leading axes): the six inputs before the first bit, the newest in bit 5; 0: a transmitter that starts"""
+    bits = np.asarray(bits, np.uint8)
+    before = ((np.asarray(state)[..., None] >> np.arange(6)) & 1).astype(np.uint8)
+    lead = np.broadcast_shapes(before.shape[:-1], bits.shape[:-1])
+    u = np.concatenate([np.broadcast_to(before, lead + (6,)), np.broadcast_to(bits, lead + bits.shape[-1:])], axis=-1)
+    t = np.arange(6, u.shape[-1])
+    c1 = u[..., t] ^ u[..., t - 1] ^ u[..., t - 2] ^ u[..., t - 3] ^ u[..., t - 6]
+    c2 = u[..., t] ^ u[..., t - 2] ^ u[..., t - 3] ^ u[..., t - 5] ^ u[..., t - 6]
+    return np.stack([c1, c2], axis=-1).reshape(lead + (-1,))
+
+
+def correlate(q, bits, state=0):
+    """the metric of a path: the code of bits [..., T] from `state` as +-1 symbols (a 0 is positive) against q[0 .. 2 T)"""
+    q = np.asarray(q, np.int64)
+    return ((1 - 2 * fec_encode(bits, state).astype(np.int64)) * q[:2 * np.shape(bits)[-1]]).sum(axis=-1)
+
+
+# Two oracles of the Viterbi decoder that share nothing with a trellis: no add-compare-select, no survivors, no traceback.
+def exhaustive_ml(q):
+    """Every path of T <= 10 steps by the code's definition: the metric of each of the 2^T input sequences from its best initial
+    state, int64 [2^T], indexed by the sequence read as a number, its first bit the highest."""
+    T = len(q) // 2
+    assert T <= 10
+    seqs = ((np.arange(1 << T)[:, None] >> np.arange(T - 1, -1, -1)) & 1).astype(np.uint8)
+    return correlate(q, seqs, np.arange(64)[:, None]).max(axis=0)
+
+
+def check_exhaustive_ml(q, bits, metric):
+    """path_metric is the largest metric of any path, and the returned bits are one of the paths that attain it.  Returns how
+    many input sequences do."""
+    per_seq = exhaustive_ml(q)
+    assert int(metric) == int(per_seq.max()), (metric, per_seq.max())
+    assert per_seq[value(bits)] == per_seq.max(), ("the returned bits are not a best path", list(bits), metric)
+    return int((per_seq == per_seq.max()).sum())
+
+
+def path_certificate(q, bits):
+    """The metric of the returned path at any length: the bits encoded again from each of the 64 initial states -- only the first
+    six steps depend on the state -- against q, the largest of them.  Equal to path_metric when the traceback returned the path
+    whose metric the forward pass reported.  It proves that metric and path belong together, not that the path is the best."""
+    bits = np.asarray(bits, np.uint8)
+    head = bits[:6]
+    tail = int(correlate(q, bits)) - int(correlate(q, head))  # from step 6 on the register holds the path's own bits
+    return tail + int(correlate(q, head, np.arange(64)).max())
 
 
 def quantise(x, n):
@@ -130,17 +172,17 @@ def quantise(x, n):
     a = np.zeros(rows * 64)
     a[:n] = np.abs(x)
     part = np.zeros(64)
-    for r in a.reshape(rows, 64):
-        part = part + r
-    S = 0.0
-    for v in part:
-        S = S + v
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(all="ignore"):  # a sum may overflow to +inf, a scale may be subnormal: both are inputs of the rule
+        for r in a.reshape(rows, 64):
+            part = part + r
+        S = 0.0
+        for v in part:
+            S = S + v
         unit = np.float64(S) / np.float64(n)
         if not np.isfinite(unit) or not unit > 0.0:
             return np.zeros(n, np.int8)
         v = (x * 16.0) / unit
-    return np.where(v >= 127.0, 127, np.where(v <= -127.0, -127, np.rint(v))).astype(np.int8)
+        return np.where(v >= 127.0, 127, np.where(v <= -127.0, -127, np.rint(v))).astype(np.int8)
 
 
 def _trellis_tables():
