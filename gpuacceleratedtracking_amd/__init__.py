@@ -29,6 +29,8 @@ from .loop import ResidentTrackingLoop, TrackingLoop  # noqa: F401
 from .monitor import (TrackMonitor, monitor_accumulators, monitor_accumulators_host, monitor_plan, overlay_for)  # noqa: F401
 from .navigation import (NavResult, cnav_fec_encode, cnav_message, crc24q, decode_navigation, decode_navigation_host,  # noqa: F401
                          lnav_subframe, nav_format_for, nav_plan)
+from .positioning import (Ephemeris, PositionFix, lnav_ephemerides, lnav_ephemeris, lnav_ephemeris_payloads, position_fix,  # noqa: F401
+                          position_fix_host, position_plan)
 from .sharding import DeviceGroup, ShardPlan, gather_outputs, shard_channels, shard_params  # noqa: F401
 from .spectrum import (auto_notch, find_tones, sample_spectrum, sample_spectrum_host, spectrum_stream)  # noqa: F401
 from .spacetime import (spacetime_covariance, spacetime_delay, spacetime_filter, spacetime_filter_host, spacetime_steering,  # noqa: F401

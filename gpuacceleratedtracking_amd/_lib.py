@@ -40,6 +40,10 @@ GAT_MAX_SYMBOL_BLOCKS, GAT_MAX_MONITOR_BLOCKS, GAT_MAX_MONITOR_CHANNELS = 128, 1
 GAT_ACC_COV_CHUNK, GAT_EIG_MAX_SWEEPS, GAT_EIG_INPUT_F32 = 256, 60, 1
 # navigation data (gat_nav_decode formats, the frame length and CNAV's unsearched traceback tail)
 GAT_NAV_LNAV, GAT_NAV_CNAV, GAT_NAV_FRAME_BITS, GAT_NAV_TAIL_BITS = 0, 1, 300, 32
+# position fix (gat_position_fix limits, the status bits of gat_fix and the reasons of gat_lnav_ephemeris_host)
+GAT_MAX_FIX_CHANNELS, GAT_MAX_FIX_EPOCHS = 64, 1 << 24
+GAT_FIX_FEW_SATS, GAT_FIX_SINGULAR, GAT_FIX_NONFINITE, GAT_FIX_NOT_CONVERGED, GAT_FIX_MASK_STARVED, GAT_FIX_MASKED = 1, 2, 4, 8, 16, 32
+GAT_EPH_OK, GAT_EPH_MISSING, GAT_EPH_IODE = 0, 1, 2
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -78,6 +82,8 @@ EXPORTS = [
     "gat_subspace_plan",
     # navigation data: frame synchronisation, LNAV parity, CNAV Viterbi decoding and CRC-24Q
     "gat_nav_decode", "gat_nav_decode_host", "gat_nav_decode_plan",
+    # position fix: LNAV ephemeris, satellite states and the batched least-squares solver
+    "gat_position_fix", "gat_position_fix_host", "gat_position_fix_plan", "gat_lnav_ephemeris_host", "gat_lnav_ephemeris_words_host",
 ]
 
 
@@ -263,6 +269,30 @@ NAV_FRAME_DTYPE = np.dtype([("status", "<i4"), ("tow", "<i4"), ("id", "<i4"), ("
 assert C.sizeof(NavConfig) == 20 and C.sizeof(NavPlan) == 48 and NAV_CHANNEL_DTYPE.itemsize == 32 and NAV_FRAME_DTYPE.itemsize == 56
 
 
+class FixConfig(C.Structure):
+    """gat_fix_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("max_iter", C.c_int32), ("tol_m", C.c_double), ("mask_sin", C.c_double),
+                ("init_xyz", C.c_double * 3), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FixPlan(C.Structure):
+    """gat_fix_plan (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("workgroups", C.c_int32), ("waves_per_workgroup", C.c_int32), ("threads", C.c_int32),
+                ("lds_bytes", C.c_int32), ("reserved", C.c_int32), ("scratch_bytes", C.c_int64)]
+
+
+# gat_ephemeris and gat_fix (include/gat.h)
+EPHEMERIS_INTS = ("wn", "iodc", "iode", "health", "ura", "fit")
+EPHEMERIS_DOUBLES = ("toc", "toe", "af0", "af1", "af2", "tgd", "sqrt_a", "e", "m0", "delta_n", "omega0", "i0", "omega", "omega_dot", "idot",
+                     "cuc", "cus", "crc", "crs", "cic", "cis")
+EPHEMERIS_DTYPE = np.dtype([(n, "<i4") for n in EPHEMERIS_INTS] + [(n, "<f8") for n in EPHEMERIS_DOUBLES] + [("valid", "<i4"), ("reason", "<i4")])
+FIX_DTYPE = np.dtype([("status", "<i4"), ("num_valid", "<i4"), ("num_used", "<i4"), ("iterations", "<i4"), ("x", "<f8"), ("y", "<f8"),
+                      ("z", "<f8"), ("clock_bias_s", "<f8"), ("rms_residual_m", "<f8"), ("last_step_m", "<f8"), ("gdop", "<f8"), ("pdop", "<f8")])
+assert C.sizeof(FixConfig) == 56 and C.sizeof(FixPlan) == 32 and EPHEMERIS_DTYPE.itemsize == 200 and FIX_DTYPE.itemsize == 80
+
+
 _LIB = None
 
 
@@ -382,6 +412,11 @@ def load(build_if_missing: bool = True):
         "gat_nav_decode": (i32, [vp, vp, vp, i32, C.POINTER(NavConfig), vp, vp, vp, vp]),
         "gat_nav_decode_host": (i32, [vp, vp, i32, C.POINTER(NavConfig), vp, vp, vp, vp]),
         "gat_nav_decode_plan": (i32, [i32, C.POINTER(NavConfig), C.POINTER(NavPlan)]),
+        "gat_position_fix": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(FixConfig), vp, vp, vp, vp, vp]),
+        "gat_position_fix_host": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(FixConfig), vp, vp, vp, vp, vp]),
+        "gat_position_fix_plan": (i32, [i32, i32, C.POINTER(FixConfig), C.POINTER(FixPlan)]),
+        "gat_lnav_ephemeris_host": (i32, [vp, i32, vp]),
+        "gat_lnav_ephemeris_words_host": (i32, [vp, vp]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

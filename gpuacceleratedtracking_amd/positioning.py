@@ -1,0 +1,237 @@
+"""Position fix (include/gat.h, "position fix"): from the decoder's checked words and the observables to a position::
+
+    nav = loop.navigation(mon)                                   # gat_nav_decode: subframes 1 - 3 of every channel
+    ephs = lnav_ephemerides(nav)                                 # gat_lnav_ephemeris_host: one Ephemeris a channel
+    fix = position_fix(ephs, tx_ms, tx_frac, rx_ms, rx_frac)     # gat_position_fix: enqueued, not synchronised
+    fix.xyz, fix.clock_bias_s, fix.status, fix.pdop              # per epoch
+    fix.sat, fix.resid, fix.sin_el, fix.used                     # per epoch and channel
+
+A time of the week is whole milliseconds (int32) and a fraction in seconds (float64): ``tx_ms``, ``tx_frac`` ``[E, K]`` of
+transmission, ``rx_ms``, ``rx_frac`` ``[E]`` of reception.  The work is libgat's HIP kernel (``position_fix``) or its host twin with
+the same bits (``position_fix_host``).  A ``PositionFix`` of the device call keeps device tensors and reads them back (after
+``ctx.sync()``) at the first look at a value.  ``lnav_ephemeris_payloads`` is the encoder a simulation needs: the payload bits of
+subframes 1 - 3 in the form ``lnav_subframe(payload=)`` takes."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .context import Context, get_context
+from .navigation import NavResult
+from .streams import addr, keep_alive, vp
+
+FEW_SATS, SINGULAR, NONFINITE = _lib.GAT_FIX_FEW_SATS, _lib.GAT_FIX_SINGULAR, _lib.GAT_FIX_NONFINITE
+NOT_CONVERGED, MASK_STARVED, MASKED = _lib.GAT_FIX_NOT_CONVERGED, _lib.GAT_FIX_MASK_STARVED, _lib.GAT_FIX_MASKED
+OUTPUTS = ("sat", "resid", "sin_el", "used")
+
+
+class Ephemeris:
+    """``gat_ephemeris``: SI units and radians.  Integers ``wn, iodc, iode, health, ura, fit``; floats ``toc, toe, af0, af1, af2, tgd,
+    sqrt_a, e, m0, delta_n, omega0, i0, omega, omega_dot, idot, cuc, cus, crc, crs, cic, cis``; ``valid`` and ``reason`` (why not)."""
+
+    FIELDS = _lib.EPHEMERIS_DTYPE.names
+
+    def __init__(self, **fields):
+        unknown = set(fields) - set(self.FIELDS)
+        if unknown:
+            raise TypeError(f"unknown ephemeris fields {sorted(unknown)}")
+        self.record = np.zeros((), dtype=_lib.EPHEMERIS_DTYPE)
+        self.record["valid"] = 1
+        for name, value in fields.items():
+            self.record[name] = value
+
+    @classmethod
+    def from_record(cls, record) -> "Ephemeris":
+        eph = cls()
+        eph.record = np.array(record, dtype=_lib.EPHEMERIS_DTYPE).reshape(())
+        return eph
+
+    def __getattr__(self, name):
+        if name in type(self).FIELDS:
+            return self.__dict__["record"][name].item()
+        raise AttributeError(name)
+
+    def __eq__(self, other):
+        return isinstance(other, Ephemeris) and self.record.tobytes() == other.record.tobytes()
+
+    def __repr__(self):
+        return "Ephemeris(" + ", ".join(f"{n}={self.record[n].item()!r}" for n in self.FIELDS) + ")"
+
+
+def ephemeris_records(ephs) -> np.ndarray:
+    """``gat_ephemeris [K]`` as a structured array from a sequence of ``Ephemeris`` (or such an array)"""
+    if isinstance(ephs, np.ndarray) and ephs.dtype == _lib.EPHEMERIS_DTYPE:
+        return np.ascontiguousarray(ephs.reshape(-1))
+    if isinstance(ephs, Ephemeris):
+        ephs = [ephs]
+    return np.array([e.record for e in ephs], dtype=_lib.EPHEMERIS_DTYPE).reshape(-1)
+
+
+def lnav_ephemeris(nav: NavResult, channel: int) -> Ephemeris:
+    """``gat_lnav_ephemeris_host`` on one channel's frames: the newest complete set of good subframes 1, 2 and 3 of one issue.
+    ``valid`` is 0 where there are none (``reason``: ``GAT_EPH_MISSING`` / ``GAT_EPH_IODE``)."""
+    frames = np.ascontiguousarray(nav.frames[int(channel)])
+    rec = np.zeros((), dtype=_lib.EPHEMERIS_DTYPE)
+    rc = _lib.load().gat_lnav_ephemeris_host(addr(frames), int(frames.shape[0]), addr(rec))
+    if rc != 0:
+        raise _lib.GatError(rc, "gat_lnav_ephemeris_host")
+    return Ephemeris.from_record(rec)
+
+
+def lnav_ephemerides(nav: NavResult) -> list:
+    """``lnav_ephemeris`` of every channel of the decoder's result"""
+    return [lnav_ephemeris(nav, k) for k in range(nav.frames.shape[0])]
+
+
+def lnav_ephemeris_payloads(eph: Ephemeris) -> np.ndarray:
+    """``gat_lnav_ephemeris_words_host``: uint8 ``[3, 190]``, the quantised payload bits of subframes 1, 2 and 3 -- row ``i`` is what
+    ``lnav_subframe(tow, i + 1, payload=)`` takes."""
+    bits = np.zeros((3, 190), dtype=np.uint8)
+    rec = np.ascontiguousarray(eph.record)
+    rc = _lib.load().gat_lnav_ephemeris_words_host(addr(rec), addr(bits))
+    if rc != 0:
+        raise _lib.GatError(rc, "gat_lnav_ephemeris_words_host")
+    return bits
+
+
+def fix_config(max_iter: int = 10, tol_m: float = 1e-4, mask_sin: float = -1.0, init_xyz=(0.0, 0.0, 0.0), flags: int = 0) -> _lib.FixConfig:
+    """``gat_fix_config`` from Python values.  Nothing is checked: the library refuses."""
+    cfg = _lib.FixConfig()
+    cfg.struct_size = C.sizeof(_lib.FixConfig)
+    cfg.max_iter, cfg.tol_m, cfg.mask_sin, cfg.flags = int(max_iter), float(tol_m), float(mask_sin), int(flags)
+    for i in range(3):
+        cfg.init_xyz[i] = float(init_xyz[i])
+    return cfg
+
+
+class PositionFix:
+    """The outputs of one call.  Raw: ``fixes`` (structured ``[E]``: status, num_valid, num_used, iterations, x, y, z, clock_bias_s,
+    rms_residual_m, last_step_m, gdop, pdop) and, where asked for, ``sat`` ``[E, K, 4]`` (ECEF at transmission and the clock
+    correction), ``resid`` and ``sin_el`` ``[E, K]``, ``used`` uint8 ``[E, K]``.  Derived: every field of ``fixes`` ``[E]``, ``xyz``
+    ``[E, 3]`` and ``ok`` (status 0)."""
+
+    def __init__(self, raw: dict, ctx: Context | None = None):
+        self._raw, self._host, self._ctx = raw, None, ctx
+
+    def _h(self) -> dict:
+        if self._host is None:
+            if self._ctx is not None:
+                self._ctx.sync()
+            host = {}
+            for name, v in self._raw.items():
+                a = v.cpu().numpy() if isinstance(v, torch.Tensor) else v
+                if name == "fixes":
+                    a = a.view(_lib.FIX_DTYPE).reshape(-1)
+                host[name] = a
+            self._host = host
+        return self._host
+
+    def __getattr__(self, name):
+        if name in _lib.FIX_DTYPE.names:
+            return self._h()["fixes"][name].copy()
+        if name in OUTPUTS:
+            if name not in self._raw:
+                raise AttributeError(f"{name} was not asked for (outputs=)")
+            return self._h()[name]
+        raise AttributeError(name)
+
+    fixes = property(lambda self: self._h()["fixes"])
+    ok = property(lambda self: self.fixes["status"] == 0)
+
+    @property
+    def xyz(self) -> np.ndarray:
+        f = self.fixes
+        return np.stack([f["x"], f["y"], f["z"]], axis=1)
+
+
+def _wanted(outputs) -> tuple:
+    outputs = OUTPUTS if outputs is None else tuple(outputs)
+    unknown = set(outputs) - set(OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}: choose from {OUTPUTS}")
+    return outputs
+
+
+_SHAPES = {"sat": (4,), "resid": (), "sin_el": (), "used": ()}
+
+
+def position_fix(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, outputs=None, ctx: Context | None = None, **config) -> PositionFix:
+    """``gat_position_fix`` on the device.  ``ephs``: ``Ephemeris`` objects (uploaded) or a uint8 device tensor of ``K`` records;
+    ``tx_ms`` int32 and ``tx_frac`` float64 ``[E, K]``, ``rx_ms`` int32 and ``rx_frac`` float64 ``[E]``, ``weights`` float64 ``[E, K]``
+    or None: contiguous device tensors, passed as they are.  ``outputs``: which of "sat", "resid", "sin_el", "used" to write (None:
+    all).  ``config``: ``max_iter``, ``tol_m``, ``mask_sin``, ``init_xyz``.  Enqueues on the context's stream and returns at once."""
+    want = _wanted(outputs)
+    for name, t, dt in (("tx_ms", tx_ms, torch.int32), ("tx_frac", tx_frac, torch.float64), ("rx_ms", rx_ms, torch.int32),
+                        ("rx_frac", rx_frac, torch.float64), ("weights", weights, torch.float64)):
+        if t is None and name == "weights":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} device tensor")
+        if not t.is_cuda or t.device != tx_ms.device:
+            raise ValueError(f"{name} must live on the HIP device, the same one as tx_ms")
+    if tx_ms.dim() != 2 or tx_frac.shape != tx_ms.shape or (weights is not None and weights.shape != tx_ms.shape):
+        raise ValueError("tx_ms, tx_frac and weights must be [E, K]")
+    E, K = (int(v) for v in tx_ms.shape)
+    if rx_ms.shape != (E,) or rx_frac.shape != (E,):
+        raise ValueError("rx_ms and rx_frac must be [E]")
+    dev = tx_ms.device
+    if isinstance(ephs, torch.Tensor):
+        eph_dev = ephs
+        if eph_dev.dtype != torch.uint8 or not eph_dev.is_contiguous() or eph_dev.numel() != K * _lib.EPHEMERIS_DTYPE.itemsize or eph_dev.device != dev:
+            raise ValueError("ephs must be the K records as a contiguous uint8 tensor on the device of tx_ms")
+    else:
+        recs = ephemeris_records(ephs)
+        if recs.shape[0] != K:
+            raise ValueError(f"{recs.shape[0]} ephemerides for {K} channels")
+        eph_dev = torch.from_numpy(recs.view(np.uint8).reshape(K, -1).copy()).to(dev)
+    if ctx is None:
+        ctx = get_context(dev)
+    cfg = fix_config(**config)
+    raw = {"fixes": torch.empty((E, _lib.FIX_DTYPE.itemsize), dtype=torch.uint8, device=dev)}
+    for name in want:
+        raw[name] = torch.empty((E, K) + _SHAPES[name], dtype=torch.uint8 if name == "used" else torch.float64, device=dev)
+    rc = ctx.lib.gat_position_fix(ctx._h, vp(eph_dev), vp(tx_ms), vp(tx_frac), vp(rx_ms), vp(rx_frac), vp(weights), E, K, C.byref(cfg),
+                                  vp(raw["fixes"]), vp(raw.get("sat")), vp(raw.get("resid")), vp(raw.get("sin_el")), vp(raw.get("used")))
+    ctx.check(rc, "gat_position_fix")
+    return keep_alive(PositionFix(raw, ctx), eph_dev, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+
+
+def position_fix_host(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, outputs=None, **config) -> PositionFix:
+    """``gat_position_fix_host``: the same rule and the same bits over numpy arrays; needs no device."""
+    want = _wanted(outputs)
+    recs = ephemeris_records(ephs)
+    tx_ms, rx_ms = np.ascontiguousarray(tx_ms, dtype=np.int32), np.ascontiguousarray(rx_ms, dtype=np.int32)
+    tx_frac, rx_frac = np.ascontiguousarray(tx_frac, dtype=np.float64), np.ascontiguousarray(rx_frac, dtype=np.float64)
+    if tx_ms.ndim != 2 or tx_frac.shape != tx_ms.shape:
+        raise ValueError("tx_ms and tx_frac must be [E, K]")
+    E, K = tx_ms.shape
+    if rx_ms.shape != (E,) or rx_frac.shape != (E,) or recs.shape[0] != K:
+        raise ValueError("rx_ms and rx_frac must be [E], and there must be K ephemerides")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if weights.shape != tx_ms.shape:
+            raise ValueError("weights must be [E, K]")
+    cfg = fix_config(**config)
+    raw = {"fixes": np.zeros(E, dtype=_lib.FIX_DTYPE)}
+    for name in want:
+        raw[name] = np.zeros((E, K) + _SHAPES[name], dtype=np.uint8 if name == "used" else np.float64)
+    rc = _lib.load().gat_position_fix_host(addr(recs), addr(tx_ms), addr(tx_frac), addr(rx_ms), addr(rx_frac), addr(weights), E, K,
+                                           C.byref(cfg), addr(raw["fixes"]), addr(raw.get("sat")), addr(raw.get("resid")),
+                                           addr(raw.get("sin_el")), addr(raw.get("used")))
+    if rc != 0:
+        raise _lib.GatError(rc, "gat_position_fix_host")
+    return PositionFix(raw)
+
+
+def position_plan(num_epochs: int, num_channels: int, **config) -> dict:
+    """``gat_position_fix_plan``: the workgroups, the waves (epochs) of each, its threads and LDS, and the scratch bytes of such a call."""
+    cfg = fix_config(**config)
+    plan = _lib.FixPlan()
+    plan.struct_size = C.sizeof(_lib.FixPlan)
+    rc = _lib.load().gat_position_fix_plan(int(num_epochs), int(num_channels), C.byref(cfg), C.byref(plan))
+    if rc != 0:
+        raise _lib.GatError(rc, "gat_position_fix_plan")
+    return {n: int(getattr(plan, n)) for n, _ in _lib.FixPlan._fields_ if n not in ("struct_size", "reserved")}

@@ -1275,6 +1275,149 @@ typedef struct gat_nav_plan {
 } gat_nav_plan;
 GAT_API int32_t gat_nav_decode_plan(int32_t num_channels, const gat_nav_config *config, gat_nav_plan *plan);
 
+/* ---- position fix: LNAV ephemeris, satellite states and a batched least-squares solver -----------------------------------
+ * What a receiver makes of the checked words and of its observables: an ephemeris from subframes 1 - 3, the satellite's
+ * clock and ECEF position at the time of transmission, and per measurement epoch the receiver's position and clock bias by
+ * iterated weighted least squares.  GPS LNAV, L1 single frequency (T_GD applied), no atmosphere model.  The yardstick is
+ * the user algorithm of IS-GPS-200 (tables 20-I .. 20-IV).  FP64 throughout, every expression evaluated as written without
+ * contraction, every sum over satellites in channel order from +0 (an unused channel adds nothing), and no libm
+ * transcendental: + - * /, sqrt, rint and explicit fused multiply-adds only (csrc/gat_fix.h, shared by the kernel and the
+ * host twin: the same bits).
+ *   sincos   q = rint(x * 2/pi); r = x - q P1 - q P2 - q P3 by three fused multiply-adds, P1 and P2 the first and second 33
+ *            bits of pi/2, P3 the rest; sin and cos of r by the Taylor polynomials of degree 17 and 18 in Horner form;
+ *            the quadrant from q mod 4.  |error| <= 1e-15 on |x| <= 64.
+ *   times    a time of the week is whole milliseconds (int32, 0 .. 604799999) and a fraction in seconds (double, [0, 1e-3)).
+ *            Transmission tx_ms, tx_frac [E][K]; reception (nominal, by the receiver's clock) rx_ms, rx_frac [E].  A
+ *            negative ms or a non-finite fraction: no measurement (of the channel; of the whole epoch for rx).
+ *            t_sv = tx_ms * 1e-3 + tx_frac; rho = c (1e-3 wrap(rx_ms - tx_ms) + (rx_frac - tx_frac)), the wrap into
+ *            [-302400000, 302400000) in integers.  Differences of seconds wrap into [-302400, 302400).
+ *   clock    dt = wrap(t_sv - toc); dts = af0 + af1 dt + af2 dt dt + F e sqrt_a sin E - tgd with E solved at t_sv;
+ *            t = t_sv - dts.  F = -4.442807633e-10.
+ *   orbit    A = sqrt_a^2; n = sqrt(mu / A^3) + delta_n; tk = wrap(t - toe); M = m0 + n tk; E by exactly 8 Newton steps
+ *            E <- E - (E - e sin E - M) / (1 - e cos E) from E = M; cos nu = (cos E - e) / (1 - e cos E), sin nu =
+ *            sqrt(1 - e^2) sin E / (1 - e cos E); Phi = nu + omega and u = Phi + du by the angle-addition formulas, 2 Phi
+ *            by the double-angle formulas; du, dr, di = c?s sin 2Phi + c?c cos 2Phi; r = A (1 - e cos E) + dr; i = i0 +
+ *            di + idot tk; Omega = omega0 + (omega_dot - OmegaE) tk - OmegaE toe; x' = r cos u, y' = r sin u; X = x' cos
+ *            Omega - y' cos i sin Omega, Y = x' sin Omega + y' cos i cos Omega, Z = y' sin i.  mu = 3.986005e14, OmegaE =
+ *            7.2921151467e-5, c = 299792458.
+ *   usable   a channel counts in an epoch (num_valid) when its ephemeris has valid != 0, 0 <= e < 0.5 and sqrt_a > 0, both
+ *            times are given and its state and pseudorange are finite; it is used when besides its weight (1 without
+ *            weights) is finite and > 0.  An unusable ephemeris is not an error.
+ *   solver   unknowns (x, y, z, b), b = c * the receiver's clock error; start init_xyz, b = 0.  An iteration: per usable
+ *            channel the travel time tau is 0.075 s until the channel has a range and r / c of its last range after, the
+ *            satellite is turned about z by OmegaE tau, r is the range from the receiver to it, los the unit vector, v =
+ *            rho - (r + b - c dts), the row a = (-los, 1); the 14 sums of w a_i a_j (i <= j) and w a_i v over the used
+ *            channels; N = L L^T column by column, L L^T d = right side; the state moves by d.  A pass ends when |d_xyz| <
+ *            tol_m or after max_iter iterations (GAT_FIX_NOT_CONVERGED, the outputs stand).  Fewer than 4 used channels
+ *            (GAT_FIX_FEW_SATS), a sum or a step that is not finite (GAT_FIX_NONFINITE; the sums are tested first) and a
+ *            pivot d_j not > 2^-40 N[j][j] -- not positive but for rounding -- (GAT_FIX_SINGULAR) end the epoch with every
+ *            output of it zero but status, num_valid, num_used and iterations.
+ *   mask     after a converged first pass, with mask_sin > -1 and |xyz| >= 1e6 m: sin el = (xyz / |xyz|) . los at that
+ *            state; the used set keeps the channels with sin el >= mask_sin.  If that changed it and at least 4 remain, a
+ *            second pass runs from the first one's state (GAT_FIX_MASKED; the iterations add, each pass has max_iter of
+ *            them); with fewer than 4 the first pass stands (GAT_FIX_MASK_STARVED).
+ *   record   at the final state the rows are evaluated once more: rms_residual_m = sqrt(sum v^2 / num_used) over the used
+ *            channels, gdop and pdop from the diagonal of the unweighted (A^T A)^-1 through the same Cholesky (0 where it
+ *            fails), clock_bias_s = b / c, last_step_m = the last |d_xyz|.
+ * Optional outputs (null: not written): sat double [E][K][4], the ECEF position at transmission (in the frame of that
+ * instant) and dts, zeros for a channel that does not count; resid double [E][K], v at the final state of every counting
+ * channel, used or not; sin_el double [E][K] likewise (0 within 1e6 m of the centre); used uint8 [E][K].  The last three
+ * are zero in an epoch that failed.  One epoch never touches another.
+ * gat_position_fix enqueues one kernel on the context's stream -- a wave of 64 lanes an epoch, a lane a channel, four
+ * epochs a workgroup --, does not synchronise, allocates nothing and uses no atomics: the same bits every call.
+ * Refusals, all before any launch (the host twin: before any write): GAT_ERR_ARG for a null required pointer (ephemerides,
+ * the four times, config, fixes), a wrong struct_size, E or K < 1, max_iter < 1, tol_m not > 0, a mask_sin or init_xyz
+ * that is not finite and non-zero flags; GAT_ERR_RANGE for K above GAT_MAX_FIX_CHANNELS and E above 2^24. */
+#define GAT_MAX_FIX_CHANNELS 64
+#define GAT_MAX_FIX_EPOCHS 16777216
+#define GAT_FIX_FEW_SATS 1
+#define GAT_FIX_SINGULAR 2
+#define GAT_FIX_NONFINITE 4
+#define GAT_FIX_NOT_CONVERGED 8
+#define GAT_FIX_MASK_STARVED 16
+#define GAT_FIX_MASKED 32
+/* gat_lnav_ephemeris_host's reason codes */
+#define GAT_EPH_OK 0
+#define GAT_EPH_MISSING 1  /* no frame with every status bit set for one of subframes 1, 2, 3 */
+#define GAT_EPH_IODE 2     /* no subframe 1 has subframes 2 and 3 whose IODE is the low 8 bits of its IODC */
+typedef struct gat_ephemeris {
+    int32_t wn;           /* week number mod 1024 */
+    int32_t iodc, iode;
+    int32_t health, ura;  /* the 6-bit health and the 4-bit URA index as sent */
+    int32_t fit;          /* the fit interval flag */
+    double toc, toe;      /* s */
+    double af0, af1, af2; /* s, s/s, s/s^2 */
+    double tgd;           /* s */
+    double sqrt_a;        /* m^(1/2) */
+    double e;
+    double m0, delta_n;   /* rad, rad/s */
+    double omega0, i0, omega, omega_dot, idot; /* rad, rad/s */
+    double cuc, cus, crc, crs, cic, cis;       /* rad, rad, m, m, rad, rad */
+    int32_t valid;        /* 1: usable */
+    int32_t reason;       /* GAT_EPH_* */
+} gat_ephemeris;
+typedef struct gat_fix_config {
+    uint32_t struct_size; /* sizeof(gat_fix_config) */
+    int32_t max_iter;     /* iterations a pass, >= 1 (10) */
+    double tol_m;         /* > 0 (1e-4) */
+    double mask_sin;      /* sin of the elevation mask; -1: off */
+    double init_xyz[3];   /* the start, m (the Earth's centre) */
+    uint32_t flags;       /* 0 */
+    uint32_t reserved;
+} gat_fix_config;
+typedef struct gat_fix {
+    int32_t status;       /* GAT_FIX_* bits; 0: a converged fix */
+    int32_t num_valid;    /* channels that count in this epoch */
+    int32_t num_used;     /* channels in the last pass's equations */
+    int32_t iterations;
+    double x, y, z;       /* ECEF at reception, m */
+    double clock_bias_s;  /* the receiver's clock minus GPS time */
+    double rms_residual_m;
+    double last_step_m;
+    double gdop, pdop;
+} gat_fix;
+GAT_API int32_t gat_position_fix(gat_ctx *ctx, const gat_ephemeris *eph_dev, const int32_t *tx_ms_dev, const double *tx_frac_dev,
+                                 const int32_t *rx_ms_dev, const double *rx_frac_dev, const double *weights_dev, int32_t num_epochs,
+                                 int32_t num_channels, const gat_fix_config *config, gat_fix *fixes_dev, double *sat_dev,
+                                 double *resid_dev, double *sin_el_dev, uint8_t *used_dev);
+/* The same rule in plain loops on the HOST (csrc/gat_fix.h, shared with the device): every pointer is host memory; needs
+ * no context and no device.  The bit-exact reference of the device call, with the same refusals. */
+GAT_API int32_t gat_position_fix_host(const gat_ephemeris *eph_host, const int32_t *tx_ms_host, const double *tx_frac_host,
+                                      const int32_t *rx_ms_host, const double *rx_frac_host, const double *weights_host,
+                                      int32_t num_epochs, int32_t num_channels, const gat_fix_config *config, gat_fix *fixes,
+                                      double *sat, double *resid, double *sin_el, uint8_t *used);
+/* What gat_position_fix would do with a call (csrc/gat_fix_plan.h; no context, no device, nothing is read but config).  The
+ * refusals are the call's, but for the pointers. */
+typedef struct gat_fix_plan {
+    uint32_t struct_size; /* sizeof(gat_fix_plan), set by the caller */
+    int32_t workgroups;
+    int32_t waves_per_workgroup;  /* = epochs a workgroup: a wave an epoch */
+    int32_t threads;
+    int32_t lds_bytes;
+    int32_t reserved;
+    int64_t scratch_bytes;        /* 0: the kernel keeps an epoch in registers and LDS */
+} gat_fix_plan;
+GAT_API int32_t gat_position_fix_plan(int32_t num_epochs, int32_t num_channels, const gat_fix_config *config, gat_fix_plan *plan);
+/* One channel's ephemeris from its gat_nav_frame records (gat_nav_decode, GAT_NAV_LNAV), on the host: the newest complete
+ * set -- the frames of subframe 1 with every status bit set are tried from the newest back, each with the newest such
+ * frames of subframes 2 and 3 whose IODE equals the low 8 bits of its IODC, and the first that has both is taken, so that
+ * the last complete issue stands until a new one is complete.  Found: *eph filled, valid = 1, reason = GAT_EPH_OK; else
+ * *eph zero but for reason.  Returns GAT_ERR_ARG for
+ * a null pointer or num_frames < 0, else GAT_OK.  Data bits d1 .. d24 of words 3 .. 10, the MSB first, signed fields in
+ * two's complement; semicircles become radians with pi = 3.1415926535898:
+ *   subframe 1  word 3: WN(10) L2 codes(2) URA(4) health(6) IODC MSBs(2); word 7: 16 reserved, TGD(8 s, 2^-31); word 8: IODC
+ *               LSBs(8) toc(16, 2^4); word 9: af2(8 s, 2^-55) af1(16 s, 2^-43); word 10: af0(22 s, 2^-31)
+ *   subframe 2  word 3: IODE(8) Crs(16 s, 2^-5); word 4: delta_n(16 s, 2^-43 sc/s) M0 31..24; word 5: M0 23..0 (32 s, 2^-31 sc);
+ *               word 6: Cuc(16 s, 2^-29) e 31..24; word 7: e 23..0 (32 u, 2^-33); word 8: Cus(16 s, 2^-29) sqrtA 31..24;
+ *               word 9: sqrtA 23..0 (32 u, 2^-19); word 10: toe(16, 2^4) fit(1) AODO(5)
+ *   subframe 3  word 3: Cic(16 s, 2^-29) Omega0 31..24; word 4: Omega0 23..0 (32 s, 2^-31 sc); word 5: Cis(16 s, 2^-29) i0
+ *               31..24; word 6: i0 23..0 (32 s, 2^-31 sc); word 7: Crc(16 s, 2^-5) omega 31..24; word 8: omega 23..0 (32 s,
+ *               2^-31 sc); word 9: OmegaDot(24 s, 2^-43 sc/s); word 10: IODE(8) IDOT(14 s, 2^-43 sc/s) */
+GAT_API int32_t gat_lnav_ephemeris_host(const gat_nav_frame *frames, int32_t num_frames, gat_ephemeris *eph);
+/* The inverse: the 190 payload bits (d1 .. d24 of words 3 .. 9, d1 .. d22 of word 10; one bit a byte) of subframes 1, 2 and
+ * 3, every field rint(value / scale) kept to its width; L2 codes, reserved bits and AODO are 0.  valid is not read. */
+GAT_API int32_t gat_lnav_ephemeris_words_host(const gat_ephemeris *eph, uint8_t *payload_bits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1273,4 +1273,138 @@ function nav_decode_plan(num_channels::Integer, cfg::NavConfig)
     plan[]
 end
 
+# ---- position fix: LNAV ephemeris, satellite states and the batched least-squares solver (include/gat.h) ----
+const GAT_MAX_FIX_CHANNELS = 64
+const GAT_MAX_FIX_EPOCHS = 16777216
+const GAT_FIX_FEW_SATS = Int32(1)
+const GAT_FIX_SINGULAR = Int32(2)
+const GAT_FIX_NONFINITE = Int32(4)
+const GAT_FIX_NOT_CONVERGED = Int32(8)
+const GAT_FIX_MASK_STARVED = Int32(16)
+const GAT_FIX_MASKED = Int32(32)
+const GAT_EPH_OK = Int32(0)
+const GAT_EPH_MISSING = Int32(1)
+const GAT_EPH_IODE = Int32(2)
+# struct gat_ephemeris (200 bytes): SI units and radians
+struct Ephemeris
+    wn::Int32
+    iodc::Int32
+    iode::Int32
+    health::Int32
+    ura::Int32
+    fit::Int32
+    toc::Float64
+    toe::Float64
+    af0::Float64
+    af1::Float64
+    af2::Float64
+    tgd::Float64
+    sqrt_a::Float64
+    e::Float64
+    m0::Float64
+    delta_n::Float64
+    omega0::Float64
+    i0::Float64
+    omega::Float64
+    omega_dot::Float64
+    idot::Float64
+    cuc::Float64
+    cus::Float64
+    crc::Float64
+    crs::Float64
+    cic::Float64
+    cis::Float64
+    valid::Int32
+    reason::Int32
+end
+# struct gat_fix_config (56 bytes)
+struct FixConfig
+    struct_size::UInt32
+    max_iter::Int32
+    tol_m::Float64
+    mask_sin::Float64             # sin of the elevation mask; -1: off
+    init_xyz::NTuple{3,Float64}
+    flags::UInt32
+    reserved::UInt32
+end
+FixConfig(; max_iter::Integer = 10, tol_m::Real = 1e-4, mask_sin::Real = -1.0, init_xyz = (0.0, 0.0, 0.0)) =
+    FixConfig(UInt32(sizeof(FixConfig)), Int32(max_iter), Float64(tol_m), Float64(mask_sin), Float64.(Tuple(init_xyz)), UInt32(0), UInt32(0))
+# struct gat_fix (80 bytes)
+struct Fix
+    status::Int32
+    num_valid::Int32
+    num_used::Int32
+    iterations::Int32
+    x::Float64
+    y::Float64
+    z::Float64
+    clock_bias_s::Float64
+    rms_residual_m::Float64
+    last_step_m::Float64
+    gdop::Float64
+    pdop::Float64
+end
+struct FixPlan
+    struct_size::UInt32
+    workgroups::Int32
+    waves_per_workgroup::Int32
+    threads::Int32
+    lds_bytes::Int32
+    reserved::Int32
+    scratch_bytes::Int64
+end
+# Every pointer is a device pointer; weights and the four last outputs may be C_NULL.  In Julia's order tx_ms, tx_frac, weights,
+# resid, sin_el, used are [K x E], sat [4 x K x E], rx_ms, rx_frac, fixes [E].  Enqueues only.
+function position_fix!(ctx::Context, eph::Ptr{Ephemeris}, tx_ms::Ptr{Int32}, tx_frac::Ptr{Float64}, rx_ms::Ptr{Int32}, rx_frac::Ptr{Float64},
+                       num_epochs::Integer, num_channels::Integer, cfg::FixConfig, fixes::Ptr{Fix};
+                       weights::Ptr{Float64} = Ptr{Float64}(C_NULL), sat::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                       resid::Ptr{Float64} = Ptr{Float64}(C_NULL), sin_el::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                       used::Ptr{UInt8} = Ptr{UInt8}(C_NULL))
+    check(ctx, ccall((:gat_position_fix, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Ephemeris}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ref{FixConfig},
+                      Ptr{Fix}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+                     ctx.handle, eph, tx_ms, tx_frac, rx_ms, rx_frac, weights, Int32(num_epochs), Int32(num_channels), Ref(cfg), fixes, sat,
+                     resid, sin_el, used))
+end
+# the same rule on host memory, the bit-exact reference of the device call: tx_ms, tx_frac [K, E]; returns
+# (fixes [E], sat [4, K, E], resid [K, E], sin_el [K, E], used [K, E])
+function position_fix_host(eph::Vector{Ephemeris}, tx_ms::Matrix{Int32}, tx_frac::Matrix{Float64}, rx_ms::Vector{Int32}, rx_frac::Vector{Float64};
+                           weights::Union{Nothing,Matrix{Float64}} = nothing, cfg::FixConfig = FixConfig())
+    K, E = size(tx_ms)
+    fixes = Vector{Fix}(undef, E)
+    sat = zeros(Float64, 4, K, E)
+    resid = zeros(Float64, K, E)
+    sin_el = zeros(Float64, K, E)
+    used = zeros(UInt8, K, E)
+    rc = ccall((:gat_position_fix_host, libgat), Int32,
+               (Ptr{Ephemeris}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ref{FixConfig}, Ptr{Fix},
+                Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+               eph, tx_ms, tx_frac, rx_ms, rx_frac, weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights), Int32(E), Int32(K), Ref(cfg),
+               fixes, sat, resid, sin_el, used)
+    rc == GAT_OK || throw(GatError(rc, "gat_position_fix_host"))
+    fixes, sat, resid, sin_el, used
+end
+# what position_fix! would do with a call, without a device
+function position_fix_plan(num_epochs::Integer, num_channels::Integer, cfg::FixConfig = FixConfig())
+    plan = Ref(FixPlan(UInt32(sizeof(FixPlan)), 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_position_fix_plan, libgat), Int32, (Int32, Int32, Ref{FixConfig}, Ref{FixPlan}), Int32(num_epochs), Int32(num_channels),
+               Ref(cfg), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_position_fix_plan"))
+    plan[]
+end
+# one channel's ephemeris from its frame records (nav_decode_host's frames[:, k]); valid = 0 and a reason where there is none
+function lnav_ephemeris(frames::Vector{NavFrame})
+    eph = Ref{Ephemeris}()
+    rc = ccall((:gat_lnav_ephemeris_host, libgat), Int32, (Ptr{NavFrame}, Int32, Ref{Ephemeris}), frames, Int32(length(frames)), eph)
+    rc == GAT_OK || throw(GatError(rc, "gat_lnav_ephemeris_host"))
+    eph[]
+end
+# the inverse: the 190 payload bits of subframes 1, 2 and 3, [190, 3]
+function lnav_ephemeris_words(eph::Ephemeris)
+    bits = zeros(UInt8, 190, 3)
+    rc = ccall((:gat_lnav_ephemeris_words_host, libgat), Int32, (Ref{Ephemeris}, Ptr{UInt8}), Ref(eph), bits)
+    rc == GAT_OK || throw(GatError(rc, "gat_lnav_ephemeris_words_host"))
+    bits
+end
+
 end # module
