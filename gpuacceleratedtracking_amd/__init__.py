@@ -29,6 +29,7 @@ from .loop import ResidentTrackingLoop, TrackingLoop  # noqa: F401
 from .monitor import (TrackMonitor, monitor_accumulators, monitor_accumulators_host, monitor_plan, overlay_for)  # noqa: F401
 from .navigation import (NavResult, cnav_fec_encode, cnav_message, crc24q, decode_navigation, decode_navigation_host,  # noqa: F401
                          lnav_subframe, nav_format_for, nav_plan)
+from .observables import Observables, obs_config, observables, observables_host, observables_plan  # noqa: F401
 from .positioning import (Ephemeris, PositionFix, lnav_ephemerides, lnav_ephemeris, lnav_ephemeris_payloads, position_fix,  # noqa: F401
                           position_fix_host, position_plan)
 from .sharding import DeviceGroup, ShardPlan, gather_outputs, shard_channels, shard_params  # noqa: F401

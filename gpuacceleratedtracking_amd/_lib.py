@@ -44,6 +44,9 @@ GAT_NAV_LNAV, GAT_NAV_CNAV, GAT_NAV_FRAME_BITS, GAT_NAV_TAIL_BITS = 0, 1, 300, 3
 GAT_MAX_FIX_CHANNELS, GAT_MAX_FIX_EPOCHS = 64, 1 << 24
 GAT_FIX_FEW_SATS, GAT_FIX_SINGULAR, GAT_FIX_NONFINITE, GAT_FIX_NOT_CONVERGED, GAT_FIX_MASK_STARVED, GAT_FIX_MASKED = 1, 2, 4, 8, 16, 32
 GAT_EPH_OK, GAT_EPH_MISSING, GAT_EPH_IODE = 0, 1, 2
+# observables (the status bits of gat_obs_channel and the reception modes of gat_obs_config)
+GAT_OBS_BAD_RECORD, GAT_OBS_NO_BIT_SYNC, GAT_OBS_NO_FRAME_SYNC, GAT_OBS_FRAME_OUTSIDE, GAT_OBS_NO_TOW, GAT_OBS_EDGE_AMBIGUOUS = 1, 2, 4, 8, 16, 32
+GAT_OBS_RX_GIVEN, GAT_OBS_RX_FROM_TX = 0, 1
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -84,6 +87,8 @@ EXPORTS = [
     "gat_nav_decode", "gat_nav_decode_host", "gat_nav_decode_plan",
     # position fix: LNAV ephemeris, satellite states and the batched least-squares solver
     "gat_position_fix", "gat_position_fix_host", "gat_position_fix_plan", "gat_lnav_ephemeris_host", "gat_lnav_ephemeris_words_host",
+    # observables: the loop's parameter history, transmit times and carrier phase from it
+    "gat_tracking_run_history", "gat_observables", "gat_observables_host", "gat_observables_plan",
 ]
 
 
@@ -293,6 +298,30 @@ FIX_DTYPE = np.dtype([("status", "<i4"), ("num_valid", "<i4"), ("num_used", "<i4
 assert C.sizeof(FixConfig) == 56 and C.sizeof(FixPlan) == 32 and EPHEMERIS_DTYPE.itemsize == 200 and FIX_DTYPE.itemsize == 80
 
 
+class ObsConfig(C.Structure):
+    """gat_obs_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_int32), ("code_length", C.c_int32), ("symbol_blocks", C.c_int32),
+                ("code_freq_nominal_hz", C.c_double), ("block_seconds", C.c_double), ("sampling_freq_hz", C.c_double), ("if_hz", C.c_double),
+                ("block_samples", C.c_int32), ("max_frames", C.c_int32), ("min_tow_steps", C.c_int32), ("epoch_first", C.c_int32),
+                ("epoch_stride", C.c_int32), ("rx_mode", C.c_int32), ("rx0_ms", C.c_int32), ("travel_ms", C.c_int32),
+                ("edge_margin", C.c_double), ("rx0_frac", C.c_double)]
+
+
+class ObsPlan(C.Structure):
+    """gat_obs_plan (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("chunk_blocks", C.c_int32), ("num_chunks", C.c_int32), ("channel_group", C.c_int32),
+                ("num_groups", C.c_int32), ("lanes", C.c_int32), ("rows", C.c_int32), ("run_blocks", C.c_int32), ("threads", C.c_int32),
+                ("lds_bytes", C.c_int32), ("chunk_workgroups", C.c_int32), ("channel_workgroups", C.c_int32), ("scratch_bytes", C.c_int64)]
+
+
+# gat_obs_channel (include/gat.h)
+OBS_CHANNEL_DTYPE = np.dtype([("status", "<i4"), ("frame_block", "<i4"), ("tow_frame", "<i4"), ("frame0_ms", "<i4"), ("edge_period", "<i8"),
+                              ("edge_fraction", "<f8")])
+assert C.sizeof(ObsConfig) == 96 and C.sizeof(ObsPlan) == 56 and OBS_CHANNEL_DTYPE.itemsize == 32
+
+
 _LIB = None
 
 
@@ -417,6 +446,11 @@ def load(build_if_missing: bool = True):
         "gat_position_fix_plan": (i32, [i32, i32, C.POINTER(FixConfig), C.POINTER(FixPlan)]),
         "gat_lnav_ephemeris_host": (i32, [vp, i32, vp]),
         "gat_lnav_ephemeris_words_host": (i32, [vp, vp]),
+        "gat_tracking_run_history": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,
+                                           C.POINTER(LoopConfig), vp, vp, vp, vp, i64, C.c_uint32, vp, vp]),
+        "gat_observables": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(ObsConfig)] + [vp] * 9),
+        "gat_observables_host": (i32, [vp, vp, vp, vp, i32, i32, i32, C.POINTER(ObsConfig)] + [vp] * 9),
+        "gat_observables_plan": (i32, [i32, i32, i32, C.POINTER(ObsConfig), C.POINTER(ObsPlan)]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

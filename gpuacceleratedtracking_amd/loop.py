@@ -139,6 +139,43 @@ class TrackingLoop:
             self.out_im.copy_(acc_im[-1:])
         return acc_re, acc_im
 
+    def run_history(self, re: torch.Tensor, im: torch.Tensor | None, num_blocks: int, start: int = 0, out: tuple | None = None):
+        """``run`` that keeps the parameters every block was correlated with (``gat_tracking_run_history``): returns ``(acc_re,
+        acc_im, history)``, the accumulators of every block [num_blocks, K, L, M] (into ``out`` = (re, im) if given) and a uint8
+        device tensor ``[num_blocks + 1, K, 40]`` of ``gat_channel_params`` records -- record 0 the parameters at entry, record b + 1
+        what block b's update wrote.  The same launches and the same bits as ``run``; afterwards the loop's current parameters
+        are record ``num_blocks``.  What ``observables`` reads."""
+        nb = int(num_blocks)
+        self.ctx.set_codes(self.system.codes)  # the context may have been bound to another system's table meanwhile
+        _, desc = input_desc((re, im), self.N, nb, start)
+        if out is not None:
+            acc_re, acc_im = out
+        else:
+            acc_re = torch.empty((nb, self.K, self.L, self.M), dtype=torch.float32, device=self.ctx.device)
+            acc_im = torch.empty_like(acc_re)
+        cur = self._params[self._cur]
+        history = torch.empty((nb + 1, self.K, 40), dtype=torch.uint8, device=self.ctx.device)
+        history[0].view(-1).copy_(cur.view(torch.uint8).view(-1))
+        rc = self.ctx.lib.gat_tracking_run_history(
+            self.ctx._h, C.byref(desc), nb, self.K, self.L, self.shifts.ctypes.data_as(C.POINTER(C.c_int32)), self.fs, C.byref(self.config),
+            C.c_void_p(self._state.data_ptr()), C.c_void_p(history.data_ptr()), C.c_void_p(acc_re.data_ptr()), C.c_void_p(acc_im.data_ptr()),
+            self.K * self.L * self.M, 0, *self._weight_ptrs())
+        self.ctx.check(rc, "gat_tracking_run_history")
+        cur.view(torch.uint8).view(-1).copy_(history[nb].view(-1))
+        self.blocks_done += nb
+        self.out_re.copy_(acc_re[-1:])
+        self.out_im.copy_(acc_im[-1:])
+        return acc_re, acc_im, history
+
+    def observables(self, history: torch.Tensor, mon, nav, **kw):
+        """``observables.observables`` over a history of this loop (``run_history``), its monitor and its decoder's result, with the
+        loop's block length, sampling rate, code, intermediate frequency and message format filled in; every keyword of that
+        function may be given."""
+        from .observables import observables
+
+        kw.setdefault("ctx", self.ctx)
+        return observables(history, mon, nav, loop=self, **kw)
+
     def monitor(self, acc_re: torch.Tensor, acc_im: torch.Tensor, **kw):
         """``monitor.monitor_accumulators`` over accumulators of this loop (``run(keep=True)``) with the loop's prompt tap, block
         length, beamformer weights and its system's overlay filled in; every keyword of that function may be given."""

@@ -1418,6 +1418,130 @@ GAT_API int32_t gat_lnav_ephemeris_host(const gat_nav_frame *frames, int32_t num
  * 3, every field rint(value / scale) kept to its width; L2 codes, reserved bits and AODO are 0.  valid is not read. */
 GAT_API int32_t gat_lnav_ephemeris_words_host(const gat_ephemeris *eph, uint8_t *payload_bits);
 
+/* ---- observables: times of transmission and carrier phase from the loop's parameter history ------------------------------
+ * What lies between the loop and the fix.  gat_tracking_run_history is gat_tracking_run_weighted (w_re = w_im = NULL: the
+ * unweighted run) with the ping-pong pair replaced by one array history_dev [num_blocks + 1][K]: the caller fills record 0,
+ * block b is correlated with record b and its update writes record b + 1 -- the same two launches a block with cur = history
+ * + b K and next = history + (b + 1) K, so accumulators, loop state and record num_blocks have the bits gat_tracking_run
+ * leaves from the same start.  GAT_FLAG_GRAPH is refused (GAT_ERR_ARG), as is one weight pointer without the other. */
+GAT_API int32_t gat_tracking_run_history(gat_ctx *ctx, const gat_signal_desc *sig, int32_t num_blocks, int32_t num_channels,
+                                         int32_t num_taps, const int32_t *shifts_host, double sampling_freq_hz,
+                                         const gat_loop_config *config_host, gat_loop_state *state_dev,
+                                         gat_channel_params *history_dev, float *acc_re_dev, float *acc_im_dev,
+                                         int64_t acc_block_stride, uint32_t flags, const double *w_re_dev, const double *w_im_dev);
+/* gat_observables reads that history [B + 1][K] (tau = code_phase_chips, phi = carrier_phase_cycles, fcode, fcarr of record
+ * b: the replica at the start of block b), the monitor's channel records [K] and the decoder's channel records [K] and frames
+ * [K][max_frames] where those calls wrote them (they covered the same B blocks: monitor block = history index) and writes,
+ * for E measurement epochs at the history indices b_e = epoch_first + e * epoch_stride <= B, what gat_position_fix takes.
+ * Everything that accumulates is an integer, so any order of summation gives the same value; the only floating-point results
+ * are single quotients, evaluated as written without contraction (csrc/gat_obs.h, shared by the kernels and the host twin:
+ * the same bits).  Lc = code_length, fc = code_freq_nominal_hz (Lc * 1000 == fc: a code period is 1 ms), T = block_seconds,
+ * N = block_samples, fs = sampling_freq_hz, Pd = symbol_blocks, P = 1 (LNAV) or 2 (CNAV) symbols a bit.
+ *   wraps    block i < B: w_i = rint(q), q = ((tau_i + fcode_i T) - tau_{i+1}) / Lc, the whole code periods of block i; c_i =
+ *            rint(d), d = (phi_i + fcarr_i T) - phi_{i+1}, its whole carrier cycles (either sign): read off the history, not
+ *            recomputed from the loop's floor.  n_b = sum_{i<b} w_i, W_b = sum_{i<b} c_i (int64).  A q or d further than 1e-6
+ *            from its integer or beyond 2^31, a record with a value that is not finite, or a tau outside [0, Lc) at an epoch or
+ *            at the frame block: GAT_OBS_BAD_RECORD, no measurement of that channel in any epoch; other channels are untouched.
+ *   frame    g = start + (symbol_phase + P * frame_offset) * Pd, the history block at which frame 0 of the decoder begins.
+ *            start < 0: GAT_OBS_NO_BIT_SYNC; frame_offset < 0: GAT_OBS_NO_FRAME_SYNC; g > B: GAT_OBS_FRAME_OUTSIDE.
+ *   tow      f* = the first written frame (f < min(num_frames, max_frames)) with every status bit of its format set; none, or
+ *            tow_steps < min_tow_steps: GAT_OBS_NO_TOW.  The TOW count names the start of the NEXT 6 s frame: frame 0 begins
+ *            at frame0_ms = 6000 * ((tow[f*] - 1 - f*) mod 100800), the mod mathematical.
+ *   edge     the bit edge is the code-period boundary nearest the start of block g: x = tau_g / Lc, p* = n_g + rint(x);
+ *            |x - 0.5| < edge_margin: GAT_OBS_EDGE_AMBIGUOUS -- the measurement stands, maybe a period off.
+ *   tx       at the start of block b = b_e: tx_ms = (frame0_ms + (n_b - p*)) mod 604800000 (mathematical), tx_frac = tau_b /
+ *            fc, a quotient >= 1e-3 written as the largest double below 1e-3.  Any status bit but EDGE_AMBIGUOUS: no
+ *            measurement, tx_ms = -1 and tx_frac = 0 in every epoch.
+ *   carrier  carrier_cycles = W_b, carrier_frac = phi_b, doppler_hz = fcarr_b - if_hz, code_rate_hz = fcode_b: the phase
+ *            includes the IF (the caller removes if_hz t).  Written without a measurement too, zeros for a BAD_RECORD channel.
+ *   rx       an anchor (ms, frac) at block a.  GAT_OBS_RX_GIVEN: (rx0_ms, rx0_frac) at a = 0.  GAT_OBS_RX_FROM_TX (the cold
+ *            start): a = b_0 and the anchor is the latest transmission of epoch 0 among the measured channels plus travel_ms,
+ *            with that channel's fraction -- latest by the integer ms difference to the first measured channel wrapped into
+ *            [-302400000, 302400000), then by the fraction, the lowest channel on a tie; no measured channel: rx_ms = -1 and
+ *            rx_frac = 0 in every epoch.  Epoch e in integers: S = (b_e - a) N, ms_add = S 1000 / fs, rem = S 1000 mod fs,
+ *            frac = anchor_frac + (double) rem / (fs * 1000.0), one carry of 1e-3 into ms_add where frac >= 1e-3, rx_ms =
+ *            (anchor_ms + ms_add) mod 604800000.
+ * Outputs, every one optional (null: not written; at least one is given): tx_ms int32 and tx_frac double [E][K]; rx_ms int32
+ * and rx_frac double [E]; carrier_cycles int64, carrier_frac, doppler_hz, code_rate_hz double [E][K]; channels [K], fields
+ * zero where undefined (frame_block with both syncs; tow_frame and frame0_ms with a TOW; the edge with g <= B in a channel
+ * that is not BAD_RECORD).  The four times go into gat_position_fix as they are.
+ * The call enqueues on the context's stream, does not synchronise and allocates nothing but the context's scratch.  The
+ * history is cut into chunks of consecutive blocks -- one contiguous span for all channels -- and the channels into groups
+ * (gat_observables_plan, csrc/gat_obs_plan.h): a workgroup a (chunk, group) sums its wraps, a wave a channel scans the chunk
+ * totals and resolves the channel's record, one wave picks the anchor, a workgroup a (chunk, group) walks its span again
+ * and writes the epochs in it.  No atomics, no floating-point sum: the same bits every call and from the twin.
+ * Refusals, all before any launch (the host twin: before any write): GAT_ERR_ARG for a null history, monitor or decoder
+ * pointer or config, a wrong struct_size, an unknown format or rx_mode, B, K, E, symbol_blocks, max_frames or epoch_stride
+ * < 1, epoch_first < 0, an epoch beyond record B, edge_margin outside [0, 0.5], block_seconds not > 0, block_samples < 1 and
+ * a call with every output null; GAT_ERR_RANGE for travel_ms outside 0 .. 1000, a given rx0_ms outside 0 .. 604799999 or
+ * rx0_frac outside [0, 1e-3), K above GAT_MAX_MONITOR_CHANNELS, B above GAT_MAX_MONITOR_BLOCKS, code_length < 1 or
+ * code_length * 1000 != code_freq_nominal_hz, an fs that is not a whole number in 1 .. 2^40, B * N * 1000 >= 2^62, an if_hz
+ * that is not finite and a call whose scratch would exceed 1 GiB. */
+#define GAT_OBS_BAD_RECORD 1
+#define GAT_OBS_NO_BIT_SYNC 2
+#define GAT_OBS_NO_FRAME_SYNC 4
+#define GAT_OBS_FRAME_OUTSIDE 8
+#define GAT_OBS_NO_TOW 16
+#define GAT_OBS_EDGE_AMBIGUOUS 32
+#define GAT_OBS_RX_GIVEN 0
+#define GAT_OBS_RX_FROM_TX 1
+typedef struct gat_obs_config {
+    uint32_t struct_size;        /* sizeof(gat_obs_config) */
+    int32_t format;              /* GAT_NAV_LNAV or GAT_NAV_CNAV */
+    int32_t code_length;         /* Lc */
+    int32_t symbol_blocks;       /* Pd, the monitor's */
+    double code_freq_nominal_hz; /* fc = Lc * 1000 */
+    double block_seconds;        /* T: the loop configuration's value, bit for bit */
+    double sampling_freq_hz;     /* fs, a whole number */
+    double if_hz;
+    int32_t block_samples;       /* N */
+    int32_t max_frames;          /* rows of the decoder's frames per channel */
+    int32_t min_tow_steps;       /* the decoder's tow_steps must reach this (0: any) */
+    int32_t epoch_first;         /* b_0 >= 0 */
+    int32_t epoch_stride;        /* >= 1 */
+    int32_t rx_mode;             /* GAT_OBS_RX_GIVEN or GAT_OBS_RX_FROM_TX */
+    int32_t rx0_ms;              /* given mode: reception at block 0 */
+    int32_t travel_ms;           /* from-tx mode: 0 .. 1000 (68) */
+    double edge_margin;          /* 0 .. 0.5 (0.1) */
+    double rx0_frac;             /* given mode: [0, 1e-3) */
+} gat_obs_config;
+typedef struct gat_obs_channel {
+    int32_t status;       /* GAT_OBS_* bits; 0 or EDGE_AMBIGUOUS alone: measured */
+    int32_t frame_block;  /* g */
+    int32_t tow_frame;    /* f* */
+    int32_t frame0_ms;
+    int64_t edge_period;  /* p* */
+    double edge_fraction; /* tau_g / Lc */
+} gat_obs_channel;
+GAT_API int32_t gat_observables(gat_ctx *ctx, const gat_channel_params *history_dev, const gat_monitor_channel *mon_channels_dev,
+                                const gat_nav_channel *nav_channels_dev, const gat_nav_frame *nav_frames_dev, int32_t num_blocks,
+                                int32_t num_channels, int32_t num_epochs, const gat_obs_config *config, int32_t *tx_ms,
+                                double *tx_frac, int32_t *rx_ms, double *rx_frac, int64_t *carrier_cycles, double *carrier_frac,
+                                double *doppler_hz, double *code_rate_hz, gat_obs_channel *channels);
+/* The same rule in plain loops on the HOST (csrc/gat_obs.h, shared with the device): every pointer is host memory; needs
+ * no context and no device.  The bit-exact reference of the device call, with the same refusals. */
+GAT_API int32_t gat_observables_host(const gat_channel_params *history_host, const gat_monitor_channel *mon_channels_host,
+                                     const gat_nav_channel *nav_channels_host, const gat_nav_frame *nav_frames_host,
+                                     int32_t num_blocks, int32_t num_channels, int32_t num_epochs, const gat_obs_config *config,
+                                     int32_t *tx_ms, double *tx_frac, int32_t *rx_ms, double *rx_frac, int64_t *carrier_cycles,
+                                     double *carrier_frac, double *doppler_hz, double *code_rate_hz, gat_obs_channel *channels);
+/* What gat_observables would do with a call (csrc/gat_obs_plan.h; no context, no device, nothing is read but config).  A chunk
+ * is chunk_blocks consecutive blocks (the last one takes what is left and record B); a channel group is channel_group
+ * consecutive channels; a workgroup of `threads` is rows x lanes, lane l < lanes holds channel l of its group and row r walks
+ * run_blocks consecutive blocks of the chunk.  The refusals are the call's, but for the pointers. */
+typedef struct gat_obs_plan {
+    uint32_t struct_size; /* sizeof(gat_obs_plan), set by the caller */
+    int32_t chunk_blocks, num_chunks;
+    int32_t channel_group, num_groups;
+    int32_t lanes, rows, run_blocks;
+    int32_t threads, lds_bytes;
+    int32_t chunk_workgroups;   /* num_chunks * num_groups: the sum kernel and the epoch kernel each */
+    int32_t channel_workgroups; /* four channels (waves) a workgroup */
+    int64_t scratch_bytes;
+} gat_obs_plan;
+GAT_API int32_t gat_observables_plan(int32_t num_blocks, int32_t num_channels, int32_t num_epochs, const gat_obs_config *config,
+                                     gat_obs_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1407,4 +1407,123 @@ function lnav_ephemeris_words(eph::Ephemeris)
     bits
 end
 
+# ---- observables: the loop's parameter history, transmit times and carrier phase from it (include/gat.h) ----
+const GAT_OBS_BAD_RECORD = Int32(1)
+const GAT_OBS_NO_BIT_SYNC = Int32(2)
+const GAT_OBS_NO_FRAME_SYNC = Int32(4)
+const GAT_OBS_FRAME_OUTSIDE = Int32(8)
+const GAT_OBS_NO_TOW = Int32(16)
+const GAT_OBS_EDGE_AMBIGUOUS = Int32(32)
+const GAT_OBS_RX_GIVEN = Int32(0)
+const GAT_OBS_RX_FROM_TX = Int32(1)
+# tracking_run_weighted! with the ping-pong pair replaced by history_dev [K x (num_blocks + 1)] records: the caller fills record
+# 1 (Julia's order), block b is correlated with record b and its update writes the next one.  C_NULL weight planes: the unweighted run.
+function tracking_run_history!(ctx::Context, desc::SignalDesc, num_blocks::Integer, K::Integer, shifts::Vector{Int32},
+                               sampling_frequency_hz::Float64, cfg::LoopConfig, state_dev::Ptr{Cvoid}, history_dev::Ptr{Cvoid},
+                               acc_re::Ptr{Cfloat}, acc_im::Ptr{Cfloat}, acc_block_stride::Integer = 0;
+                               w_re::Ptr{Float64} = Ptr{Float64}(C_NULL), w_im::Ptr{Float64} = Ptr{Float64}(C_NULL), flags::UInt32 = UInt32(0))
+    check(ctx, ccall((:gat_tracking_run_history, libgat), Int32,
+                     (Ptr{Cvoid}, Ref{SignalDesc}, Int32, Int32, Int32, Ptr{Int32}, Float64, Ref{LoopConfig}, Ptr{Cvoid}, Ptr{Cvoid},
+                      Ptr{Cfloat}, Ptr{Cfloat}, Int64, UInt32, Ptr{Float64}, Ptr{Float64}),
+                     ctx.handle, Ref(desc), Int32(num_blocks), Int32(K), Int32(length(shifts)), shifts, sampling_frequency_hz,
+                     Ref(cfg), state_dev, history_dev, acc_re, acc_im, Int64(acc_block_stride), flags, w_re, w_im))
+end
+# struct gat_obs_config (96 bytes)
+struct ObsConfig
+    struct_size::UInt32
+    format::Int32                 # GAT_NAV_LNAV or GAT_NAV_CNAV
+    code_length::Int32
+    symbol_blocks::Int32          # the monitor's
+    code_freq_nominal_hz::Float64 # code_length * 1000
+    block_seconds::Float64        # the loop configuration's value
+    sampling_freq_hz::Float64     # a whole number
+    if_hz::Float64
+    block_samples::Int32
+    max_frames::Int32             # rows of the decoder's frames per channel
+    min_tow_steps::Int32
+    epoch_first::Int32            # 0-based history index of epoch 0
+    epoch_stride::Int32
+    rx_mode::Int32                # GAT_OBS_RX_GIVEN or GAT_OBS_RX_FROM_TX
+    rx0_ms::Int32
+    travel_ms::Int32
+    edge_margin::Float64
+    rx0_frac::Float64
+end
+ObsConfig(format::Integer, code_length::Integer, symbol_blocks::Integer, block_seconds::Real, block_samples::Integer, sampling_freq_hz::Real,
+          max_frames::Integer; if_hz::Real = 0.0, min_tow_steps::Integer = 0, epoch_first::Integer = 0, epoch_stride::Integer = 1,
+          rx_mode::Integer = GAT_OBS_RX_FROM_TX, rx0_ms::Integer = 0, rx0_frac::Real = 0.0, travel_ms::Integer = 68, edge_margin::Real = 0.1) =
+    ObsConfig(UInt32(sizeof(ObsConfig)), Int32(format), Int32(code_length), Int32(symbol_blocks), Float64(code_length) * 1000.0,
+              Float64(block_seconds), Float64(sampling_freq_hz), Float64(if_hz), Int32(block_samples), Int32(max_frames), Int32(min_tow_steps),
+              Int32(epoch_first), Int32(epoch_stride), Int32(rx_mode), Int32(rx0_ms), Int32(travel_ms), Float64(edge_margin), Float64(rx0_frac))
+# struct gat_obs_channel (32 bytes)
+struct ObsChannel
+    status::Int32
+    frame_block::Int32
+    tow_frame::Int32
+    frame0_ms::Int32
+    edge_period::Int64
+    edge_fraction::Float64
+end
+struct ObsPlan
+    struct_size::UInt32
+    chunk_blocks::Int32
+    num_chunks::Int32
+    channel_group::Int32
+    num_groups::Int32
+    lanes::Int32
+    rows::Int32
+    run_blocks::Int32
+    threads::Int32
+    lds_bytes::Int32
+    chunk_workgroups::Int32
+    channel_workgroups::Int32
+    scratch_bytes::Int64
+end
+# Every pointer is a device pointer; every output may be C_NULL but one.  In Julia's order history is [K x (B + 1)], frames
+# [max_frames x K], tx_ms .. code_rate_hz [K x E], rx_ms, rx_frac [E], channels [K].  Enqueues only.
+function observables!(ctx::Context, history::Ptr{ChannelParams}, mon_channels::Ptr{MonitorChannel}, nav_channels::Ptr{NavChannel},
+                      nav_frames::Ptr{NavFrame}, num_blocks::Integer, num_channels::Integer, num_epochs::Integer, cfg::ObsConfig;
+                      tx_ms::Ptr{Int32} = Ptr{Int32}(C_NULL), tx_frac::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                      rx_ms::Ptr{Int32} = Ptr{Int32}(C_NULL), rx_frac::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                      carrier_cycles::Ptr{Int64} = Ptr{Int64}(C_NULL), carrier_frac::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                      doppler_hz::Ptr{Float64} = Ptr{Float64}(C_NULL), code_rate_hz::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                      channels::Ptr{ObsChannel} = Ptr{ObsChannel}(C_NULL))
+    check(ctx, ccall((:gat_observables, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{ChannelParams}, Ptr{MonitorChannel}, Ptr{NavChannel}, Ptr{NavFrame}, Int32, Int32, Int32, Ref{ObsConfig},
+                      Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{ObsChannel}),
+                     ctx.handle, history, mon_channels, nav_channels, nav_frames, Int32(num_blocks), Int32(num_channels), Int32(num_epochs),
+                     Ref(cfg), tx_ms, tx_frac, rx_ms, rx_frac, carrier_cycles, carrier_frac, doppler_hz, code_rate_hz, channels))
+end
+# the same rule on host memory, the bit-exact reference of the device call: history [K, B + 1], frames [max_frames, K]; returns
+# (tx_ms, tx_frac, rx_ms, rx_frac, carrier_cycles, carrier_frac, doppler_hz, code_rate_hz, channels)
+function observables_host(history::Matrix{ChannelParams}, mon_channels::Vector{MonitorChannel}, nav_channels::Vector{NavChannel},
+                          nav_frames::Matrix{NavFrame}, num_epochs::Integer, cfg::ObsConfig)
+    K, B1 = size(history)
+    E = Int(num_epochs)
+    tx_ms = zeros(Int32, K, E)
+    tx_frac = zeros(Float64, K, E)
+    rx_ms = zeros(Int32, E)
+    rx_frac = zeros(Float64, E)
+    cycles = zeros(Int64, K, E)
+    carrier_frac = zeros(Float64, K, E)
+    doppler = zeros(Float64, K, E)
+    code_rate = zeros(Float64, K, E)
+    channels = Vector{ObsChannel}(undef, K)
+    rc = ccall((:gat_observables_host, libgat), Int32,
+               (Ptr{ChannelParams}, Ptr{MonitorChannel}, Ptr{NavChannel}, Ptr{NavFrame}, Int32, Int32, Int32, Ref{ObsConfig},
+                Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{ObsChannel}),
+               history, mon_channels, nav_channels, nav_frames, Int32(B1 - 1), Int32(K), Int32(E), Ref(cfg), tx_ms, tx_frac, rx_ms, rx_frac,
+               cycles, carrier_frac, doppler, code_rate, channels)
+    rc == GAT_OK || throw(GatError(rc, "gat_observables_host"))
+    tx_ms, tx_frac, rx_ms, rx_frac, cycles, carrier_frac, doppler, code_rate, channels
+end
+# what observables! would do with a call, without a device
+function observables_plan(num_blocks::Integer, num_channels::Integer, num_epochs::Integer, cfg::ObsConfig)
+    plan = Ref(ObsPlan(UInt32(sizeof(ObsPlan)), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_observables_plan, libgat), Int32, (Int32, Int32, Int32, Ref{ObsConfig}, Ref{ObsPlan}), Int32(num_blocks),
+               Int32(num_channels), Int32(num_epochs), Ref(cfg), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_observables_plan"))
+    plan[]
+end
+
 end # module
