@@ -31,7 +31,8 @@ from .navigation import (NavResult, cnav_fec_encode, cnav_message, crc24q, decod
                          lnav_subframe, nav_format_for, nav_plan)
 from .observables import Observables, obs_config, observables, observables_host, observables_plan  # noqa: F401
 from .positioning import (Ephemeris, PositionFix, lnav_ephemerides, lnav_ephemeris, lnav_ephemeris_payloads, position_fix,  # noqa: F401
-                          position_fix_host, position_plan)
+                          position_fix_host, position_fix_raim, position_fix_raim_host, position_plan, raim_config, raim_plan,
+                          raim_thresholds)
 from .sharding import DeviceGroup, ShardPlan, gather_outputs, shard_channels, shard_params  # noqa: F401
 from .spectrum import (auto_notch, find_tones, sample_spectrum, sample_spectrum_host, spectrum_stream)  # noqa: F401
 from .spacetime import (spacetime_covariance, spacetime_delay, spacetime_filter, spacetime_filter_host, spacetime_steering,  # noqa: F401

@@ -47,6 +47,9 @@ GAT_EPH_OK, GAT_EPH_MISSING, GAT_EPH_IODE = 0, 1, 2
 # observables (the status bits of gat_obs_channel and the reception modes of gat_obs_config)
 GAT_OBS_BAD_RECORD, GAT_OBS_NO_BIT_SYNC, GAT_OBS_NO_FRAME_SYNC, GAT_OBS_FRAME_OUTSIDE, GAT_OBS_NO_TOW, GAT_OBS_EDGE_AMBIGUOUS = 1, 2, 4, 8, 16, 32
 GAT_OBS_RX_GIVEN, GAT_OBS_RX_FROM_TX = 0, 1
+# fix integrity (the status bits of gat_fix_integrity, the bit gat_position_fix_raim adds to gat_fix.status, the rounds' limit)
+GAT_RAIM_NOT_CHECKED, GAT_RAIM_NO_REDUNDANCY, GAT_RAIM_DETECTED, GAT_RAIM_EXCLUDED, GAT_RAIM_UNRESOLVED = 1, 2, 4, 8, 16
+GAT_FIX_EXCLUDED, GAT_RAIM_MAX_EXCLUDE = 64, 4
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -89,6 +92,8 @@ EXPORTS = [
     "gat_position_fix", "gat_position_fix_host", "gat_position_fix_plan", "gat_lnav_ephemeris_host", "gat_lnav_ephemeris_words_host",
     # observables: the loop's parameter history, transmit times and carrier phase from it
     "gat_tracking_run_history", "gat_observables", "gat_observables_host", "gat_observables_plan",
+    # fix integrity: the residual test and fault exclusion on top of the position fix
+    "gat_position_fix_raim", "gat_position_fix_raim_host", "gat_position_fix_raim_plan",
 ]
 
 
@@ -322,6 +327,19 @@ OBS_CHANNEL_DTYPE = np.dtype([("status", "<i4"), ("frame_block", "<i4"), ("tow_f
 assert C.sizeof(ObsConfig) == 96 and C.sizeof(ObsPlan) == 56 and OBS_CHANNEL_DTYPE.itemsize == 32
 
 
+class RaimConfig(C.Structure):
+    """gat_raim_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("max_exclude", C.c_int32), ("trial_iter", C.c_int32), ("flags", C.c_uint32),
+                ("threshold", C.c_double * (GAT_MAX_FIX_CHANNELS - 3))]
+
+
+# gat_fix_integrity (include/gat.h)
+INTEGRITY_DTYPE = np.dtype([("status", "<i4"), ("dof", "<i4"), ("num_excluded", "<i4"), ("excluded", "<i4", (4,)), ("reserved", "<i4"),
+                            ("stat0", "<f8"), ("threshold0", "<f8"), ("stat", "<f8"), ("threshold", "<f8")])
+assert C.sizeof(RaimConfig) == 504 and INTEGRITY_DTYPE.itemsize == 64
+
+
 _LIB = None
 
 
@@ -451,6 +469,9 @@ def load(build_if_missing: bool = True):
         "gat_observables": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(ObsConfig)] + [vp] * 9),
         "gat_observables_host": (i32, [vp, vp, vp, vp, i32, i32, i32, C.POINTER(ObsConfig)] + [vp] * 9),
         "gat_observables_plan": (i32, [i32, i32, i32, C.POINTER(ObsConfig), C.POINTER(ObsPlan)]),
+        "gat_position_fix_raim": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(FixConfig), C.POINTER(RaimConfig)] + [vp] * 7),
+        "gat_position_fix_raim_host": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(FixConfig), C.POINTER(RaimConfig)] + [vp] * 7),
+        "gat_position_fix_raim_plan": (i32, [i32, i32, C.POINTER(FixConfig), C.POINTER(RaimConfig), C.POINTER(FixPlan)]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

@@ -73,44 +73,55 @@ inline void fix_report(const FixPlan &p, gat_fix_plan *out)
 }
 
 // ---- the host twin ----------------------------------------------------------------------------------------------------------------
-// One epoch in plain loops over its K channels: what a wave of the kernel does, a channel where the kernel has a lane.
-inline void fix_host_epoch(const FixPlan &p, const gat_ephemeris *eph, const int32_t *tx_ms, const double *tx_frac, int32_t rx_ms, double rx_frac,
-                           const double *w, gat_fix *fix, double *sat, double *resid, double *sin_el, uint8_t *used_out)
-{
-    const int K = p.K;
+// One epoch in plain loops over its K channels: what a wave of the kernel does, a channel where the kernel has a lane.  The state
+// is a struct so that the integrity twin (gat_raim_plan.h) goes on from where the fix ends.
+struct FixHostEpoch {
+    int K, max_iter;
+    double tol_m, mask_sin;
     FixSat s[GAT_MAX_FIX_CHANNELS];
     FixRow row[GAT_MAX_FIX_CHANNELS];
     double wk[GAT_MAX_FIX_CHANNELS], tau[GAT_MAX_FIX_CHANNELS], sel[GAT_MAX_FIX_CHANNELS];
     bool used[GAT_MAX_FIX_CHANNELS];
-    int num_valid = 0, num_used = 0;
-    for (int k = 0; k < K; ++k) {
-        s[k] = fix_sat(eph[k], tx_ms[k], tx_frac[k], rx_ms, rx_frac);
-        wk[k] = w ? w[k] : 1.0;
-        used[k] = s[k].ok && fix_weight_ok(wk[k]);
-        tau[k] = kFixFirstTravel;
-        row[k] = FixRow{0.0, 0.0, 0.0, 0.0, 0.0};
-        sel[k] = 0.0;
-        num_valid += s[k].ok ? 1 : 0;
-        num_used += used[k] ? 1 : 0;
+    int num_valid, num_used;
+    double st[4];
+    int status, iterations;
+    double last_step;
+
+    void init(const FixPlan &p, const gat_ephemeris *eph, const int32_t *tx_ms, const double *tx_frac, int32_t rx_ms, double rx_frac, const double *w)
+    {
+        K = p.K, max_iter = p.max_iter, tol_m = p.tol_m, mask_sin = p.mask_sin;
+        num_valid = 0, num_used = 0;
+        for (int k = 0; k < K; ++k) {
+            s[k] = fix_sat(eph[k], tx_ms[k], tx_frac[k], rx_ms, rx_frac);
+            wk[k] = w ? w[k] : 1.0;
+            used[k] = s[k].ok && fix_weight_ok(wk[k]);
+            tau[k] = kFixFirstTravel;
+            row[k] = FixRow{0.0, 0.0, 0.0, 0.0, 0.0};
+            sel[k] = 0.0;
+            num_valid += s[k].ok ? 1 : 0;
+            num_used += used[k] ? 1 : 0;
+        }
+        st[0] = p.init_xyz[0], st[1] = p.init_xyz[1], st[2] = p.init_xyz[2], st[3] = 0.0;
+        status = 0, iterations = 0;
+        last_step = 0.0;
     }
-    double st[4] = {p.init_xyz[0], p.init_xyz[1], p.init_xyz[2], 0.0};
-    int status = 0, iterations = 0;
-    double last_step = 0.0;
     // the rows of every counting channel at the state, each with its own travel time
-    auto rows = [&]() {
+    void rows()
+    {
         for (int k = 0; k < K; ++k)
             if (s[k].ok) {
                 row[k] = fix_row(s[k], tau[k], st);
                 tau[k] = row[k].r / kFixC;
             }
-    };
+    }
     // one pass over the used set; true: converged
-    auto pass = [&]() -> bool {
+    bool pass()
+    {
         if (num_used < 4) {
             status |= GAT_FIX_FEW_SATS;
             return false;
         }
-        for (int it = 0; it < p.max_iter; ++it) {
+        for (int it = 0; it < max_iter; ++it) {
             rows();
             double sums[kFixTerms] = {};
             for (int k = 0; k < K; ++k) {
@@ -128,26 +139,30 @@ inline void fix_host_epoch(const FixPlan &p, const gat_ephemeris *eph, const int
             for (int i = 0; i < 4; ++i) st[i] += d[i];
             last_step = __builtin_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
             iterations += 1;
-            if (last_step < p.tol_m) return true;
+            if (last_step < tol_m) return true;
         }
         status |= GAT_FIX_NOT_CONVERGED;
         return false;
-    };
-    auto elevations = [&]() {
+    }
+    double elevations()
+    {
         rows();
         const double radius = fix_radius(st);
         for (int k = 0; k < K; ++k) sel[k] = s[k].ok ? fix_sin_el(row[k], st, radius) : 0.0;
         return radius;
-    };
-    const bool converged = pass();
-    if (!fix_failed(status)) {
+    }
+    // the first pass, the mask and the second pass
+    void solve()
+    {
+        const bool converged = pass();
+        if (fix_failed(status)) return;
         const double radius = elevations();
-        if (converged && p.mask_sin > -1.0 && radius >= kFixMaskRadius) {
+        if (converged && mask_sin > -1.0 && radius >= kFixMaskRadius) {
             int kept = 0;
-            for (int k = 0; k < K; ++k) kept += used[k] && sel[k] >= p.mask_sin ? 1 : 0;
+            for (int k = 0; k < K; ++k) kept += used[k] && sel[k] >= mask_sin ? 1 : 0;
             if (kept != num_used) {
                 if (kept >= 4) {
-                    for (int k = 0; k < K; ++k) used[k] = used[k] && sel[k] >= p.mask_sin;
+                    for (int k = 0; k < K; ++k) used[k] = used[k] && sel[k] >= mask_sin;
                     num_used = kept;
                     status |= GAT_FIX_MASKED;
                     pass();
@@ -157,23 +172,36 @@ inline void fix_host_epoch(const FixPlan &p, const gat_ephemeris *eph, const int
             }
         }
     }
-    const bool failed = fix_failed(status);
-    double sums[kFixTerms] = {};
-    if (!failed)
+    // the record and the channels' outputs of the state as it stands, `extra` status bits added
+    void write(int extra, gat_fix *fix, double *sat, double *resid, double *sin_el, uint8_t *used_out) const
+    {
+        const bool failed = fix_failed(status);
+        double sums[kFixTerms] = {};
+        if (!failed)
+            for (int k = 0; k < K; ++k) {
+                if (!used[k]) continue;
+                double t[kFixTerms];
+                fix_terms(row[k], 1.0, t);
+                t[10] = row[k].v * row[k].v;
+                for (int q = 0; q < 11; ++q) sums[q] += t[q];
+            }
+        *fix = fix_record(status | extra, num_valid, num_used, iterations, st, sums[10], last_step, sums);
         for (int k = 0; k < K; ++k) {
-            if (!used[k]) continue;
-            double t[kFixTerms];
-            fix_terms(row[k], 1.0, t);
-            t[10] = row[k].v * row[k].v;
-            for (int q = 0; q < 11; ++q) sums[q] += t[q];
+            if (sat) sat[4 * k] = s[k].X, sat[4 * k + 1] = s[k].Y, sat[4 * k + 2] = s[k].Z, sat[4 * k + 3] = s[k].dts;
+            if (resid) resid[k] = !failed && s[k].ok ? row[k].v : 0.0;
+            if (sin_el) sin_el[k] = !failed ? sel[k] : 0.0;
+            if (used_out) used_out[k] = (uint8_t)(!failed && used[k] ? 1 : 0);
         }
-    *fix = fix_record(status, num_valid, num_used, iterations, st, sums[10], last_step, sums);
-    for (int k = 0; k < K; ++k) {
-        if (sat) sat[4 * k] = s[k].X, sat[4 * k + 1] = s[k].Y, sat[4 * k + 2] = s[k].Z, sat[4 * k + 3] = s[k].dts;
-        if (resid) resid[k] = !failed && s[k].ok ? row[k].v : 0.0;
-        if (sin_el) sin_el[k] = !failed ? sel[k] : 0.0;
-        if (used_out) used_out[k] = (uint8_t)(!failed && used[k] ? 1 : 0);
     }
+};
+
+inline void fix_host_epoch(const FixPlan &p, const gat_ephemeris *eph, const int32_t *tx_ms, const double *tx_frac, int32_t rx_ms, double rx_frac,
+                           const double *w, gat_fix *fix, double *sat, double *resid, double *sin_el, uint8_t *used_out)
+{
+    FixHostEpoch h;
+    h.init(p, eph, tx_ms, tx_frac, rx_ms, rx_frac, w);
+    h.solve();
+    h.write(0, fix, sat, resid, sin_el, used_out);
 }
 
 // The twin's loops (gat_position_fix_host) for a planned call, every pointer host memory.

@@ -5,6 +5,8 @@
     fix = position_fix(ephs, tx_ms, tx_frac, rx_ms, rx_frac)     # gat_position_fix: enqueued, not synchronised
     fix.xyz, fix.clock_bias_s, fix.status, fix.pdop              # per epoch
     fix.sat, fix.resid, fix.sin_el, fix.used                     # per epoch and channel
+    fix = position_fix_raim(ephs, tx_ms, tx_frac, rx_ms, rx_frac, sigma_m=3.0)   # gat_position_fix_raim: the fix with integrity
+    fix.detected, fix.excluded, fix.integrity                    # per epoch: the residual test and the channels left out
 
 A time of the week is whole milliseconds (int32) and a fraction in seconds (float64): ``tx_ms``, ``tx_frac`` ``[E, K]`` of
 transmission, ``rx_ms``, ``rx_frac`` ``[E]`` of reception.  The work is libgat's HIP kernel (``position_fix``) or its host twin with
@@ -26,6 +28,10 @@ from .streams import addr, keep_alive, vp
 FEW_SATS, SINGULAR, NONFINITE = _lib.GAT_FIX_FEW_SATS, _lib.GAT_FIX_SINGULAR, _lib.GAT_FIX_NONFINITE
 NOT_CONVERGED, MASK_STARVED, MASKED = _lib.GAT_FIX_NOT_CONVERGED, _lib.GAT_FIX_MASK_STARVED, _lib.GAT_FIX_MASKED
 OUTPUTS = ("sat", "resid", "sin_el", "used")
+EXCLUDED = _lib.GAT_FIX_EXCLUDED  # in ``status``, by position_fix_raim alone
+RAIM_NOT_CHECKED, RAIM_NO_REDUNDANCY, RAIM_DETECTED = _lib.GAT_RAIM_NOT_CHECKED, _lib.GAT_RAIM_NO_REDUNDANCY, _lib.GAT_RAIM_DETECTED
+RAIM_EXCLUDED, RAIM_UNRESOLVED = _lib.GAT_RAIM_EXCLUDED, _lib.GAT_RAIM_UNRESOLVED
+RAIM_OUTPUTS = OUTPUTS + ("trial",)
 
 
 class Ephemeris:
@@ -111,7 +117,8 @@ class PositionFix:
     """The outputs of one call.  Raw: ``fixes`` (structured ``[E]``: status, num_valid, num_used, iterations, x, y, z, clock_bias_s,
     rms_residual_m, last_step_m, gdop, pdop) and, where asked for, ``sat`` ``[E, K, 4]`` (ECEF at transmission and the clock
     correction), ``resid`` and ``sin_el`` ``[E, K]``, ``used`` uint8 ``[E, K]``.  Derived: every field of ``fixes`` ``[E]``, ``xyz``
-    ``[E, 3]`` and ``ok`` (status 0)."""
+    ``[E, 3]`` and ``ok`` (status 0).  Of ``position_fix_raim``: ``integrity`` (structured ``[E]``), ``excluded`` ``[E, 4]``,
+    ``detected`` ``[E]`` and, where asked for, ``trial`` ``[E, K]``."""
 
     def __init__(self, raw: dict, ctx: Context | None = None):
         self._raw, self._host, self._ctx = raw, None, ctx
@@ -125,6 +132,8 @@ class PositionFix:
                 a = v.cpu().numpy() if isinstance(v, torch.Tensor) else v
                 if name == "fixes":
                     a = a.view(_lib.FIX_DTYPE).reshape(-1)
+                if name == "integrity":
+                    a = a.view(_lib.INTEGRITY_DTYPE).reshape(-1)
                 host[name] = a
             self._host = host
         return self._host
@@ -132,7 +141,7 @@ class PositionFix:
     def __getattr__(self, name):
         if name in _lib.FIX_DTYPE.names:
             return self._h()["fixes"][name].copy()
-        if name in OUTPUTS:
+        if name in RAIM_OUTPUTS:
             if name not in self._raw:
                 raise AttributeError(f"{name} was not asked for (outputs=)")
             return self._h()[name]
@@ -141,29 +150,37 @@ class PositionFix:
     fixes = property(lambda self: self._h()["fixes"])
     ok = property(lambda self: self.fixes["status"] == 0)
 
+    # of position_fix_raim alone
+    @property
+    def integrity(self) -> np.ndarray:
+        """``gat_fix_integrity`` structured ``[E]``: status (``RAIM_*`` bits), dof, num_excluded, excluded ``[4]``, stat0, threshold0,
+        stat, threshold"""
+        if "integrity" not in self._raw:
+            raise AttributeError("integrity: not a result of position_fix_raim")
+        return self._h()["integrity"]
+
+    excluded = property(lambda self: self.integrity["excluded"].copy(), doc="int32 [E, 4]: the channels left out, in order; -1 where unused")
+    detected = property(lambda self: (self.integrity["status"] & RAIM_DETECTED) != 0, doc="bool [E]: the full set failed the test")
+
     @property
     def xyz(self) -> np.ndarray:
         f = self.fixes
         return np.stack([f["x"], f["y"], f["z"]], axis=1)
 
 
-def _wanted(outputs) -> tuple:
+def _wanted(outputs, known: tuple = OUTPUTS) -> tuple:
     outputs = OUTPUTS if outputs is None else tuple(outputs)
-    unknown = set(outputs) - set(OUTPUTS)
+    unknown = set(outputs) - set(known)
     if unknown:
-        raise ValueError(f"unknown outputs {sorted(unknown)}: choose from {OUTPUTS}")
+        raise ValueError(f"unknown outputs {sorted(unknown)}: choose from {known}")
     return outputs
 
 
-_SHAPES = {"sat": (4,), "resid": (), "sin_el": (), "used": ()}
+_SHAPES = {"sat": (4,), "resid": (), "sin_el": (), "used": (), "trial": ()}
 
 
-def position_fix(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, outputs=None, ctx: Context | None = None, **config) -> PositionFix:
-    """``gat_position_fix`` on the device.  ``ephs``: ``Ephemeris`` objects (uploaded) or a uint8 device tensor of ``K`` records;
-    ``tx_ms`` int32 and ``tx_frac`` float64 ``[E, K]``, ``rx_ms`` int32 and ``rx_frac`` float64 ``[E]``, ``weights`` float64 ``[E, K]``
-    or None: contiguous device tensors, passed as they are.  ``outputs``: which of "sat", "resid", "sin_el", "used" to write (None:
-    all).  ``config``: ``max_iter``, ``tol_m``, ``mask_sin``, ``init_xyz``.  Enqueues on the context's stream and returns at once."""
-    want = _wanted(outputs)
+def _device_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights):
+    """the checks of a device call: (E, K, the device, the ephemerides on it)"""
     for name, t, dt in (("tx_ms", tx_ms, torch.int32), ("tx_frac", tx_frac, torch.float64), ("rx_ms", rx_ms, torch.int32),
                         ("rx_frac", rx_frac, torch.float64), ("weights", weights, torch.float64)):
         if t is None and name == "weights":
@@ -187,12 +204,27 @@ def position_fix(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, outputs=
         if recs.shape[0] != K:
             raise ValueError(f"{recs.shape[0]} ephemerides for {K} channels")
         eph_dev = torch.from_numpy(recs.view(np.uint8).reshape(K, -1).copy()).to(dev)
-    if ctx is None:
-        ctx = get_context(dev)
-    cfg = fix_config(**config)
+    return E, K, dev, eph_dev
+
+
+def _device_outputs(want: tuple, E: int, K: int, dev) -> dict:
     raw = {"fixes": torch.empty((E, _lib.FIX_DTYPE.itemsize), dtype=torch.uint8, device=dev)}
     for name in want:
         raw[name] = torch.empty((E, K) + _SHAPES[name], dtype=torch.uint8 if name == "used" else torch.float64, device=dev)
+    return raw
+
+
+def position_fix(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, outputs=None, ctx: Context | None = None, **config) -> PositionFix:
+    """``gat_position_fix`` on the device.  ``ephs``: ``Ephemeris`` objects (uploaded) or a uint8 device tensor of ``K`` records;
+    ``tx_ms`` int32 and ``tx_frac`` float64 ``[E, K]``, ``rx_ms`` int32 and ``rx_frac`` float64 ``[E]``, ``weights`` float64 ``[E, K]``
+    or None: contiguous device tensors, passed as they are.  ``outputs``: which of "sat", "resid", "sin_el", "used" to write (None:
+    all).  ``config``: ``max_iter``, ``tol_m``, ``mask_sin``, ``init_xyz``.  Enqueues on the context's stream and returns at once."""
+    want = _wanted(outputs)
+    E, K, dev, eph_dev = _device_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+    if ctx is None:
+        ctx = get_context(dev)
+    cfg = fix_config(**config)
+    raw = _device_outputs(want, E, K, dev)
     rc = ctx.lib.gat_position_fix(ctx._h, vp(eph_dev), vp(tx_ms), vp(tx_frac), vp(rx_ms), vp(rx_frac), vp(weights), E, K, C.byref(cfg),
                                   vp(raw["fixes"]), vp(raw.get("sat")), vp(raw.get("resid")), vp(raw.get("sin_el")), vp(raw.get("used")))
     ctx.check(rc, "gat_position_fix")
@@ -202,6 +234,19 @@ def position_fix(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, outputs=
 def position_fix_host(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, outputs=None, **config) -> PositionFix:
     """``gat_position_fix_host``: the same rule and the same bits over numpy arrays; needs no device."""
     want = _wanted(outputs)
+    recs, tx_ms, tx_frac, rx_ms, rx_frac, weights, E, K = _host_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+    cfg = fix_config(**config)
+    raw = _host_outputs(want, E, K)
+    rc = _lib.load().gat_position_fix_host(addr(recs), addr(tx_ms), addr(tx_frac), addr(rx_ms), addr(rx_frac), addr(weights), E, K,
+                                           C.byref(cfg), addr(raw["fixes"]), addr(raw.get("sat")), addr(raw.get("resid")),
+                                           addr(raw.get("sin_el")), addr(raw.get("used")))
+    if rc != 0:
+        raise _lib.GatError(rc, "gat_position_fix_host")
+    return PositionFix(raw)
+
+
+def _host_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights):
+    """the checks of a host call: the arrays as the library takes them, E and K"""
     recs = ephemeris_records(ephs)
     tx_ms, rx_ms = np.ascontiguousarray(tx_ms, dtype=np.int32), np.ascontiguousarray(rx_ms, dtype=np.int32)
     tx_frac, rx_frac = np.ascontiguousarray(tx_frac, dtype=np.float64), np.ascontiguousarray(rx_frac, dtype=np.float64)
@@ -214,16 +259,14 @@ def position_fix_host(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, out
         weights = np.ascontiguousarray(weights, dtype=np.float64)
         if weights.shape != tx_ms.shape:
             raise ValueError("weights must be [E, K]")
-    cfg = fix_config(**config)
+    return recs, tx_ms, tx_frac, rx_ms, rx_frac, weights, int(E), int(K)
+
+
+def _host_outputs(want: tuple, E: int, K: int) -> dict:
     raw = {"fixes": np.zeros(E, dtype=_lib.FIX_DTYPE)}
     for name in want:
         raw[name] = np.zeros((E, K) + _SHAPES[name], dtype=np.uint8 if name == "used" else np.float64)
-    rc = _lib.load().gat_position_fix_host(addr(recs), addr(tx_ms), addr(tx_frac), addr(rx_ms), addr(rx_frac), addr(weights), E, K,
-                                           C.byref(cfg), addr(raw["fixes"]), addr(raw.get("sat")), addr(raw.get("resid")),
-                                           addr(raw.get("sin_el")), addr(raw.get("used")))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_position_fix_host")
-    return PositionFix(raw)
+    return raw
 
 
 def position_plan(num_epochs: int, num_channels: int, **config) -> dict:
@@ -234,4 +277,143 @@ def position_plan(num_epochs: int, num_channels: int, **config) -> dict:
     rc = _lib.load().gat_position_fix_plan(int(num_epochs), int(num_channels), C.byref(cfg), C.byref(plan))
     if rc != 0:
         raise _lib.GatError(rc, "gat_position_fix_plan")
+    return {n: int(getattr(plan, n)) for n, _ in _lib.FixPlan._fields_ if n not in ("struct_size", "reserved")}
+
+
+# ---- fix integrity (include/gat.h, "fix integrity") -------------------------------------------------------------------------------
+def _gamma_q(a: float, x: float) -> float:
+    """the regularised upper incomplete gamma function Q(a, x): the series of P below a + 1, Lentz's continued fraction above"""
+    import math
+
+    if x <= 0.0:
+        return 1.0
+    lead = math.exp(a * math.log(x) - x - math.lgamma(a))
+    if x < a + 1.0:
+        term = total = 1.0 / a
+        n = a
+        while abs(term) > abs(total) * 1e-17:
+            n += 1.0
+            term *= x / n
+            total += term
+        return 1.0 - lead * total
+    tiny = 1e-300
+    b = x + 1.0 - a
+    c, d = 1.0 / tiny, 1.0 / b
+    h = d
+    for i in range(1, 10000):
+        an = -i * (i - a)
+        b += 2.0
+        d = an * d + b
+        d = tiny if abs(d) < tiny else d
+        c = b + an / c
+        c = tiny if abs(c) < tiny else c
+        d = 1.0 / d
+        delta = d * c
+        h *= delta
+        if abs(delta - 1.0) < 1e-16:
+            break
+    return lead * h
+
+
+def chi2_quantile(p_fa: float, dof: int) -> float:
+    """the value a chi-square variable of ``dof`` degrees of freedom exceeds with probability ``p_fa``: Q(dof / 2, x / 2) = p_fa by
+    bisection"""
+    if not 0.0 < p_fa < 1.0 or dof < 1:
+        raise ValueError("p_fa must lie in (0, 1) and dof be positive")
+    a = 0.5 * dof
+    lo, hi = 0.0, max(1.0, a)
+    while _gamma_q(a, hi) > p_fa:
+        hi *= 2.0
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid == lo or mid == hi:
+            break
+        if _gamma_q(a, mid) > p_fa:
+            lo = mid
+        else:
+            hi = mid
+    return 2.0 * 0.5 * (lo + hi)
+
+
+def raim_thresholds(p_fa: float = 1e-3, sigma_m: float = 1.0) -> np.ndarray:
+    """float64 ``[GAT_MAX_FIX_CHANNELS - 3]``, by d = n - 4: ``sigma_m``^2 times the chi-square quantile at 1 - ``p_fa`` of d degrees of
+    freedom, d = 1 .. 60 -- what T = sum w v^2 stays under with probability 1 - p_fa when the pseudorange errors are independent
+    with standard deviation ``sigma_m`` (unit weights) or 1 / sqrt(w) (``sigma_m`` = 1).  Entry 0 is not read (0)."""
+    out = np.zeros(_lib.GAT_MAX_FIX_CHANNELS - 3, dtype=np.float64)
+    for d in range(1, out.shape[0]):
+        out[d] = float(sigma_m) ** 2 * chi2_quantile(float(p_fa), d)
+    return out
+
+
+def raim_config(thresholds, max_exclude: int = 1, trial_iter: int = 8, flags: int = 0) -> _lib.RaimConfig:
+    """``gat_raim_config`` from Python values.  Nothing is checked but the thresholds' count: the library refuses."""
+    thresholds = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    if thresholds.shape[0] != _lib.GAT_MAX_FIX_CHANNELS - 3:
+        raise ValueError(f"thresholds must be [{_lib.GAT_MAX_FIX_CHANNELS - 3}], indexed by d = n - 4")
+    cfg = _lib.RaimConfig()
+    cfg.struct_size = C.sizeof(_lib.RaimConfig)
+    cfg.max_exclude, cfg.trial_iter, cfg.flags = int(max_exclude), int(trial_iter), int(flags)
+    for d, v in enumerate(thresholds):
+        cfg.threshold[d] = float(v)
+    return cfg
+
+
+def _raim_setup(weights, thresholds, p_fa, sigma_m, max_exclude, trial_iter, raim_flags):
+    if thresholds is None:
+        if weights is None and sigma_m is None:
+            raise ValueError("without weights the thresholds need sigma_m, the standard deviation of a pseudorange in metres")
+        thresholds = raim_thresholds(p_fa, 1.0 if sigma_m is None else sigma_m)
+    return raim_config(thresholds, max_exclude, trial_iter, raim_flags)
+
+
+def position_fix_raim(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, thresholds=None, p_fa: float = 1e-3, sigma_m=None,
+                      max_exclude: int = 1, trial_iter: int = 8, raim_flags: int = 0, outputs=None, ctx: Context | None = None,
+                      **config) -> PositionFix:
+    """``gat_position_fix_raim`` on the device: ``position_fix`` with the residual test and fault exclusion.  The arguments are
+    ``position_fix``'s; ``thresholds`` float64 ``[61]`` by d = n - 4 in the units of sum w v^2 (None: ``raim_thresholds(p_fa,
+    sigma_m)`` -- with ``weights`` = 1 / sigma^2 leave ``sigma_m`` unset, without weights it is required), ``max_exclude`` rounds of
+    exclusion (0: detect only), ``trial_iter`` iterations a leave-one-out trial.  ``outputs`` may also name "trial" (None: the fix's
+    four).  The result also has ``integrity``, ``excluded``, ``detected`` and, where asked for, ``trial``."""
+    want = _wanted(outputs, RAIM_OUTPUTS)
+    E, K, dev, eph_dev = _device_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+    if ctx is None:
+        ctx = get_context(dev)
+    cfg = fix_config(**config)
+    rcfg = _raim_setup(weights, thresholds, p_fa, sigma_m, max_exclude, trial_iter, raim_flags)
+    raw = _device_outputs(want, E, K, dev)
+    raw["integrity"] = torch.empty((E, _lib.INTEGRITY_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    rc = ctx.lib.gat_position_fix_raim(ctx._h, vp(eph_dev), vp(tx_ms), vp(tx_frac), vp(rx_ms), vp(rx_frac), vp(weights), E, K, C.byref(cfg),
+                                       C.byref(rcfg), vp(raw["fixes"]), vp(raw["integrity"]), vp(raw.get("sat")), vp(raw.get("resid")),
+                                       vp(raw.get("sin_el")), vp(raw.get("used")), vp(raw.get("trial")))
+    ctx.check(rc, "gat_position_fix_raim")
+    return keep_alive(PositionFix(raw, ctx), eph_dev, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+
+
+def position_fix_raim_host(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, thresholds=None, p_fa: float = 1e-3, sigma_m=None,
+                           max_exclude: int = 1, trial_iter: int = 8, raim_flags: int = 0, outputs=None, **config) -> PositionFix:
+    """``gat_position_fix_raim_host``: the same rule and the same bits over numpy arrays; needs no device."""
+    want = _wanted(outputs, RAIM_OUTPUTS)
+    recs, tx_ms, tx_frac, rx_ms, rx_frac, weights, E, K = _host_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+    cfg = fix_config(**config)
+    rcfg = _raim_setup(weights, thresholds, p_fa, sigma_m, max_exclude, trial_iter, raim_flags)
+    raw = _host_outputs(want, E, K)
+    raw["integrity"] = np.zeros(E, dtype=_lib.INTEGRITY_DTYPE)
+    rc = _lib.load().gat_position_fix_raim_host(addr(recs), addr(tx_ms), addr(tx_frac), addr(rx_ms), addr(rx_frac), addr(weights), E, K,
+                                                C.byref(cfg), C.byref(rcfg), addr(raw["fixes"]), addr(raw["integrity"]), addr(raw.get("sat")),
+                                                addr(raw.get("resid")), addr(raw.get("sin_el")), addr(raw.get("used")), addr(raw.get("trial")))
+    if rc != 0:
+        raise _lib.GatError(rc, "gat_position_fix_raim_host")
+    return PositionFix(raw)
+
+
+def raim_plan(num_epochs: int, num_channels: int, *, thresholds=None, p_fa: float = 1e-3, sigma_m: float = 1.0, max_exclude: int = 1,
+              trial_iter: int = 8, raim_flags: int = 0, **config) -> dict:
+    """``gat_position_fix_raim_plan``: ``position_plan``'s report for such a call (the LDS holds a round's frozen channels too)."""
+    cfg = fix_config(**config)
+    rcfg = _raim_setup(None, thresholds, p_fa, sigma_m, max_exclude, trial_iter, raim_flags)
+    plan = _lib.FixPlan()
+    plan.struct_size = C.sizeof(_lib.FixPlan)
+    rc = _lib.load().gat_position_fix_raim_plan(int(num_epochs), int(num_channels), C.byref(cfg), C.byref(rcfg), C.byref(plan))
+    if rc != 0:
+        raise _lib.GatError(rc, "gat_position_fix_raim_plan")
     return {n: int(getattr(plan, n)) for n, _ in _lib.FixPlan._fields_ if n not in ("struct_size", "reserved")}

@@ -1542,6 +1542,82 @@ typedef struct gat_obs_plan {
 GAT_API int32_t gat_observables_plan(int32_t num_blocks, int32_t num_channels, int32_t num_epochs, const gat_obs_config *config,
                                      gat_obs_plan *plan);
 
+/* ---- fix integrity: residual test and fault exclusion -------------------------------------------------------------------------
+ * gat_position_fix takes every measurement with its full weight; one that is a code period off (GAT_OBS_EDGE_AMBIGUOUS: 300 km)
+ * moves the fix by kilometres and the status stays 0.  gat_position_fix_raim is gat_position_fix followed per epoch by a test of
+ * the weighted residuals against thresholds of the caller's and, where the test fails, by leave-one-out solves that name the
+ * channel to leave out.  The arithmetic is the position fix's (FP64, no contraction, no libm transcendental, every sum in channel
+ * order from +0: csrc/gat_raim.h on top of csrc/gat_fix.h, shared by the kernel and the host twin: the same bits).
+ *   fix      the position fix's rule unchanged: first pass, mask, second pass -- the state, the used set U and n = num_used.  A
+ *            fix that failed or carries GAT_FIX_NOT_CONVERGED: GAT_RAIM_NOT_CHECKED, every output that of gat_position_fix.
+ *   test     T = sum over the used channels of w (v v) at the final rows (w = 1 without weights), d = n - 4.  d = 0:
+ *            GAT_RAIM_NO_REDUNDANCY.  Else the epoch is detected (GAT_RAIM_DETECTED) when T > threshold[d]: the thresholds are
+ *            the caller's, in the units of T, indexed by d = 1 .. GAT_MAX_FIX_CHANNELS - 4 (entry 0 is not read); +inf never
+ *            detects.  dof = d, stat0 = T, threshold0 = threshold[d] (0 where d = 0).
+ *   round    a detected epoch runs up to max_exclude rounds (0: detection only); a round needs n >= 6.  Once a round every
+ *            channel is frozen where its last row put it: turned about z by OmegaE tau with tau as that row left it, (xr, yr,
+ *            Z), and its range term g = rho + c dts.  A trial of the used channel j solves U \ {j} from the epoch's state
+ *            with the frozen satellites: r = |(xr, yr, Z) - xyz|, los, v = g - (r + b), the same 14 sums (channel j adds +0),
+ *            the same step, at most trial_iter iterations, converged when |d_xyz| < tol_m; T_j = sum of w (v v) over U \ {j}
+ *            at the trial's last state.  A trial counts when it converged, no step failed (a sum or step not finite, a
+ *            singular system) and T_j is finite.  The channel left out, j*, is the counting one with the smallest (T_j, j);
+ *            none counts: the rounds end.
+ *   final    j* leaves the used set, the state becomes j*'s trial state and the rows are evaluated there once, so that every
+ *            travel time is that state's and not the one the fault had moved (68 km of state are 0.4 m of Earth rotation;
+ *            the trial carries that error, a pass that began with it would take it for converged).  Then an ordinary pass of
+ *            the fix's rule (live travel times, max_iter, tol_m) and the rows at its state once more as after every pass;
+ *            the iterations add.  A pass that fails or does not converge ends the rounds.  Else T is tested again at d - 1: passed, the epoch is GAT_RAIM_EXCLUDED and
+ *            the rounds end; failed, the next round runs from there.  There is no second elevation mask.
+ *   stands   GAT_RAIM_EXCLUDED: the outputs are the last pass's -- used and num_used the final set, GAT_FIX_EXCLUDED set in
+ *            fixes.status (by this call alone), the left-out channel's resid and sin_el at the final state like any unused
+ *            channel's; num_excluded and excluded[] in the order of exclusion, stat and threshold those of the final set.
+ *            Detected and not excluded (rounds ended or used up, n < 6, max_exclude = 0): GAT_RAIM_UNRESOLVED, every output
+ *            the full set's, num_excluded = 0, excluded[] = -1, stat = stat0, threshold = threshold0.  Wherever num_excluded
+ *            is 0, fixes, sat, resid, sin_el and used have the bytes gat_position_fix writes.
+ *   trial    optional double [E][K]: T_j of the first round; -1 for a channel that was no candidate or whose trial did not
+ *            count, and in an epoch without a round.
+ * gat_position_fix_raim enqueues one kernel of gat_position_fix's geometry (a wave an epoch, a lane a channel, four epochs a
+ * workgroup); in a round lane j runs trial j by itself from the wave's LDS.  No atomics, no scratch, no synchronisation.
+ * Refusals: gat_position_fix's, and GAT_ERR_ARG for a null integrity pointer or raim config, a wrong struct_size, max_exclude
+ * outside 0 .. GAT_RAIM_MAX_EXCLUDE, trial_iter < 1, non-zero flags and a threshold[1 ..] that is NaN or not > 0. */
+#define GAT_RAIM_MAX_EXCLUDE 4
+#define GAT_RAIM_NOT_CHECKED 1
+#define GAT_RAIM_NO_REDUNDANCY 2
+#define GAT_RAIM_DETECTED 4
+#define GAT_RAIM_EXCLUDED 8
+#define GAT_RAIM_UNRESOLVED 16
+#define GAT_FIX_EXCLUDED 64 /* in gat_fix.status: a channel was left out by gat_position_fix_raim */
+typedef struct gat_raim_config {
+    uint32_t struct_size; /* sizeof(gat_raim_config) */
+    int32_t max_exclude;  /* rounds, 0 .. GAT_RAIM_MAX_EXCLUDE (1); 0: detect only */
+    int32_t trial_iter;   /* iterations a trial, >= 1 (8) */
+    uint32_t flags;       /* 0 */
+    double threshold[61]; /* [GAT_MAX_FIX_CHANNELS - 3]: by d = n - 4, in the units of T; entry 0 is not read */
+} gat_raim_config;
+typedef struct gat_fix_integrity {
+    int32_t status;       /* GAT_RAIM_* bits; 0: tested and passed */
+    int32_t dof;          /* d of the full set */
+    int32_t num_excluded;
+    int32_t excluded[4];  /* channels in the order of exclusion, -1 where unused */
+    int32_t reserved;
+    double stat0, threshold0; /* the full set */
+    double stat, threshold;   /* the final set */
+} gat_fix_integrity;
+GAT_API int32_t gat_position_fix_raim(gat_ctx *ctx, const gat_ephemeris *eph_dev, const int32_t *tx_ms_dev, const double *tx_frac_dev,
+                                      const int32_t *rx_ms_dev, const double *rx_frac_dev, const double *weights_dev,
+                                      int32_t num_epochs, int32_t num_channels, const gat_fix_config *config,
+                                      const gat_raim_config *raim, gat_fix *fixes_dev, gat_fix_integrity *integrity_dev,
+                                      double *sat_dev, double *resid_dev, double *sin_el_dev, uint8_t *used_dev, double *trial_dev);
+/* The same rule in plain loops on the HOST: every pointer is host memory; the bit-exact reference of the device call. */
+GAT_API int32_t gat_position_fix_raim_host(const gat_ephemeris *eph_host, const int32_t *tx_ms_host, const double *tx_frac_host,
+                                           const int32_t *rx_ms_host, const double *rx_frac_host, const double *weights_host,
+                                           int32_t num_epochs, int32_t num_channels, const gat_fix_config *config,
+                                           const gat_raim_config *raim, gat_fix *fixes, gat_fix_integrity *integrity, double *sat,
+                                           double *resid, double *sin_el, uint8_t *used, double *trial);
+/* What gat_position_fix_raim would do with a call (csrc/gat_raim_plan.h): gat_position_fix's geometry with the trial's LDS. */
+GAT_API int32_t gat_position_fix_raim_plan(int32_t num_epochs, int32_t num_channels, const gat_fix_config *config,
+                                           const gat_raim_config *raim, gat_fix_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1526,4 +1526,76 @@ function observables_plan(num_blocks::Integer, num_channels::Integer, num_epochs
     plan[]
 end
 
+# ---- fix integrity: the residual test and fault exclusion on top of the position fix (include/gat.h) ----
+const GAT_RAIM_MAX_EXCLUDE = 4
+const GAT_RAIM_NOT_CHECKED = Int32(1)
+const GAT_RAIM_NO_REDUNDANCY = Int32(2)
+const GAT_RAIM_DETECTED = Int32(4)
+const GAT_RAIM_EXCLUDED = Int32(8)
+const GAT_RAIM_UNRESOLVED = Int32(16)
+const GAT_FIX_EXCLUDED = Int32(64)
+# struct gat_raim_config (504 bytes): threshold by d = n - 4 in the units of T = sum w v^2; entry 1 (d = 0) is not read
+struct RaimConfig
+    struct_size::UInt32
+    max_exclude::Int32            # rounds, 0 .. 4; 0: detect only
+    trial_iter::Int32
+    flags::UInt32
+    threshold::NTuple{61,Float64}
+end
+RaimConfig(threshold; max_exclude::Integer = 1, trial_iter::Integer = 8) =
+    RaimConfig(UInt32(sizeof(RaimConfig)), Int32(max_exclude), Int32(trial_iter), UInt32(0), NTuple{61,Float64}(Float64.(threshold)))
+# struct gat_fix_integrity (64 bytes)
+struct FixIntegrity
+    status::Int32                 # GAT_RAIM_* bits
+    dof::Int32
+    num_excluded::Int32
+    excluded::NTuple{4,Int32}     # 0-based channels in the order of exclusion, -1 where unused
+    reserved::Int32
+    stat0::Float64
+    threshold0::Float64
+    stat::Float64
+    threshold::Float64
+end
+# position_fix! with the residual test and fault exclusion; integrity [E], trial [K x E] (may be C_NULL).  Enqueues only.
+function position_fix_raim!(ctx::Context, eph::Ptr{Ephemeris}, tx_ms::Ptr{Int32}, tx_frac::Ptr{Float64}, rx_ms::Ptr{Int32}, rx_frac::Ptr{Float64},
+                            num_epochs::Integer, num_channels::Integer, cfg::FixConfig, raim::RaimConfig, fixes::Ptr{Fix},
+                            integrity::Ptr{FixIntegrity}; weights::Ptr{Float64} = Ptr{Float64}(C_NULL), sat::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                            resid::Ptr{Float64} = Ptr{Float64}(C_NULL), sin_el::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                            used::Ptr{UInt8} = Ptr{UInt8}(C_NULL), trial::Ptr{Float64} = Ptr{Float64}(C_NULL))
+    check(ctx, ccall((:gat_position_fix_raim, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Ephemeris}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ref{FixConfig},
+                      Ref{RaimConfig}, Ptr{Fix}, Ptr{FixIntegrity}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}),
+                     ctx.handle, eph, tx_ms, tx_frac, rx_ms, rx_frac, weights, Int32(num_epochs), Int32(num_channels), Ref(cfg), Ref(raim), fixes,
+                     integrity, sat, resid, sin_el, used, trial))
+end
+# the same rule on host memory, the bit-exact reference of the device call: tx_ms, tx_frac [K, E]; returns
+# (fixes [E], integrity [E], sat [4, K, E], resid [K, E], sin_el [K, E], used [K, E], trial [K, E])
+function position_fix_raim_host(eph::Vector{Ephemeris}, tx_ms::Matrix{Int32}, tx_frac::Matrix{Float64}, rx_ms::Vector{Int32},
+                                rx_frac::Vector{Float64}, raim::RaimConfig; weights::Union{Nothing,Matrix{Float64}} = nothing,
+                                cfg::FixConfig = FixConfig())
+    K, E = size(tx_ms)
+    fixes = Vector{Fix}(undef, E)
+    integrity = Vector{FixIntegrity}(undef, E)
+    sat = zeros(Float64, 4, K, E)
+    resid = zeros(Float64, K, E)
+    sin_el = zeros(Float64, K, E)
+    used = zeros(UInt8, K, E)
+    trial = zeros(Float64, K, E)
+    rc = ccall((:gat_position_fix_raim_host, libgat), Int32,
+               (Ptr{Ephemeris}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ref{FixConfig}, Ref{RaimConfig},
+                Ptr{Fix}, Ptr{FixIntegrity}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}),
+               eph, tx_ms, tx_frac, rx_ms, rx_frac, weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights), Int32(E), Int32(K), Ref(cfg),
+               Ref(raim), fixes, integrity, sat, resid, sin_el, used, trial)
+    rc == GAT_OK || throw(GatError(rc, "gat_position_fix_raim_host"))
+    fixes, integrity, sat, resid, sin_el, used, trial
+end
+# what position_fix_raim! would do with a call, without a device
+function position_fix_raim_plan(num_epochs::Integer, num_channels::Integer, raim::RaimConfig, cfg::FixConfig = FixConfig())
+    plan = Ref(FixPlan(UInt32(sizeof(FixPlan)), 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_position_fix_raim_plan, libgat), Int32, (Int32, Int32, Ref{FixConfig}, Ref{RaimConfig}, Ref{FixPlan}), Int32(num_epochs),
+               Int32(num_channels), Ref(cfg), Ref(raim), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_position_fix_raim_plan"))
+    plan[]
+end
+
 end # module
