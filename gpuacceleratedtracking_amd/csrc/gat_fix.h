@@ -34,7 +34,9 @@ GAT_HD inline bool fix_finite(double x)
 
 // ---- sine and cosine ------------------------------------------------------------------------------------------------------------------
 // Cody-Waite by pi/2 in three parts (33 + 33 + 53 bits: q P1 and q P2 are exact for |q| < 2^20), then the Taylor polynomials of
-// degree 17 and 18 on [-pi/4, pi/4] in Horner form with explicit fused multiply-adds.  |error| <= 1e-15 on |x| <= 64.
+// degree 17 and 18 on [-pi/4, pi/4] in Horner form with explicit fused multiply-adds.  |error| <= 1e-15 on |x| <= 72.
+// Beyond the reduction's range (|x| well above 2^20) the results are no sine and cosine -- of any magnitude, or not finite --, but
+// every operation is defined for every x, NaN and the infinities included, so both builds still give the same bits.
 GAT_HD inline void fix_sincos(double x, double *c, double *s)
 {
     const double q = __builtin_rint(x * 0.6366197723675814);
@@ -59,7 +61,10 @@ GAT_HD inline void fix_sincos(double x, double *c, double *s)
     cp = __builtin_fma(r2, cp, 4.1666666666666664e-02);
     cp = __builtin_fma(r2, cp, -0.5);
     cp = __builtin_fma(r2, cp, 1.0);
-    const int qi = (int)(long long)q & 3;
+    // q mod 4 in doubles: q / 4, its floor, the product and the difference are exact for every finite q, so the conversion sees 0 .. 3
+    // whatever |q| is (a conversion of q itself is undefined from 2^63 on and differs between the builds); not finite: quadrant 0
+    const double qm = q - 4.0 * __builtin_floor(q * 0.25);
+    const int qi = qm < 4.0 ? (int)qm : 0;
     const double cs = (qi & 1) ? sp : cp;
     const double sn = (qi & 1) ? cp : sp;
     *c = (qi == 1 || qi == 2) ? -cs : cs;

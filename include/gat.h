@@ -1285,7 +1285,11 @@ GAT_API int32_t gat_nav_decode_plan(int32_t num_channels, const gat_nav_config *
  * host twin: the same bits).
  *   sincos   q = rint(x * 2/pi); r = x - q P1 - q P2 - q P3 by three fused multiply-adds, P1 and P2 the first and second 33
  *            bits of pi/2, P3 the rest; sin and cos of r by the Taylor polynomials of degree 17 and 18 in Horner form;
- *            the quadrant from q mod 4.  |error| <= 1e-15 on |x| <= 64.
+ *            the quadrant from q mod 4, taken in doubles (q - 4 floor(q / 4), exact for every finite q; 0 where q is not
+ *            finite).  |error| <= 1e-15 on |x| <= 72 (Omega reaches +-69.3).  Beyond the reduction's range -- |x| above
+ *            2^20, which an ephemeris that is usable below can reach: sqrt_a = 0.004 gives M = 1e18 -- the results are
+ *            defined for every x and equal on the device and on the host, but are not a sine and a cosine and need not lie
+ *            in [-1, 1]: such a channel counts with a meaningless finite state, or does not count where it is not finite.
  *   times    a time of the week is whole milliseconds (int32, 0 .. 604799999) and a fraction in seconds (double, [0, 1e-3)).
  *            Transmission tx_ms, tx_frac [E][K]; reception (nominal, by the receiver's clock) rx_ms, rx_frac [E].  A
  *            negative ms or a non-finite fraction: no measurement (of the channel; of the whole epoch for rx).
@@ -1302,7 +1306,13 @@ GAT_API int32_t gat_nav_decode_plan(int32_t num_channels, const gat_nav_config *
  *            7.2921151467e-5, c = 299792458.
  *   usable   a channel counts in an epoch (num_valid) when its ephemeris has valid != 0, 0 <= e < 0.5 and sqrt_a > 0, both
  *            times are given and its state and pseudorange are finite; it is used when besides its weight (1 without
- *            weights) is finite and > 0.  An unusable ephemeris is not an error.
+ *            weights) is finite and > 0.  An unusable ephemeris is not an error.  Given means ms >= 0 and a finite
+ *            fraction, nothing more: tx_ms = 604800000 or INT32_MAX counts, -0.0 is an eccentricity.  On all of e < 0.5,
+ *            sqrt_a in 3000 .. 7000 and t_k in [-302400, 302400) the state is within 1e-5 m and 1e-18 s of the formulas
+ *            in exact arithmetic (derived from the roundings: 4.6e-6 m at e = 0 to 7.9e-6 m at e = 0.5; measured 5e-7 to
+ *            9.5e-7 m: DESIGN.md 4.15).  What passes this fence with numbers no orbit has (sqrt_a = 0.0086: a satellite
+ *            76 m from the Earth's centre) counts all the same, and the fix of its epoch is wrong with status 0 or does
+ *            not converge: an elevation mask takes such a satellite out, gat_position_fix_raim detects and names it.
  *   solver   unknowns (x, y, z, b), b = c * the receiver's clock error; start init_xyz, b = 0.  An iteration: per usable
  *            channel the travel time tau is 0.075 s until the channel has a range and r / c of its last range after, the
  *            satellite is turned about z by OmegaE tau, r is the range from the receiver to it, los the unit vector, v =

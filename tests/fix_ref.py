@@ -2,7 +2,8 @@
 algorithm: numpy's sin, cos and arctan2, the true anomaly as an angle, Kepler's equation iterated until it stands still, and the
 least-squares step by ``np.linalg.lstsq``.  It shares no text with the library's rule; the tests compare the two within bounds
 derived from the arithmetic, never bit for bit.  An ephemeris is anything indexable by field name (a record of the structured
-array), a time of the week a pair (whole milliseconds, fraction in seconds)."""
+array), a time of the week a pair (whole milliseconds, fraction in seconds).  The clock and the orbit compute in the type they are
+given: float64, or numpy's long double through ``satellite_long``, for the tests whose bound is the rule's own rounding."""
 import numpy as np
 
 MU = 3.986005e14
@@ -12,12 +13,18 @@ F_REL = -4.442807633e-10
 WEEK = 604800.0
 
 
+def _real(x):
+    """float64, or numpy's long double where the caller brought one: every function below computes in the type it is given"""
+    x = np.asarray(x)
+    return x if x.dtype == np.longdouble else x.astype(np.float64)
+
+
 def wrap_week(dt):
-    return (np.asarray(dt, dtype=np.float64) + WEEK / 2) % WEEK - WEEK / 2
+    return (_real(dt) + WEEK / 2) % WEEK - WEEK / 2
 
 
 def eccentric_anomaly(mean, ecc):
-    big_e = np.array(mean, dtype=np.float64, copy=True)
+    big_e = np.array(_real(mean), copy=True)
     for _ in range(20):  # Newton; quadratic, at rest long before
         big_e = big_e - (big_e - ecc * np.sin(big_e) - mean) / (1.0 - ecc * np.cos(big_e))
     return big_e
@@ -54,6 +61,18 @@ def satellite(eph, tx_ms, tx_frac):
     t_sv = np.asarray(tx_ms, dtype=np.float64) * 1e-3 + tx_frac
     dts = clock_correction(eph, t_sv)
     return orbit(eph, t_sv - dts), dts
+
+
+def satellite_long(eph, tx_ms, tx_frac):
+    """``satellite`` in numpy's long double (64 bits of mantissa on x86): every field and both parts of the time raised first, the
+    milliseconds divided by 1000 there, so that no rounding of a double is left in it -- the yardstick where the bound is derived
+    from the rule's own roundings (tests/test_position_domain_host.py).  eph: a record or records of the structured array."""
+    if np.finfo(np.longdouble).eps > 1e-18:
+        raise RuntimeError("numpy's long double is no wider than double here")
+    wide = {name: np.asarray(eph[name]).astype(np.longdouble) for name in eph.dtype.names if eph.dtype[name].kind == "f"}
+    t_sv = np.asarray(tx_ms).astype(np.longdouble) / np.longdouble(1000) + np.asarray(tx_frac).astype(np.longdouble)
+    dts = clock_correction(wide, t_sv)
+    return orbit(wide, t_sv - dts), dts
 
 
 def pseudorange(rx_ms, rx_frac, tx_ms, tx_frac):

@@ -4,8 +4,10 @@
 // documented refusal must return its code with nothing planned.  The twin then runs on heap buffers of exactly the extents the
 // call describes -- every subset of the optional outputs, with and without weights, epochs without measurements among good ones --
 // so that AddressSanitizer sees any access outside them, and must find the receivers the transmit times were made for.  The
-// ephemeris goes through the encoder and the decoder and must come back equal.  Built with -fsanitize=address,undefined by
-// tests/test_position_plan_host.py.  `fixplan sincos FILE` writes x, cos, sin of fix_sincos over a grid as raw doubles instead.
+// ephemeris goes through the encoder and the decoder and must come back equal.  Built with -fsanitize=address,undefined,
+// float-cast-overflow by tests/test_position_plan_host.py.  `fixplan sincos FILE` writes x, cos, sin of fix_sincos as raw doubles
+// instead: a dense grid on [-72, 72], every multiple of pi/4 there, and +-2^k up to the largest double with their neighbours, where
+// the sanitizer sees a quadrant taken by an out-of-range conversion.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -295,17 +297,21 @@ int sincos_grid(const char *path)
         fix_sincos(x, &v[1], &v[2]);
         std::fwrite(v, sizeof(double), 3, out);
     };
-    const int n = 400000;
-    for (int i = 0; i <= n; ++i) put(-64.0 + 128.0 * (double)i / n);
-    for (int k = -82; k <= 82; ++k) { // the reduction's boundaries and its zeros, with their neighbours
-        double x = (double)k * 0.78539816339744831;
+    auto around = [&](double x) { // x with four neighbours each side
         double lo = x, hi = x;
         put(x);
         for (int j = 0; j < 4; ++j) {
-            lo = std::nextafter(lo, -100.0), hi = std::nextafter(hi, 100.0);
+            lo = std::nextafter(lo, -std::numeric_limits<double>::infinity()), hi = std::nextafter(hi, std::numeric_limits<double>::infinity());
             put(lo), put(hi);
         }
-    }
+    };
+    const int n = 450000; // the density of the grid on [-64, 64] before it reached 72: Omega goes to +-69.3
+    for (int i = 0; i <= n; ++i) put(-72.0 + 144.0 * (double)i / n);
+    for (int k = -92; k <= 92; ++k) around((double)k * 0.78539816339744831); // the reduction's boundaries and its zeros
+    // every power of two from 64 to the largest, both signs: a sine up to 2^20, defined (and equal in both builds) beyond, where the
+    // quadrant's q passes 2^53, 2^63 and every other width a conversion could have; then what is not finite
+    for (int k = 6; k <= 1023; ++k) around(std::ldexp(1.0, k)), around(-std::ldexp(1.0, k));
+    put(std::numeric_limits<double>::infinity()), put(-std::numeric_limits<double>::infinity()), put(std::numeric_limits<double>::quiet_NaN());
     std::fclose(out);
     return 0;
 }

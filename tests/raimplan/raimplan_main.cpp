@@ -6,7 +6,9 @@
 // that AddressSanitizer sees any access outside them, and must leave out the channel that was moved and find the receiver.  Last, a
 // round is walked the way the kernel runs it -- 64 lanes in step, lane j holding candidate j, every lane reading the same entry, the
 // lanes that are done idling, the choice by a butterfly of exchanges over (T_j, j) -- and must give the twin's T_j and choice to the
-// bit.  Built with -fsanitize=address,undefined by tests/test_raim_plan_host.py.
+// bit; and the twin runs through orbits that are usable by the letter and garbage by their numbers, where the sine's quadrant must
+// be taken without an out-of-range conversion.  Built with -fsanitize=address,undefined,float-cast-overflow by
+// tests/test_raim_plan_host.py.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -347,6 +349,43 @@ int twins(std::mt19937_64 &rng, int count, int *rounds)
     return calls;
 }
 
+// Orbits that are usable by the letter and garbage by their numbers (gat.h, "sincos"): sqrt_a of 2^-19, 0.004 and 0.0086 put the mean
+// anomaly at 1e28, 1e18 and 1e17 rad, where the quadrant's q passes 2^63 and 2^53, and a transmit time of 1e19 s.  The twin must run
+// through them with every operation defined -- the sanitizers' business, float-cast-overflow among them -- and write finite numbers.
+void garbage_orbits(std::mt19937_64 &rng)
+{
+    const int K = 10, E = 2;
+    std::vector<gat_ephemeris> ephs = constellation(rng, K);
+    std::vector<int32_t> tx_ms((size_t)E * K), rx_ms((size_t)E);
+    std::vector<double> tx_frac((size_t)E * K), rx_frac((size_t)E);
+    for (int e = 0; e < E; ++e) {
+        const double x[3] = {6371e3 * std::cos(0.8 + e), 6371e3 * std::sin(0.8 + e), 0.0};
+        rx_ms[(size_t)e] = 208800000 + 1000 * e, rx_frac[(size_t)e] = 2e-4;
+        for (int k = 0; k < K; ++k) {
+            const size_t o = (size_t)e * K + k;
+            if (!measure(ephs[(size_t)k], x, rx_ms[(size_t)e], rx_frac[(size_t)e], 1e-4, &tx_ms[o], &tx_frac[o])) tx_ms[o] = rx_ms[(size_t)e] - 70, tx_frac[o] = 5e-4;
+        }
+    }
+    ephs[0].sqrt_a = 0x1p-19, ephs[1].sqrt_a = 0.004, ephs[2].sqrt_a = 0.0086;
+    tx_frac[3] = 1e19;
+    const gat_fix_config cfg = fix_cfg(12, 1e-6, -1.0);
+    gat_raim_config rc = raim_cfg(4, 8);
+    for (int d = 1; d < kRaimThresholds; ++d) rc.threshold[d] = 1e-300; // every checked epoch is detected and runs its rounds
+    std::vector<double> sat((size_t)E * K * 4), resid((size_t)E * K), sel((size_t)E * K), trial((size_t)E * K);
+    std::vector<uint8_t> used((size_t)E * K);
+    std::vector<gat_fix> fixes((size_t)E);
+    std::vector<gat_fix_integrity> integ((size_t)E);
+    static RaimPlan p;
+    const Refusal r = raim_plan(RaimCall{FixCall{ephs.data(), tx_ms.data(), tx_frac.data(), rx_ms.data(), rx_frac.data(), E, K, &cfg, fixes.data()}, &rc, integ.data()},
+                                &p);
+    CHECK(r.code == GAT_OK, "garbage orbits: refused");
+    raim_host_run(p, ephs.data(), tx_ms.data(), tx_frac.data(), rx_ms.data(), rx_frac.data(), nullptr, fixes.data(), integ.data(), sat.data(), resid.data(),
+                  sel.data(), used.data(), trial.data());
+    for (int e = 0; e < E; ++e) CHECK(fixes[(size_t)e].num_valid >= K - 1, "garbage orbits: epoch %d counts %d channels", e, fixes[(size_t)e].num_valid);
+    for (double v : sat) CHECK(std::isfinite(v), "garbage orbits: a state that is not finite was written");
+    CHECK(sat[4] != 0.0 && sat[8] != 0.0 && sat[12] != 0.0, "garbage orbits: sqrt_a = 0.004 and 0.0086 and t_sv = 1e19 s count");
+}
+
 } // namespace
 
 int main()
@@ -356,6 +395,7 @@ int main()
     const int planned = plans(rng, 3000);
     int rounds = 0;
     const int calls = twins(rng, 6, &rounds);
+    garbage_orbits(rng);
     std::printf("planned %d calls, ran the twin %d times, walked %d rounds, %d failures\n", planned, calls, rounds, failures);
     return failures || rounds < 12 ? 1 : 0;
 }

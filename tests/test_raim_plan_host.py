@@ -1,25 +1,24 @@
 """The pure plan of gat_position_fix_raim (csrc/gat_raim_plan.h) and the host twin's loops over it (the rules of csrc/gat_fix.h and
-csrc/gat_raim.h), compiled stand-alone with their own main (tests/raimplan/raimplan_main.cpp) under AddressSanitizer and UBSan, and
-run: every documented refusal with nothing planned, a few thousand random plans with every lane's frozen channel inside the wave's
+csrc/gat_raim.h), compiled stand-alone with their own main (tests/raimplan/raimplan_main.cpp) under AddressSanitizer and UBSan with
+float-cast-overflow, and run: every documented refusal with nothing planned, a few thousand random plans with every lane's frozen channel inside the wave's
 LDS, the host twin on heap buffers of exactly the described extents with every subset of the optional outputs -- it must leave out
 the channel that was moved by a code period and find the receiver --, and a round walked lane-per-candidate the way the kernel runs
 it, which must give the twin's trial statistics and its choice to the bit.  The program stands alone; nothing is loaded into Python."""
 import os
-import shutil
 import subprocess
 
 import pytest
+
+from tests.fix_domain import sanitizing_compiler
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.fail("g++ not found: the plan header cannot be checked")
     out = str(tmp_path_factory.mktemp("raimplan") / "raimplan")
-    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
+    subprocess.run([sanitizing_compiler(), "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
+                    "-fsanitize=address,undefined,float-cast-overflow",
                     "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "gpuacceleratedtracking_amd", "csrc"),
                     os.path.join(ROOT, "tests", "raimplan", "raimplan_main.cpp"), "-o", out], check=True)
     return out
