@@ -23,6 +23,7 @@ from . import _lib
 from .array import beamform_desc
 from .context import Context, get_context
 from .gen_signal import make_params
+from .results import host_check, new_plan, plan_report
 from .signals import GNSSSystem, get_code_frequency
 from .streams import input_desc, ref, vp
 
@@ -145,13 +146,11 @@ def acquire_fft_plan(desc: _lib.SignalDesc, num_blocks: int, num_prns: int, samp
     """``gat_acquire_fft_plan``: what ``gat_acquire_fft`` would do with this call (transform length, lag segments, passes, batches,
     unit groups, scratch bytes), without a device.  ``num_cus``: the device's compute units (``Context.device_info()``); the three
     options as ``Context.set_option`` would set them.  Raises ``GatError`` with the refusal the call would get."""
-    plan = _lib.AcqFftPlan()
-    plan.struct_size = C.sizeof(_lib.AcqFftPlan)
+    plan = new_plan(_lib.AcqFftPlan)
     rc = _lib.load().gat_acquire_fft_plan(ref(desc), int(num_blocks), int(num_prns), float(sampling_frequency), ref(config), int(fft_log2),
                                           int(doppler_batch), int(unit_batch), int(num_cus), int(bool(own_power)), C.byref(plan))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_acquire_fft_plan")
-    return {n: int(getattr(plan, n)) for n, _ in plan._fields_ if n != "struct_size"}
+    host_check(rc, "gat_acquire_fft_plan")
+    return plan_report(plan)
 
 
 def acquire_fft_host(desc: _lib.SignalDesc, num_blocks: int, codes: np.ndarray, prns, sampling_frequency: float, config: _lib.AcqConfig,
@@ -167,8 +166,7 @@ def acquire_fft_host(desc: _lib.SignalDesc, num_blocks: int, codes: np.ndarray, 
     rc = _lib.load().gat_acquire_fft_host(C.byref(desc), int(num_blocks), C.c_void_p(tab.ctypes.data), int(tab.shape[1]), int(tab.shape[1]),
                                           prn_arr.ctypes.data_as(C.POINTER(C.c_int32)), P, float(sampling_frequency), C.byref(config),
                                           int(fft_log2), int(unit_groups), C.c_void_p(power.ctypes.data))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_acquire_fft_host")
+    host_check(rc, "gat_acquire_fft_host")
     return power
 
 
@@ -183,8 +181,7 @@ def acquisition_stats_host(power: np.ndarray, config: _lib.AcqConfig, sampling_f
     res = np.zeros(max(P, 1), dtype=_lib.ACQ_RESULT_DTYPE)
     rc = _lib.load().gat_acq_stats_host(C.c_void_p(g.ctypes.data), P, D, J, C.byref(config), float(sampling_frequency),
                                         int(num_samples), C.c_void_p(res.ctypes.data))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_acq_stats_host")
+    host_check(rc, "gat_acq_stats_host")
     return res[:P]
 
 

@@ -105,34 +105,29 @@ int32_t check_loop_config(gat_ctx *c, const gat_loop_config *cfg)
     return GAT_OK;
 }
 
-} // namespace gat
-
-namespace {
-
-// `update`: the loop's update step for one block's accumulators (gat_tracking_update, or a weighted one handed in by
-// gat_array_api.cpp: this file names no launcher of the array kernels)
-int32_t tracking_run_enqueue(gat_ctx *c, const gat_signal_desc *sig, int32_t num_blocks, int32_t K, int32_t L,
-                             const int32_t *shifts, double fs, gat_channel_params *params_a, gat_channel_params *params_b,
-                             float *acc_re, float *acc_im, int64_t acc_block_stride, uint32_t flags, int32_t *current_is_b,
-                             const LoopUpdateFn &update)
+int32_t tracking_run_enqueue(gat_ctx *c, const gat_signal_desc *sig, int32_t num_blocks, int32_t K, int32_t L, const int32_t *shifts, double fs,
+                             const gat_loop_config *cfg, gat_loop_state *state, LoopRecords rec, float *acc_re, float *acc_im,
+                             int64_t acc_block_stride, uint32_t flags, const double *w_re, const double *w_im)
 {
     const size_t sample_bytes = (size_t)layout_sample_bytes(sig->layout);
-    gat_channel_params *cur = params_a, *nxt = params_b;
     for (int32_t b = 0; b < num_blocks; ++b) { // everything is enqueued on the ctx stream, nothing synchronises
         gat_signal_desc d = *sig;
         const size_t off = (size_t)b * (size_t)sig->block_stride * sample_bytes;
         d.re = static_cast<const char *>(sig->re) + off;
         if (sig->im) d.im = static_cast<const char *>(sig->im) + off;
         float *o_re = acc_re + (size_t)b * (size_t)acc_block_stride, *o_im = acc_im + (size_t)b * (size_t)acc_block_stride;
+        gat_channel_params *cur = rec.of(b, K), *nxt = rec.of(b + 1, K);
         int32_t rc = correlate_impl(c, &d, cur, 1, K, L, shifts, fs, o_re, o_im, flags);
         if (rc != GAT_OK) return rc;
-        rc = update(o_re, o_im, cur, nxt);
+        rc = gat_tracking_update_weighted(c, o_re, o_im, K, sig->num_ants, cfg, state, cur, nxt, w_re, w_im);
         if (rc != GAT_OK) return rc;
-        std::swap(cur, nxt);
     }
-    if (current_is_b) *current_is_b = cur == params_b ? 1 : 0;
     return GAT_OK;
 }
+
+} // namespace gat
+
+namespace {
 
 template <typename T>
 void key_put(std::vector<unsigned char> &k, const T &v)
@@ -274,7 +269,7 @@ namespace gat {
 int32_t tracking_run_shared(gat_ctx *c, const gat_signal_desc *sig, int32_t num_blocks, int32_t K, int32_t L, const int32_t *shifts,
                             double fs, const gat_loop_config *cfg, gat_loop_state *state, gat_channel_params *params_a,
                             gat_channel_params *params_b, float *acc_re, float *acc_im, int64_t acc_block_stride, uint32_t flags,
-                            int32_t *current_is_b, const double *w_re, const double *w_im, const LoopUpdateFn &update)
+                            int32_t *current_is_b, const double *w_re, const double *w_im)
 {
     if (!c || !sig || !shifts || !cfg || !state || !params_a || !params_b || !acc_re || !acc_im)
         return fail(c, GAT_ERR_ARG, "null argument");
@@ -283,9 +278,12 @@ int32_t tracking_run_shared(gat_ctx *c, const gat_signal_desc *sig, int32_t num_
     if (flags & ~(GAT_FLAG_ATOMIC | GAT_FLAG_GRAPH)) return fail(c, GAT_ERR_ARG, "unknown flag bits");
     GAT_ENTER(c, "gat_tracking_run");
     const uint32_t kflags = flags & ~GAT_FLAG_GRAPH;
-    if (!(flags & GAT_FLAG_GRAPH))
-        return tracking_run_enqueue(c, sig, num_blocks, K, L, shifts, fs, params_a, params_b, acc_re, acc_im, acc_block_stride, kflags,
-                                    current_is_b, update);
+    const LoopRecords rec{params_a, params_b};
+    if (!(flags & GAT_FLAG_GRAPH)) {
+        const int32_t rc = tracking_run_enqueue(c, sig, num_blocks, K, L, shifts, fs, cfg, state, rec, acc_re, acc_im, acc_block_stride, kflags, w_re, w_im);
+        if (rc == GAT_OK && current_is_b) *current_is_b = rec.of(num_blocks, K) == params_b ? 1 : 0;
+        return rc;
+    }
 
     // hipGraph path: the 2-3 launches per block are too short to hide their launch gaps.  Every argument that
     // shapes the launch sequence is part of the key -- field by field (struct padding of a C caller is not
@@ -308,8 +306,7 @@ int32_t tracking_run_shared(gat_ctx *c, const gat_signal_desc *sig, int32_t num_
     };
     if (current_is_b) *current_is_b = (num_blocks & 1) ? 1 : 0; // the buffers swap once per block
     return graph_replay_or_record(c, make_key, [&]() {
-        return tracking_run_enqueue(c, sig, num_blocks, K, L, shifts, fs, params_a, params_b, acc_re, acc_im, acc_block_stride, kflags,
-                                    nullptr, update);
+        return tracking_run_enqueue(c, sig, num_blocks, K, L, shifts, fs, cfg, state, rec, acc_re, acc_im, acc_block_stride, kflags, w_re, w_im);
     });
 }
 
@@ -700,12 +697,8 @@ GAT_API int32_t gat_tracking_run(gat_ctx *c, const gat_signal_desc *sig, int32_t
                                  gat_channel_params *params_a, gat_channel_params *params_b, float *acc_re,
                                  float *acc_im, int64_t acc_block_stride, uint32_t flags, int32_t *current_is_b)
 {
-    // (the null checks are tracking_run_shared's: the update below is not called before them)
     return tracking_run_shared(c, sig, num_blocks, K, L, shifts, fs, cfg, state, params_a, params_b, acc_re, acc_im, acc_block_stride,
-                               flags, current_is_b, nullptr, nullptr,
-                               [&](const float *o_re, const float *o_im, const gat_channel_params *cur, gat_channel_params *nxt) {
-                                   return gat_tracking_update(c, o_re, o_im, K, sig->num_ants, cfg, state, cur, nxt);
-                               });
+                               flags, current_is_b, nullptr, nullptr);
 }
 
 GAT_API int32_t gat_malloc(gat_ctx *c, size_t bytes, void **out)

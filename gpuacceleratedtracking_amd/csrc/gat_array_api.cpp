@@ -83,8 +83,5 @@ GAT_API int32_t gat_tracking_run_weighted(gat_ctx *c, const gat_signal_desc *sig
                                 current_is_b);
     if (!w_re || !w_im) return fail(c, GAT_ERR_ARG, "null argument"); // (the other null checks are tracking_run_shared's)
     return tracking_run_shared(c, sig, num_blocks, K, L, shifts, fs, cfg, state, params_a, params_b, acc_re, acc_im, acc_block_stride, flags,
-                               current_is_b, w_re, w_im,
-                               [&](const float *o_re, const float *o_im, const gat_channel_params *cur, gat_channel_params *nxt) {
-                                   return gat_tracking_update_weighted(c, o_re, o_im, K, sig->num_ants, cfg, state, cur, nxt, w_re, w_im);
-                               });
+                               current_is_b, w_re, w_im);
 }

@@ -13,7 +13,6 @@
 #pragma once
 
 #include <cmath>
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -180,17 +179,37 @@ int32_t enqueue_estimates(gat_ctx *c, const gat_signal_desc *sig, const Estimate
     }
     return GAT_OK;
 }
+// What gat_last_launch_info reports after an entry point whose launch is told by these five: scalar loads (vec 1), the rest zero.
+inline void set_last_launch(gat_ctx *c, long long workgroups, int32_t threads, int32_t splits, int32_t ant_tile, int32_t lds_bytes)
+{
+    c->last = gat_launch_info{};
+    c->last.workgroups = (int32_t)workgroups;
+    c->last.threads = threads;
+    c->last.splits = splits;
+    c->last.ant_tile = ant_tile;
+    c->last.vec = 1;
+    c->last.lds_bytes = lds_bytes;
+}
 // validation of a loop configuration (gat_tracking_update and the weighted update)
 int32_t check_loop_config(gat_ctx *c, const gat_loop_config *cfg);
 
-// The closed loop's native run (gat_api.cpp), shared by gat_tracking_run and gat_tracking_run_weighted (gat_array_api.cpp):
-// `update` enqueues the loop's update step for one block's accumulators and parameter pair; w_re / w_im (null: the
-// unweighted run) are what that step reads besides, and belong to the key of a recorded graph.
-using LoopUpdateFn = std::function<int32_t(const float *acc_re, const float *acc_im, const gat_channel_params *cur, gat_channel_params *next)>;
+// Where the closed loop's block b reads its records and writes its successor's: the ping-pong pair alternating (b set; block 0
+// reads a), or rows b and b + 1 of one array of K records a row (b null: the history run).
+struct LoopRecords {
+    gat_channel_params *a, *b;
+    gat_channel_params *of(int32_t block, int32_t K) const { return b ? ((block & 1) ? b : a) : a + (size_t)block * (size_t)K; }
+};
+// The closed loop's block sequence (gat_api.cpp), the one enqueue of gat_tracking_run, gat_tracking_run_weighted and
+// gat_tracking_run_history: per block the correlator call, then gat_tracking_update_weighted (w_re / w_im null: gat_tracking_update).
+int32_t tracking_run_enqueue(gat_ctx *c, const gat_signal_desc *sig, int32_t num_blocks, int32_t K, int32_t L, const int32_t *shifts, double fs,
+                             const gat_loop_config *cfg, gat_loop_state *state, LoopRecords rec, float *acc_re, float *acc_im,
+                             int64_t acc_block_stride, uint32_t flags, const double *w_re, const double *w_im);
+// gat_tracking_run and gat_tracking_run_weighted (gat_array_api.cpp): validation, the eager sequence, the graph cache; w_re / w_im
+// (null: the unweighted run) belong to the key of a recorded graph.
 int32_t tracking_run_shared(gat_ctx *c, const gat_signal_desc *sig, int32_t num_blocks, int32_t K, int32_t L, const int32_t *shifts,
                             double fs, const gat_loop_config *cfg, gat_loop_state *state, gat_channel_params *params_a,
                             gat_channel_params *params_b, float *acc_re, float *acc_im, int64_t acc_block_stride, uint32_t flags,
-                            int32_t *current_is_b, const double *w_re, const double *w_im, const LoopUpdateFn &update);
+                            int32_t *current_is_b, const double *w_re, const double *w_im);
 
 // params_dev: [B*K] records on the device -- or null with params_inline: B*K <= kInlineParams validated HOST records that
 // travel inside the vector kernel's arguments (uploaded after all if a matrix-core kernel takes the call)

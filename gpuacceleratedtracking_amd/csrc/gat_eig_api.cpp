@@ -51,13 +51,7 @@ GAT_API int32_t gat_accumulator_covariance(gat_ctx *c, const float *acc_re, cons
         GAT_HIP(c, launch_acc_cov_reduce(a, p, c->stream));
     } else
         GAT_HIP(c, launch_acc_cov_direct(a, p, c->stream));
-    c->last = gat_launch_info{};
-    c->last.workgroups = (int32_t)p.g_chunk;
-    c->last.threads = kCovThreads;
-    c->last.splits = p.split ? p.C : 1;
-    c->last.ant_tile = p.M;
-    c->last.vec = 1;
-    c->last.lds_bytes = p.lds_bytes;
+    set_last_launch(c, p.g_chunk, kCovThreads, p.split ? p.C : 1, p.M, p.lds_bytes);
     return GAT_OK;
 }
 
@@ -81,13 +75,7 @@ GAT_API int32_t gat_hermitian_eig(gat_ctx *c, const void *a_re, const void *a_im
     GAT_ENTER(c, "gat_hermitian_eig");
     a.a_re = a_re, a.a_im = a_im, a.eigenvalues = eigenvalues, a.vec_re = vec_re, a.vec_im = vec_im, a.status = status;
     GAT_HIP(c, launch_hermitian_eig(a, c->stream));
-    c->last = gat_launch_info{};
-    c->last.workgroups = (int32_t)a.p.g;
-    c->last.threads = a.p.threads;
-    c->last.splits = 1;
-    c->last.ant_tile = a.p.Q;
-    c->last.vec = 1;
-    c->last.lds_bytes = a.p.lds_bytes;
+    set_last_launch(c, a.p.g, a.p.threads, 1, a.p.Q, a.p.lds_bytes);
     return GAT_OK;
 }
 

@@ -27,19 +27,9 @@ GAT_API int32_t gat_position_fix(gat_ctx *c, const gat_ephemeris *eph, const int
     const Refusal r = fix_plan(FixCall{eph, tx_ms, tx_frac, rx_ms, rx_frac, E, K, cfg, fixes}, &p);
     if (r.code != GAT_OK) return fail(c, r.code, r.msg);
     GAT_ENTER(c, "gat_position_fix");
-    FixArgs a{};
-    a.eph = eph, a.tx_ms = tx_ms, a.tx_frac = tx_frac, a.rx_ms = rx_ms, a.rx_frac = rx_frac, a.w = weights;
-    a.fixes = fixes, a.sat = sat, a.resid = resid, a.sin_el = sin_el, a.used = used;
-    a.E = p.E, a.K = p.K, a.max_iter = p.max_iter, a.tol_m = p.tol_m, a.mask_sin = p.mask_sin;
-    for (int i = 0; i < 3; ++i) a.init_xyz[i] = p.init_xyz[i];
+    const FixArgs a = fix_args(p, eph, tx_ms, tx_frac, rx_ms, rx_frac, weights, fixes, sat, resid, sin_el, used);
     GAT_HIP(c, launch_fix(a, p.groups, c->stream));
-    c->last = gat_launch_info{};
-    c->last.workgroups = (int32_t)p.groups;
-    c->last.threads = kFixThreads;
-    c->last.splits = 1;
-    c->last.ant_tile = 1;
-    c->last.vec = 1;
-    c->last.lds_bytes = kFixLdsBytes;
+    set_last_launch(c, p.groups, kFixThreads, 1, 1, kFixLdsBytes);
     return GAT_OK;
 }
 

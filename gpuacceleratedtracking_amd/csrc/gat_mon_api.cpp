@@ -69,13 +69,7 @@ GAT_API int32_t gat_track_monitor(gat_ctx *c, const float *acc_re, const float *
     if (p.g_energy) GAT_HIP(c, launch_mon_energies(a, p.g_energy, c->stream));
     if (p.g_pick) GAT_HIP(c, launch_mon_pick(a, p.g_pick, c->stream));
     if (p.g_symbol) GAT_HIP(c, launch_mon_symbols(a, p.g_symbol, c->stream));
-    c->last = gat_launch_info{};
-    c->last.workgroups = (int32_t)p.g_prompt;
-    c->last.threads = kMonThreads;
-    c->last.splits = 1;
-    c->last.ant_tile = p.M;
-    c->last.vec = 1;
-    c->last.lds_bytes = p.g_window ? (int32_t)(2 * kMonThreads * sizeof(double)) : 0;
+    set_last_launch(c, p.g_prompt, kMonThreads, 1, p.M, p.g_window ? (int32_t)(2 * kMonThreads * sizeof(double)) : 0);
     return GAT_OK;
 }
 

@@ -45,13 +45,7 @@ GAT_API int32_t gat_nav_decode(gat_ctx *c, const double *sym_re, const gat_monit
     if (p.g_score) GAT_HIP(c, launch_nav_score(a, p.g_score, c->stream));
     if (p.g_pick) GAT_HIP(c, launch_nav_pick(a, p.g_pick, c->stream));
     if (p.g_frame) GAT_HIP(c, launch_nav_frames(a, p.g_frame, c->stream));
-    c->last = gat_launch_info{};
-    c->last.workgroups = (int32_t)(p.g_trellis ? p.g_trellis : p.g_slice);
-    c->last.threads = p.g_trellis ? kNavWave : kNavThreads;
-    c->last.splits = 1;
-    c->last.ant_tile = 1;
-    c->last.vec = 1;
-    c->last.lds_bytes = 0;
+    set_last_launch(c, p.g_trellis ? p.g_trellis : p.g_slice, p.g_trellis ? kNavWave : kNavThreads, 1, 1, 0);
     return GAT_OK;
 }
 

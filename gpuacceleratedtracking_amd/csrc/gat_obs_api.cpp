@@ -7,8 +7,8 @@
 using namespace gat;
 
 // The sequence of gat_tracking_run (tracking_run_enqueue, gat_api.cpp) with the ping-pong pair replaced by the rows of one array:
-// block b is correlated with history + b K and its update writes history + (b + 1) K.  The update is the public entry point,
-// which with null weights is gat_tracking_update: the launches and the bits of the runs that keep two buffers.
+// block b is correlated with history + b K and its update writes history + (b + 1) K.  Its own checks and trace range; the same
+// launches and bits as the runs that keep two buffers.
 GAT_API int32_t gat_tracking_run_history(gat_ctx *c, const gat_signal_desc *sig, int32_t num_blocks, int32_t K, int32_t L, const int32_t *shifts,
                                          double fs, const gat_loop_config *cfg, gat_loop_state *state, gat_channel_params *history,
                                          float *acc_re, float *acc_im, int64_t acc_block_stride, uint32_t flags, const double *w_re,
@@ -21,20 +21,8 @@ GAT_API int32_t gat_tracking_run_history(gat_ctx *c, const gat_signal_desc *sig,
     if (flags & GAT_FLAG_GRAPH) return fail(c, GAT_ERR_ARG, "the history run is not replayed as a graph");
     if (flags & ~GAT_FLAG_ATOMIC) return fail(c, GAT_ERR_ARG, "unknown flag bits");
     GAT_ENTER(c, "gat_tracking_run_history");
-    const size_t sample_bytes = (size_t)layout_sample_bytes(sig->layout);
-    for (int32_t b = 0; b < num_blocks; ++b) { // everything is enqueued on the ctx stream, nothing synchronises
-        gat_signal_desc d = *sig;
-        const size_t off = (size_t)b * (size_t)sig->block_stride * sample_bytes;
-        d.re = static_cast<const char *>(sig->re) + off;
-        if (sig->im) d.im = static_cast<const char *>(sig->im) + off;
-        float *o_re = acc_re + (size_t)b * (size_t)acc_block_stride, *o_im = acc_im + (size_t)b * (size_t)acc_block_stride;
-        gat_channel_params *cur = history + (size_t)b * (size_t)K, *nxt = cur + K;
-        int32_t rc = correlate_impl(c, &d, cur, 1, K, L, shifts, fs, o_re, o_im, flags);
-        if (rc != GAT_OK) return rc;
-        rc = gat_tracking_update_weighted(c, o_re, o_im, K, sig->num_ants, cfg, state, cur, nxt, w_re, w_im);
-        if (rc != GAT_OK) return rc;
-    }
-    return GAT_OK;
+    return tracking_run_enqueue(c, sig, num_blocks, K, L, shifts, fs, cfg, state, LoopRecords{history, nullptr}, acc_re, acc_im, acc_block_stride,
+                                flags, w_re, w_im);
 }
 
 GAT_API int32_t gat_observables_plan(int32_t B, int32_t K, int32_t E, const gat_obs_config *cfg, gat_obs_plan *out)
@@ -73,13 +61,7 @@ GAT_API int32_t gat_observables(gat_ctx *c, const gat_channel_params *history, c
     a.chan = reinterpret_cast<ObsChan *>(scratch + p.off_chan);
     a.anchor = reinterpret_cast<ObsAnchor *>(scratch + p.off_anchor);
     GAT_HIP(c, launch_obs(a, p, c->stream));
-    c->last = gat_launch_info{};
-    c->last.workgroups = (int32_t)p.chunk_groups;
-    c->last.threads = kObsThreads;
-    c->last.splits = p.chunks;
-    c->last.ant_tile = 1;
-    c->last.vec = 1;
-    c->last.lds_bytes = kObsLdsBytes;
+    set_last_launch(c, p.chunk_groups, kObsThreads, p.chunks, 1, kObsLdsBytes);
     return GAT_OK;
 }
 

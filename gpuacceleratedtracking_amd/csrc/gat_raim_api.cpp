@@ -28,22 +28,12 @@ GAT_API int32_t gat_position_fix_raim(gat_ctx *c, const gat_ephemeris *eph, cons
     if (r.code != GAT_OK) return fail(c, r.code, r.msg);
     GAT_ENTER(c, "gat_position_fix_raim");
     RaimArgs a{};
-    FixArgs &f = a.fix;
-    f.eph = eph, f.tx_ms = tx_ms, f.tx_frac = tx_frac, f.rx_ms = rx_ms, f.rx_frac = rx_frac, f.w = weights;
-    f.fixes = fixes, f.sat = sat, f.resid = resid, f.sin_el = sin_el, f.used = used;
-    f.E = p.fix.E, f.K = p.fix.K, f.max_iter = p.fix.max_iter, f.tol_m = p.fix.tol_m, f.mask_sin = p.fix.mask_sin;
-    for (int i = 0; i < 3; ++i) f.init_xyz[i] = p.fix.init_xyz[i];
+    a.fix = fix_args(p.fix, eph, tx_ms, tx_frac, rx_ms, rx_frac, weights, fixes, sat, resid, sin_el, used);
     a.integrity = integrity, a.trial = trial;
     a.max_exclude = p.max_exclude, a.trial_iter = p.trial_iter;
     for (int d = 0; d < kRaimThresholds; ++d) a.threshold[d] = p.threshold[d];
     GAT_HIP(c, launch_raim(a, p.fix.groups, c->stream));
-    c->last = gat_launch_info{};
-    c->last.workgroups = (int32_t)p.fix.groups;
-    c->last.threads = kFixThreads;
-    c->last.splits = 1;
-    c->last.ant_tile = 1;
-    c->last.vec = 1;
-    c->last.lds_bytes = kRaimLdsBytes;
+    set_last_launch(c, p.fix.groups, kFixThreads, 1, 1, kRaimLdsBytes);
     return GAT_OK;
 }
 

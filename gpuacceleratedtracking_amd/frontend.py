@@ -19,6 +19,7 @@ import torch
 from . import _lib
 from ._lib import COND_PARAMS_DTYPE, GAT_COND_BLANK_ALL_ANTS, SAMPLE_STATS_DTYPE  # noqa: F401
 from .context import Context, get_context
+from .results import host_check
 from .streams import addr, alloc_stream, input_desc, keep_alive, output_desc, ref, vp
 from .streams import host_desc  # noqa: F401  (the name the host twins' docstrings point to)
 
@@ -109,8 +110,7 @@ def agc_params_host(stats: np.ndarray, target_rms: float, blank_factor: float = 
     out = np.zeros(st.size, dtype=COND_PARAMS_DTYPE)
     cfg = _agc_config(target_rms, blank_factor, remove_dc)
     rc = _lib.load().gat_agc_update_host(addr(st), st.size, C.byref(cfg), addr(out))
-    if rc != _lib.GAT_OK:
-        raise _lib.GatError(rc, "gat_agc_update_host")
+    host_check(rc, "gat_agc_update_host")
     return out
 
 

@@ -15,6 +15,7 @@ import torch
 from . import _lib
 from .context import Context, get_context
 from .gen_signal import make_params
+from .results import host_check
 from .signals import GNSSSystem, get_code_frequency
 from .streams import input_desc, signal_desc
 
@@ -254,8 +255,7 @@ class ResidentTrackingLoop:
         re, im = self.resident.correlate(self._cur, block_offset=start)
         rc = self._fn(C.c_void_p(re.ctypes.data), C.c_void_p(im.ctypes.data), self.K, self.M, C.byref(self.config),
                       C.c_void_p(self._state.ctypes.data), C.c_void_p(self._cur.ctypes.data), C.c_void_p(self._next.ctypes.data))
-        if rc != 0:
-            raise _lib.GatError(rc, "gat_tracking_update_host")
+        host_check(rc, "gat_tracking_update_host")
         self._cur, self._next = self._next, self._cur
         self.acc_re, self.acc_im = re, im
         self.blocks_done += 1

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from .context import Context, get_context
+from .results import PlannedResult, host_check, new_plan, plan_report
 from .streams import addr, keep_alive, vp
 
 NH10 = "0000110101"
@@ -58,31 +59,18 @@ def monitor_config(num_taps: int, prompt_index: int, window_blocks: int, overlay
     return cfg
 
 
-class TrackMonitor:
+class TrackMonitor(PlannedResult):
     """The monitor of one call.  Raw sums: ``windows`` (structured ``[K, NW]``: sum_p2, sum_p4, sum_d, sum_i, sum_q, blocks),
     ``energy`` ``[K, Pd]``, ``channels`` (structured ``[K]``), ``symbols`` complex ``[K, capacity]`` with ``wbp`` and ``num_symbols``
     ``[K]``, ``prompts`` complex ``[K, B]`` or None.  Derived: ``phase_lock``, ``cn0_m2m4`` ``[K, NW]``; ``symbol_offset`` (stream
     blocks, -1: none), ``start`` (the call's block of symbol 0), ``sync_ratio``, ``synced``, ``bits`` int8 ``[K, capacity]`` (0
     beyond ``num_symbols``), ``cn0_nwpr`` ``[K]``."""
 
-    def __init__(self, raw: dict, block_seconds: float, symbol_blocks: int, min_sync_ratio: float, ctx: Context | None = None):
-        self._raw, self._host, self._ctx = raw, None, ctx
-        self.block_seconds, self.symbol_blocks, self.min_sync_ratio = float(block_seconds), int(symbol_blocks), float(min_sync_ratio)
+    _VIEWS = {"windows": (_lib.MONITOR_WINDOW_DTYPE, True), "channels": (_lib.MONITOR_CHANNEL_DTYPE, False)}
 
-    def _h(self) -> dict:
-        if self._host is None:
-            if self._ctx is not None:
-                self._ctx.sync()
-            host = {}
-            for name, v in self._raw.items():
-                a = v.cpu().numpy() if isinstance(v, torch.Tensor) else v
-                if name == "windows":
-                    a = a.view(_lib.MONITOR_WINDOW_DTYPE).reshape(a.shape[0], -1)
-                elif name == "channels":
-                    a = a.view(_lib.MONITOR_CHANNEL_DTYPE).reshape(-1)
-                host[name] = a
-            self._host = host
-        return self._host
+    def __init__(self, raw: dict, block_seconds: float, symbol_blocks: int, min_sync_ratio: float, ctx: Context | None = None):
+        super().__init__(raw, ctx)
+        self.block_seconds, self.symbol_blocks, self.min_sync_ratio = float(block_seconds), int(symbol_blocks), float(min_sync_ratio)
 
     # ---- raw sums
     windows = property(lambda self: self._h()["windows"])
@@ -233,8 +221,7 @@ def monitor_accumulators_host(acc_re, acc_im, *, block_seconds: float, prompt_in
     rc = _lib.load().gat_track_monitor_host(addr(acc_re), addr(acc_im), stride, B, K, M, C.byref(cfg), addr(w_re), addr(w_im),
                                             addr(raw.get("prompt_re")), addr(raw.get("prompt_im")), addr(raw["windows"]), addr(raw["energy"]),
                                             addr(raw["channels"]), addr(raw["sym_re"]), addr(raw["sym_im"]), addr(raw["sym_wbp"]))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_track_monitor_host")
+    host_check(rc, "gat_track_monitor_host")
     return TrackMonitor(raw, block_seconds, Pd, min_sync_ratio)
 
 
@@ -244,10 +231,8 @@ def monitor_plan(num_blocks: int, num_channels: int, num_ants: int, num_taps: in
     """``gat_track_monitor_plan``: the counts, the scratch bytes and the workgroups of each kernel of such a call."""
     cfg = monitor_config(num_taps, prompt_index, window_blocks, overlay, symbol_offset, first_block)
     stride = int(num_channels) * int(num_taps) * int(num_ants) if acc_block_stride is None else int(acc_block_stride)
-    plan = _lib.MonitorPlan()
-    plan.struct_size = C.sizeof(_lib.MonitorPlan)
+    plan = new_plan(_lib.MonitorPlan)
     rc = _lib.load().gat_track_monitor_plan(stride, int(num_blocks), int(num_channels), int(num_ants), C.byref(cfg), int(own_prompts),
                                             int(want_symbols), C.byref(plan))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_track_monitor_plan")
-    return {n: int(getattr(plan, n)) for n, _ in _lib.MonitorPlan._fields_ if n != "struct_size"}
+    host_check(rc, "gat_track_monitor_plan")
+    return plan_report(plan)

@@ -22,6 +22,7 @@ import torch
 from . import _lib
 from .context import Context, get_context
 from .monitor import TrackMonitor
+from .results import PlannedResult, host_check, new_plan, plan_report
 from .streams import addr, keep_alive, vp
 
 LNAV, CNAV = _lib.GAT_NAV_LNAV, _lib.GAT_NAV_CNAV
@@ -61,7 +62,7 @@ def nav_config(fmt, symbol_capacity: int, max_frames: int | None, min_frames: in
     return cfg
 
 
-class NavResult:
+class NavResult(PlannedResult):
     """The decoder's outputs of one call.  Raw: ``channels`` (structured ``[K]``: frame_offset, symbol_phase, inverted, score,
     second_score, num_frames, num_bits, tow_steps), ``frames`` (structured ``[K, max_frames]``: status, tow, id, prn, words),
     ``decoded`` uint8 ``[K, P, bit_capacity]`` (every phase, before the polarity), ``path_metric`` int32 ``[K, P]``.  Derived:
@@ -69,23 +70,11 @@ class NavResult:
     ``words``, ``tow``, ``subframe_id`` / ``message_type``, ``prn``, ``status``, ``ok`` ``[K, max_frames]``; ``bits``: a list of the
     channels' bits of the chosen phase with the polarity undone."""
 
-    def __init__(self, raw: dict, fmt: int, ctx: Context | None = None):
-        self._raw, self._host, self._ctx, self.format = raw, None, ctx, int(fmt)
+    _VIEWS = {"channels": (_lib.NAV_CHANNEL_DTYPE, False), "frames": (_lib.NAV_FRAME_DTYPE, True)}
 
-    def _h(self) -> dict:
-        if self._host is None:
-            if self._ctx is not None:
-                self._ctx.sync()
-            host = {}
-            for name, v in self._raw.items():
-                a = v.cpu().numpy() if isinstance(v, torch.Tensor) else v
-                if name == "channels":
-                    a = a.view(_lib.NAV_CHANNEL_DTYPE).reshape(-1)
-                elif name == "frames":
-                    a = a.view(_lib.NAV_FRAME_DTYPE).reshape(a.shape[0], -1)
-                host[name] = a
-            self._host = host
-        return self._host
+    def __init__(self, raw: dict, fmt: int, ctx: Context | None = None):
+        super().__init__(raw, ctx)
+        self.format = int(fmt)
 
     channels = property(lambda self: self._h()["channels"])
     frames = property(lambda self: self._h()["frames"])
@@ -181,20 +170,17 @@ def decode_navigation_host(mon_or_sym_re, format=None, *, channels=None, max_fra
            "decoded": np.zeros((K, P, cap // P), dtype=np.uint8), "path_metric": np.zeros((K, P), dtype=np.int32)}
     rc = _lib.load().gat_nav_decode_host(addr(sym), addr(recs), K, C.byref(cfg), addr(raw["channels"]), addr(raw["frames"]),
                                          addr(raw["decoded"]), addr(raw["path_metric"]))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_nav_decode_host")
+    host_check(rc, "gat_nav_decode_host")
     return NavResult(raw, fmt)
 
 
 def nav_plan(num_channels: int, symbol_capacity: int, format, max_frames: int | None = None, min_frames: int = 1) -> dict:
     """``gat_nav_decode_plan``: the counts, the scratch bytes and the workgroups of each kernel of such a call."""
     cfg = nav_config(format, symbol_capacity, max_frames, min_frames)
-    plan = _lib.NavPlan()
-    plan.struct_size = C.sizeof(_lib.NavPlan)
+    plan = new_plan(_lib.NavPlan)
     rc = _lib.load().gat_nav_decode_plan(int(num_channels), C.byref(cfg), C.byref(plan))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_nav_decode_plan")
-    return {n: int(getattr(plan, n)) for n, _ in _lib.NavPlan._fields_ if n != "struct_size"}
+    host_check(rc, "gat_nav_decode_plan")
+    return plan_report(plan)
 
 
 # ---- encoders: what a simulation sends ---------------------------------------------------------------------------------------------

@@ -22,6 +22,7 @@ from . import _lib
 from .context import Context, get_context
 from .monitor import TrackMonitor
 from .navigation import NavResult, _format
+from .results import PlannedResult, host_check, new_plan, plan_report, wanted
 from .streams import addr, keep_alive, vp
 
 BAD_RECORD, NO_BIT_SYNC, NO_FRAME_SYNC = _lib.GAT_OBS_BAD_RECORD, _lib.GAT_OBS_NO_BIT_SYNC, _lib.GAT_OBS_NO_FRAME_SYNC
@@ -52,26 +53,12 @@ def obs_config(*, format, code_length: int, code_freq_nominal_hz: float, block_s
     return cfg
 
 
-class Observables:
+class Observables(PlannedResult):
     """The outputs of one call: the arrays that were asked for, as the call wrote them (device tensors of the device call, numpy
     arrays of the host twin) and, derived from ``channels`` on the host, ``status``, ``frame_block``, ``tow_frame``, ``frame0_ms``,
     ``edge_period``, ``edge_fraction`` ``[K]`` and ``measured``."""
 
-    def __init__(self, raw: dict, ctx: Context | None = None):
-        self._raw, self._host, self._ctx = raw, None, ctx
-
-    def _h(self) -> dict:
-        if self._host is None:
-            if self._ctx is not None:
-                self._ctx.sync()
-            host = {}
-            for name, v in self._raw.items():
-                a = v.cpu().numpy() if isinstance(v, torch.Tensor) else v
-                if name == "channels":
-                    a = a.view(_lib.OBS_CHANNEL_DTYPE).reshape(-1)
-                host[name] = a
-            self._host = host
-        return self._host
+    _VIEWS = {"channels": (_lib.OBS_CHANNEL_DTYPE, False)}
 
     def host(self, name: str) -> np.ndarray:
         """output ``name`` as a numpy array (synchronises a device call once)"""
@@ -90,14 +77,6 @@ class Observables:
     @property
     def measured(self) -> np.ndarray:
         return (self.channels["status"] & ~EDGE_AMBIGUOUS) == 0
-
-
-def _wanted(outputs) -> tuple:
-    outputs = OUTPUTS if outputs is None else tuple(outputs)
-    unknown = set(outputs) - set(OUTPUTS)
-    if unknown:
-        raise ValueError(f"unknown outputs {sorted(unknown)}: choose from {OUTPUTS}")
-    return outputs
 
 
 def _loop_config(loop, mon, config: dict) -> dict:
@@ -130,7 +109,7 @@ def observables(history: torch.Tensor, mon, nav, *, loop=None, epoch_first: int 
     ``(channels, frames)`` device tensors -- all passed as they are.  ``loop=`` fills block_seconds, block_samples,
     sampling_freq_hz, code_length, code_freq_nominal_hz, if_hz and the format; a monitor fills symbol_blocks; ``config`` takes the
     rest of ``obs_config``.  ``num_epochs`` None: every epoch up to record B.  Enqueues on the context's stream and returns at once."""
-    want = _wanted(outputs)
+    want = wanted(outputs, OUTPUTS, OUTPUTS)
     if not isinstance(history, torch.Tensor) or history.dtype != torch.uint8 or history.dim() != 3 or history.shape[2] != 40 or not history.is_contiguous():
         raise ValueError("history must be a contiguous uint8 device tensor [B + 1, K, 40]")
     B, K, dev = int(history.shape[0]) - 1, int(history.shape[1]), history.device
@@ -171,7 +150,7 @@ def observables_host(history, mon, nav, *, loop=None, epoch_first: int = 0, epoc
     """``gat_observables_host``: the same rule and the same bits over numpy arrays; needs no device.  ``history``: a structured
     ``[B + 1, K]`` array of ``gat_channel_params`` (or uint8 ``[B + 1, K, 40]``); ``mon``: a ``TrackMonitor`` or its records; ``nav``: a
     ``NavResult`` or ``(channels, frames [K, max_frames])``."""
-    want = _wanted(outputs)
+    want = wanted(outputs, OUTPUTS, OUTPUTS)
     history = np.ascontiguousarray(history)
     if history.dtype != _lib.PARAMS_DTYPE:
         history = history.view(_lib.PARAMS_DTYPE).reshape(history.shape[0], -1)
@@ -199,8 +178,7 @@ def observables_host(history, mon, nav, *, loop=None, epoch_first: int = 0, epoc
             raw[name] = np.zeros(_shape(name, max(E, 0), K), dtype=_DTYPES.get(name, (None, np.float64))[1])
     rc = _lib.load().gat_observables_host(addr(history), addr(mon_recs), addr(nav_chan), addr(nav_frames), B, K, E, C.byref(cfg),
                                           *[addr(raw.get(n)) for n in OUTPUTS])
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_observables_host")
+    host_check(rc, "gat_observables_host")
     return Observables(raw)
 
 
@@ -210,10 +188,8 @@ def observables_plan(num_blocks: int, num_channels: int, num_epochs: int | None 
     scratch bytes of such a call."""
     config = _loop_config(loop, None, dict(config))
     cfg = obs_config(epoch_first=epoch_first, epoch_stride=epoch_stride, rx=rx, **config)
-    plan = _lib.ObsPlan()
-    plan.struct_size = C.sizeof(_lib.ObsPlan)
+    plan = new_plan(_lib.ObsPlan)
     E = _epochs(int(num_blocks), epoch_first, epoch_stride, num_epochs)
     rc = _lib.load().gat_observables_plan(int(num_blocks), int(num_channels), E, C.byref(cfg), C.byref(plan))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_observables_plan")
-    return {n: int(getattr(plan, n)) for n, _ in _lib.ObsPlan._fields_ if n != "struct_size"}
+    host_check(rc, "gat_observables_plan")
+    return plan_report(plan)

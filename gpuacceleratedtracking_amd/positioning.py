@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from .context import Context, get_context
 from .navigation import NavResult
+from .results import PlannedResult, host_check, new_plan, plan_report, wanted
 from .streams import addr, keep_alive, vp
 
 FEW_SATS, SINGULAR, NONFINITE = _lib.GAT_FIX_FEW_SATS, _lib.GAT_FIX_SINGULAR, _lib.GAT_FIX_NONFINITE
@@ -82,8 +83,7 @@ def lnav_ephemeris(nav: NavResult, channel: int) -> Ephemeris:
     frames = np.ascontiguousarray(nav.frames[int(channel)])
     rec = np.zeros((), dtype=_lib.EPHEMERIS_DTYPE)
     rc = _lib.load().gat_lnav_ephemeris_host(addr(frames), int(frames.shape[0]), addr(rec))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_lnav_ephemeris_host")
+    host_check(rc, "gat_lnav_ephemeris_host")
     return Ephemeris.from_record(rec)
 
 
@@ -98,8 +98,7 @@ def lnav_ephemeris_payloads(eph: Ephemeris) -> np.ndarray:
     bits = np.zeros((3, 190), dtype=np.uint8)
     rec = np.ascontiguousarray(eph.record)
     rc = _lib.load().gat_lnav_ephemeris_words_host(addr(rec), addr(bits))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_lnav_ephemeris_words_host")
+    host_check(rc, "gat_lnav_ephemeris_words_host")
     return bits
 
 
@@ -113,30 +112,14 @@ def fix_config(max_iter: int = 10, tol_m: float = 1e-4, mask_sin: float = -1.0, 
     return cfg
 
 
-class PositionFix:
+class PositionFix(PlannedResult):
     """The outputs of one call.  Raw: ``fixes`` (structured ``[E]``: status, num_valid, num_used, iterations, x, y, z, clock_bias_s,
     rms_residual_m, last_step_m, gdop, pdop) and, where asked for, ``sat`` ``[E, K, 4]`` (ECEF at transmission and the clock
     correction), ``resid`` and ``sin_el`` ``[E, K]``, ``used`` uint8 ``[E, K]``.  Derived: every field of ``fixes`` ``[E]``, ``xyz``
     ``[E, 3]`` and ``ok`` (status 0).  Of ``position_fix_raim``: ``integrity`` (structured ``[E]``), ``excluded`` ``[E, 4]``,
     ``detected`` ``[E]`` and, where asked for, ``trial`` ``[E, K]``."""
 
-    def __init__(self, raw: dict, ctx: Context | None = None):
-        self._raw, self._host, self._ctx = raw, None, ctx
-
-    def _h(self) -> dict:
-        if self._host is None:
-            if self._ctx is not None:
-                self._ctx.sync()
-            host = {}
-            for name, v in self._raw.items():
-                a = v.cpu().numpy() if isinstance(v, torch.Tensor) else v
-                if name == "fixes":
-                    a = a.view(_lib.FIX_DTYPE).reshape(-1)
-                if name == "integrity":
-                    a = a.view(_lib.INTEGRITY_DTYPE).reshape(-1)
-                host[name] = a
-            self._host = host
-        return self._host
+    _VIEWS = {"fixes": (_lib.FIX_DTYPE, False), "integrity": (_lib.INTEGRITY_DTYPE, False)}
 
     def __getattr__(self, name):
         if name in _lib.FIX_DTYPE.names:
@@ -166,14 +149,6 @@ class PositionFix:
     def xyz(self) -> np.ndarray:
         f = self.fixes
         return np.stack([f["x"], f["y"], f["z"]], axis=1)
-
-
-def _wanted(outputs, known: tuple = OUTPUTS) -> tuple:
-    outputs = OUTPUTS if outputs is None else tuple(outputs)
-    unknown = set(outputs) - set(known)
-    if unknown:
-        raise ValueError(f"unknown outputs {sorted(unknown)}: choose from {known}")
-    return outputs
 
 
 _SHAPES = {"sat": (4,), "resid": (), "sin_el": (), "used": (), "trial": ()}
@@ -207,11 +182,46 @@ def _device_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights):
     return E, K, dev, eph_dev
 
 
-def _device_outputs(want: tuple, E: int, K: int, dev) -> dict:
+def _device_fix(raim, ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights, outputs, ctx, config) -> PositionFix:
+    """the device call of both: ``raim`` None is ``gat_position_fix``, else ``_raim_setup``'s arguments after the weights"""
+    want = wanted(outputs, OUTPUTS if raim is None else RAIM_OUTPUTS, OUTPUTS)
+    E, K, dev, eph_dev = _device_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+    if ctx is None:
+        ctx = get_context(dev)
+    cfg = fix_config(**config)
     raw = {"fixes": torch.empty((E, _lib.FIX_DTYPE.itemsize), dtype=torch.uint8, device=dev)}
     for name in want:
         raw[name] = torch.empty((E, K) + _SHAPES[name], dtype=torch.uint8 if name == "used" else torch.float64, device=dev)
-    return raw
+    call = (ctx._h, vp(eph_dev), vp(tx_ms), vp(tx_frac), vp(rx_ms), vp(rx_frac), vp(weights), E, K, C.byref(cfg))
+    outs = [vp(raw.get(n)) for n in OUTPUTS]
+    if raim is None:
+        ctx.check(ctx.lib.gat_position_fix(*call, vp(raw["fixes"]), *outs), "gat_position_fix")
+    else:
+        rcfg = _raim_setup(weights, *raim)
+        raw["integrity"] = torch.empty((E, _lib.INTEGRITY_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        ctx.check(ctx.lib.gat_position_fix_raim(*call, C.byref(rcfg), vp(raw["fixes"]), vp(raw["integrity"]), *outs, vp(raw.get("trial"))),
+                  "gat_position_fix_raim")
+    return keep_alive(PositionFix(raw, ctx), eph_dev, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+
+
+def _host_fix(raim, ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights, outputs, config) -> PositionFix:
+    """the host twin of both, as ``_device_fix``"""
+    want = wanted(outputs, OUTPUTS if raim is None else RAIM_OUTPUTS, OUTPUTS)
+    recs, tx_ms, tx_frac, rx_ms, rx_frac, weights, E, K = _host_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+    cfg = fix_config(**config)
+    raw = {"fixes": np.zeros(E, dtype=_lib.FIX_DTYPE)}
+    for name in want:
+        raw[name] = np.zeros((E, K) + _SHAPES[name], dtype=np.uint8 if name == "used" else np.float64)
+    call = (addr(recs), addr(tx_ms), addr(tx_frac), addr(rx_ms), addr(rx_frac), addr(weights), E, K, C.byref(cfg))
+    outs = [addr(raw.get(n)) for n in OUTPUTS]
+    if raim is None:
+        host_check(_lib.load().gat_position_fix_host(*call, addr(raw["fixes"]), *outs), "gat_position_fix_host")
+    else:
+        rcfg = _raim_setup(weights, *raim)
+        raw["integrity"] = np.zeros(E, dtype=_lib.INTEGRITY_DTYPE)
+        host_check(_lib.load().gat_position_fix_raim_host(*call, C.byref(rcfg), addr(raw["fixes"]), addr(raw["integrity"]), *outs,
+                                                          addr(raw.get("trial"))), "gat_position_fix_raim_host")
+    return PositionFix(raw)
 
 
 def position_fix(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, outputs=None, ctx: Context | None = None, **config) -> PositionFix:
@@ -219,30 +229,12 @@ def position_fix(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, outputs=
     ``tx_ms`` int32 and ``tx_frac`` float64 ``[E, K]``, ``rx_ms`` int32 and ``rx_frac`` float64 ``[E]``, ``weights`` float64 ``[E, K]``
     or None: contiguous device tensors, passed as they are.  ``outputs``: which of "sat", "resid", "sin_el", "used" to write (None:
     all).  ``config``: ``max_iter``, ``tol_m``, ``mask_sin``, ``init_xyz``.  Enqueues on the context's stream and returns at once."""
-    want = _wanted(outputs)
-    E, K, dev, eph_dev = _device_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights)
-    if ctx is None:
-        ctx = get_context(dev)
-    cfg = fix_config(**config)
-    raw = _device_outputs(want, E, K, dev)
-    rc = ctx.lib.gat_position_fix(ctx._h, vp(eph_dev), vp(tx_ms), vp(tx_frac), vp(rx_ms), vp(rx_frac), vp(weights), E, K, C.byref(cfg),
-                                  vp(raw["fixes"]), vp(raw.get("sat")), vp(raw.get("resid")), vp(raw.get("sin_el")), vp(raw.get("used")))
-    ctx.check(rc, "gat_position_fix")
-    return keep_alive(PositionFix(raw, ctx), eph_dev, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+    return _device_fix(None, ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights, outputs, ctx, config)
 
 
 def position_fix_host(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, outputs=None, **config) -> PositionFix:
     """``gat_position_fix_host``: the same rule and the same bits over numpy arrays; needs no device."""
-    want = _wanted(outputs)
-    recs, tx_ms, tx_frac, rx_ms, rx_frac, weights, E, K = _host_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights)
-    cfg = fix_config(**config)
-    raw = _host_outputs(want, E, K)
-    rc = _lib.load().gat_position_fix_host(addr(recs), addr(tx_ms), addr(tx_frac), addr(rx_ms), addr(rx_frac), addr(weights), E, K,
-                                           C.byref(cfg), addr(raw["fixes"]), addr(raw.get("sat")), addr(raw.get("resid")),
-                                           addr(raw.get("sin_el")), addr(raw.get("used")))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_position_fix_host")
-    return PositionFix(raw)
+    return _host_fix(None, ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights, outputs, config)
 
 
 def _host_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights):
@@ -262,22 +254,13 @@ def _host_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights):
     return recs, tx_ms, tx_frac, rx_ms, rx_frac, weights, int(E), int(K)
 
 
-def _host_outputs(want: tuple, E: int, K: int) -> dict:
-    raw = {"fixes": np.zeros(E, dtype=_lib.FIX_DTYPE)}
-    for name in want:
-        raw[name] = np.zeros((E, K) + _SHAPES[name], dtype=np.uint8 if name == "used" else np.float64)
-    return raw
-
-
 def position_plan(num_epochs: int, num_channels: int, **config) -> dict:
     """``gat_position_fix_plan``: the workgroups, the waves (epochs) of each, its threads and LDS, and the scratch bytes of such a call."""
     cfg = fix_config(**config)
-    plan = _lib.FixPlan()
-    plan.struct_size = C.sizeof(_lib.FixPlan)
+    plan = new_plan(_lib.FixPlan)
     rc = _lib.load().gat_position_fix_plan(int(num_epochs), int(num_channels), C.byref(cfg), C.byref(plan))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_position_fix_plan")
-    return {n: int(getattr(plan, n)) for n, _ in _lib.FixPlan._fields_ if n not in ("struct_size", "reserved")}
+    host_check(rc, "gat_position_fix_plan")
+    return plan_report(plan)
 
 
 # ---- fix integrity (include/gat.h, "fix integrity") -------------------------------------------------------------------------------
@@ -374,36 +357,14 @@ def position_fix_raim(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, thr
     sigma_m)`` -- with ``weights`` = 1 / sigma^2 leave ``sigma_m`` unset, without weights it is required), ``max_exclude`` rounds of
     exclusion (0: detect only), ``trial_iter`` iterations a leave-one-out trial.  ``outputs`` may also name "trial" (None: the fix's
     four).  The result also has ``integrity``, ``excluded``, ``detected`` and, where asked for, ``trial``."""
-    want = _wanted(outputs, RAIM_OUTPUTS)
-    E, K, dev, eph_dev = _device_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights)
-    if ctx is None:
-        ctx = get_context(dev)
-    cfg = fix_config(**config)
-    rcfg = _raim_setup(weights, thresholds, p_fa, sigma_m, max_exclude, trial_iter, raim_flags)
-    raw = _device_outputs(want, E, K, dev)
-    raw["integrity"] = torch.empty((E, _lib.INTEGRITY_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    rc = ctx.lib.gat_position_fix_raim(ctx._h, vp(eph_dev), vp(tx_ms), vp(tx_frac), vp(rx_ms), vp(rx_frac), vp(weights), E, K, C.byref(cfg),
-                                       C.byref(rcfg), vp(raw["fixes"]), vp(raw["integrity"]), vp(raw.get("sat")), vp(raw.get("resid")),
-                                       vp(raw.get("sin_el")), vp(raw.get("used")), vp(raw.get("trial")))
-    ctx.check(rc, "gat_position_fix_raim")
-    return keep_alive(PositionFix(raw, ctx), eph_dev, tx_ms, tx_frac, rx_ms, rx_frac, weights)
+    return _device_fix((thresholds, p_fa, sigma_m, max_exclude, trial_iter, raim_flags), ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights, outputs, ctx,
+                       config)
 
 
 def position_fix_raim_host(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights=None, *, thresholds=None, p_fa: float = 1e-3, sigma_m=None,
                            max_exclude: int = 1, trial_iter: int = 8, raim_flags: int = 0, outputs=None, **config) -> PositionFix:
     """``gat_position_fix_raim_host``: the same rule and the same bits over numpy arrays; needs no device."""
-    want = _wanted(outputs, RAIM_OUTPUTS)
-    recs, tx_ms, tx_frac, rx_ms, rx_frac, weights, E, K = _host_args(ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights)
-    cfg = fix_config(**config)
-    rcfg = _raim_setup(weights, thresholds, p_fa, sigma_m, max_exclude, trial_iter, raim_flags)
-    raw = _host_outputs(want, E, K)
-    raw["integrity"] = np.zeros(E, dtype=_lib.INTEGRITY_DTYPE)
-    rc = _lib.load().gat_position_fix_raim_host(addr(recs), addr(tx_ms), addr(tx_frac), addr(rx_ms), addr(rx_frac), addr(weights), E, K,
-                                                C.byref(cfg), C.byref(rcfg), addr(raw["fixes"]), addr(raw["integrity"]), addr(raw.get("sat")),
-                                                addr(raw.get("resid")), addr(raw.get("sin_el")), addr(raw.get("used")), addr(raw.get("trial")))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_position_fix_raim_host")
-    return PositionFix(raw)
+    return _host_fix((thresholds, p_fa, sigma_m, max_exclude, trial_iter, raim_flags), ephs, tx_ms, tx_frac, rx_ms, rx_frac, weights, outputs, config)
 
 
 def raim_plan(num_epochs: int, num_channels: int, *, thresholds=None, p_fa: float = 1e-3, sigma_m: float = 1.0, max_exclude: int = 1,
@@ -411,9 +372,7 @@ def raim_plan(num_epochs: int, num_channels: int, *, thresholds=None, p_fa: floa
     """``gat_position_fix_raim_plan``: ``position_plan``'s report for such a call (the LDS holds a round's frozen channels too)."""
     cfg = fix_config(**config)
     rcfg = _raim_setup(None, thresholds, p_fa, sigma_m, max_exclude, trial_iter, raim_flags)
-    plan = _lib.FixPlan()
-    plan.struct_size = C.sizeof(_lib.FixPlan)
+    plan = new_plan(_lib.FixPlan)
     rc = _lib.load().gat_position_fix_raim_plan(int(num_epochs), int(num_channels), C.byref(cfg), C.byref(rcfg), C.byref(plan))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_position_fix_raim_plan")
-    return {n: int(getattr(plan, n)) for n, _ in _lib.FixPlan._fields_ if n not in ("struct_size", "reserved")}
+    host_check(rc, "gat_position_fix_raim_plan")
+    return plan_report(plan)

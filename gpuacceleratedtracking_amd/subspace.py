@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from .context import Context, get_context
+from .results import host_check, new_plan, plan_report
 from .streams import addr, keep_alive, planes, vp
 
 
@@ -78,8 +79,7 @@ def accumulator_covariance_host(acc_re, acc_im, *, tap_index: int, blocks_per_es
     bpe, E = _estimates(B, blocks_per_estimate)
     cov_re, cov_im = np.zeros((E, K, M, M)), np.zeros((E, K, M, M))
     rc = _lib.load().gat_accumulator_covariance_host(addr(acc_re), addr(acc_im), stride, B, K, L, M, int(tap_index), bpe, addr(cov_re), addr(cov_im))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_accumulator_covariance_host")
+    host_check(rc, "gat_accumulator_covariance_host")
     return _complex(cov_re, cov_im)
 
 
@@ -127,8 +127,7 @@ def hermitian_eig_host(cov, num_vectors: int | None = None):
     status = np.zeros(lead, dtype=np.int32)
     rc = _lib.load().gat_hermitian_eig_host(addr(a_re), addr(a_im), n, Q, R, _lib.GAT_EIG_INPUT_F32 if f32 else 0, addr(lam), addr(v_re), addr(v_im),
                                             addr(status))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_hermitian_eig_host")
+    host_check(rc, "gat_hermitian_eig_host")
     return lam, _complex(v_re, v_im), status
 
 
@@ -156,14 +155,12 @@ def subspace_plan(num_blocks: int = 0, num_channels: int = 1, num_taps: int = 1,
     """``gat_subspace_plan``: the estimates, the chunks, the work split, the scratch bytes and the workgroups of
     ``accumulator_covariance`` (``num_blocks`` > 0) and of ``hermitian_eig`` (``eig_matrices`` > 0) for such calls."""
     stride = int(num_channels) * int(num_taps) * int(num_ants) if acc_block_stride is None else int(acc_block_stride)
-    plan = _lib.SubspacePlan()
-    plan.struct_size = C.sizeof(_lib.SubspacePlan)
+    plan = new_plan(_lib.SubspacePlan)
     rc = _lib.load().gat_subspace_plan(stride, int(num_blocks), int(num_channels), int(num_taps), int(num_ants), int(tap_index),
                                        0 if blocks_per_estimate is None else int(blocks_per_estimate), int(eig_matrices), int(eig_order),
                                        int(eig_order) if eig_vectors is None else int(eig_vectors), C.byref(plan))
-    if rc != 0:
-        raise _lib.GatError(rc, "gat_subspace_plan")
-    return {n: int(getattr(plan, n)) for n, _ in _lib.SubspacePlan._fields_ if n not in ("struct_size", "reserved")}
+    host_check(rc, "gat_subspace_plan")
+    return plan_report(plan)
 
 
 def source_count(eigenvalues, num_snapshots: int, method: str = "mdl"):
