@@ -40,6 +40,7 @@ from .spacetime import (spacetime_covariance, spacetime_delay, spacetime_filter,
 from .signals import GNSSDICT, GPSL1, GPSL5, generate_codes, get_code_frequency, get_code_length  # noqa: F401
 from .subspace import (accumulator_covariance, accumulator_covariance_host, hermitian_eig, hermitian_eig_host, source_count,  # noqa: F401
                        steering_from_accumulators, subspace_plan)
+from .velocity import VelocityFix, velocity_fix, velocity_fix_host, velocity_plan  # noqa: F401
 from .tracking import (StreamCorrelator, downconvert_and_accumulate_strided, downconvert_and_correlate,  # noqa: F401
                        gen_code_replica, gen_code_replica_nsat, reduce_cplx_multi)
 

@@ -50,6 +50,8 @@ GAT_OBS_RX_GIVEN, GAT_OBS_RX_FROM_TX = 0, 1
 # fix integrity (the status bits of gat_fix_integrity, the bit gat_position_fix_raim adds to gat_fix.status, the rounds' limit)
 GAT_RAIM_NOT_CHECKED, GAT_RAIM_NO_REDUNDANCY, GAT_RAIM_DETECTED, GAT_RAIM_EXCLUDED, GAT_RAIM_UNRESOLVED = 1, 2, 4, 8, 16
 GAT_FIX_EXCLUDED, GAT_RAIM_MAX_EXCLUDE = 64, 4
+# velocity fix (the status bits of gat_velocity)
+GAT_VEL_FEW_SATS, GAT_VEL_SINGULAR, GAT_VEL_NONFINITE, GAT_VEL_NO_FIX, GAT_VEL_NO_GEODETIC = 1, 2, 4, 8, 16
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -94,6 +96,8 @@ EXPORTS = [
     "gat_tracking_run_history", "gat_observables", "gat_observables_host", "gat_observables_plan",
     # fix integrity: the residual test and fault exclusion on top of the position fix
     "gat_position_fix_raim", "gat_position_fix_raim_host", "gat_position_fix_raim_plan",
+    # velocity fix: satellite velocities, the Doppler solver and the local frame
+    "gat_velocity_fix", "gat_velocity_fix_host", "gat_velocity_fix_plan",
 ]
 
 
@@ -340,6 +344,19 @@ INTEGRITY_DTYPE = np.dtype([("status", "<i4"), ("dof", "<i4"), ("num_excluded", 
 assert C.sizeof(RaimConfig) == 504 and INTEGRITY_DTYPE.itemsize == 64
 
 
+class VelConfig(C.Structure):
+    """gat_vel_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("carrier_hz", C.c_double)]
+
+
+# gat_velocity (include/gat.h)
+VELOCITY_DTYPE = np.dtype([("status", "<i4"), ("num_valid", "<i4"), ("num_used", "<i4"), ("reserved", "<i4")]
+                          + [(n, "<f8") for n in ("vx", "vy", "vz", "clock_drift", "rms_residual_mps", "ve", "vn", "vu", "sin_lat", "cos_lat",
+                                                  "sin_lon", "cos_lon", "height_m")])
+assert C.sizeof(VelConfig) == 16 and VELOCITY_DTYPE.itemsize == 120
+
+
 _LIB = None
 
 
@@ -472,6 +489,9 @@ def load(build_if_missing: bool = True):
         "gat_position_fix_raim": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(FixConfig), C.POINTER(RaimConfig)] + [vp] * 7),
         "gat_position_fix_raim_host": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(FixConfig), C.POINTER(RaimConfig)] + [vp] * 7),
         "gat_position_fix_raim_plan": (i32, [i32, i32, C.POINTER(FixConfig), C.POINTER(RaimConfig), C.POINTER(FixPlan)]),
+        "gat_velocity_fix": (i32, [vp] * 8 + [i32, i32, C.POINTER(VelConfig), vp, vp, vp]),
+        "gat_velocity_fix_host": (i32, [vp] * 7 + [i32, i32, C.POINTER(VelConfig), vp, vp, vp]),
+        "gat_velocity_fix_plan": (i32, [i32, i32, C.POINTER(VelConfig), C.POINTER(FixPlan)]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

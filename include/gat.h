@@ -1628,6 +1628,87 @@ GAT_API int32_t gat_position_fix_raim_host(const gat_ephemeris *eph_host, const 
 GAT_API int32_t gat_position_fix_raim_plan(int32_t num_epochs, int32_t num_channels, const gat_fix_config *config,
                                            const gat_raim_config *raim, gat_fix_plan *plan);
 
+/* ---- velocity fix: satellite velocities, a Doppler solver and the local frame ------------------------------------------------
+ * From the ephemerides, the times of transmission, gat_observables' doppler_hz and the fixes of gat_position_fix or
+ * gat_position_fix_raim: per epoch the receiver's ECEF velocity and clock drift by one weighted least-squares solve, the same
+ * velocity as east / north / up, and the geodetic frame it was turned into.  The arithmetic is the position fix's (FP64, no
+ * contraction, no libm transcendental, every sum in channel order from +0: csrc/gat_vel.h on top of csrc/gat_fix.h, shared by
+ * the kernel and the host twin: the same bits).
+ *   satellite the position fix's clock and orbit, the same expressions in the same order (X, Y, Z and dts have its bits), and
+ *            from the sines and cosines they hold the rates: Edot = n / (1 - e cos E); nudot = Edot sqrt(1 - e^2) / (1 - e cos
+ *            E); udot = nudot + 2 nudot (cus cos 2Phi - cuc sin 2Phi); rdot = A e sin E Edot + 2 nudot (crs cos 2Phi - crc sin
+ *            2Phi); idot_k = idot + 2 nudot (cis cos 2Phi - cic sin 2Phi); Omegadot_k = omega_dot - OmegaE; x'dot = rdot cos u
+ *            - r udot sin u, y'dot = rdot sin u + r udot cos u; Vx = x'dot cos Omega - y'dot cos i sin Omega + y' sin i sin
+ *            Omega idot_k - (x' sin Omega + y' cos i cos Omega) Omegadot_k, Vy = x'dot sin Omega + y'dot cos i cos Omega - y'
+ *            sin i cos Omega idot_k + (x' cos Omega - y' cos i sin Omega) Omegadot_k, Vz = y'dot sin i + y' cos i idot_k: the
+ *            ECEF velocity in the frame of the instant.  ddts = af1 + 2 af2 dt + F e sqrt_a cos E Edot, E solved at t_sv.
+ *   counts   a channel counts in an epoch (num_valid) when its ephemeris is usable (the position fix's fence), its transmit
+ *            time is given, its doppler_hz is finite and X, Y, Z, V, dts and ddts are finite.  It is used when besides its
+ *            weight (1 without weights) is finite and > 0 and its byte in `used` is non-zero (without `used`: every one).
+ *   row      at the fix's state st = (x, y, z, c clock_bias_s): the position fix's row is evaluated exactly three times, with
+ *            tau = 0.075 s, then r / c, then r / c.  theta = OmegaE tau of the last evaluation; (Xr, Yr) the position and Vr
+ *            the velocity turned about z by theta, los the row's unit vector; q = los . (Vr - OmegaE (Yr, -Xr, 0)), the
+ *            satellite's inertial velocity along the line of sight; k = 1 / (1 + q / c).  The range rate is k los . (Vr - v)
+ *            -- the light-time equation differentiated: the instant of transmission advances at 1 - taudot and the angle of
+ *            rotation with tau -- and the measurement -lambda doppler_hz = range rate + d - c ddts with lambda = c /
+ *            carrier_hz and d = c * the receiver's clock drift: the row a = (-k los, 1), the right side y = -lambda
+ *            doppler_hz - k los . Vr + c ddts.  Neglected: the second order in the receiver's own drift (doppler_hz times the
+ *            drift) and the clock rate's own 1 - taudot (8e-12 m/s).
+ *   solve    linear: one solve, no iteration.  The 14 sums of w a_i a_j (i <= j) and w a_i y over the used channels, the
+ *            position fix's Cholesky solve with its pivot rule and its order of tests; then v_k = y_k - a_k . s of every
+ *            counting channel, rms_residual_mps = sqrt(sum over the used of v^2 / num_used), clock_drift = s_3 / c.
+ *   frame    p = sqrt(x^2 + y^2), R = |xyz|; from s = z / R, c = p / R exactly 8 steps N = a / sqrt(1 - e2 s^2), z' = z + e2 N s,
+ *            q = sqrt(z'^2 + p^2), s = z' / q, c = p / q (a = 6378137, e2 = 6.69437999014e-3: WGS-84); sin_lat = s, cos_lat =
+ *            c, height_m = p c + z s - a sqrt(1 - e2 s^2); cos_lon = x / p, sin_lon = y / p, or (1, 0) where p = 0.  east =
+ *            (-sin_lon, cos_lon, 0), north = (-sin_lat cos_lon, -sin_lat sin_lon, cos_lat), up = (cos_lat cos_lon, cos_lat
+ *            sin_lon, sin_lat); ve, vn, vu the velocity along them.  No arctangent: a caller turns the pairs into angles.
+ *   status   GAT_VEL_NO_FIX: the fix's status has GAT_FIX_FEW_SATS, SINGULAR or NONFINITE, or its x, y, z or clock_bias_s is
+ *            not finite -- every output of the epoch is zero but status.  A fix that carries only GAT_FIX_NOT_CONVERGED,
+ *            MASKED, MASK_STARVED or EXCLUDED is used as it stands.  GAT_VEL_FEW_SATS: fewer than 4 used channels;
+ *            GAT_VEL_SINGULAR, GAT_VEL_NONFINITE: the solve's -- the record is zero but status and the two counts, resid is
+ *            zero.  GAT_VEL_NO_GEODETIC: R not >= 1e6 m -- the ECEF velocity, the drift and the rms stand, the frame, the
+ *            height and ve, vn, vu are zero.
+ * Optional outputs (null: not written): sat_vel double [E][K][4], Vx, Vy, Vz and ddts of every counting channel (zeros for
+ * one that does not count and in a GAT_VEL_NO_FIX epoch); resid double [E][K], v of every counting channel, used or not.
+ * One epoch never touches another.
+ * gat_velocity_fix enqueues one kernel of gat_position_fix's geometry on the context's stream (a wave an epoch, a lane a
+ * channel, four epochs a workgroup), does not synchronise, allocates nothing and uses no atomics: the same bits every call.
+ * Refusals, all before any launch (the host twin: before any write): GAT_ERR_ARG for a null required pointer (ephemerides,
+ * the two times, doppler_hz, fixes, config, velocities), a wrong struct_size, E or K < 1, non-zero flags and a carrier_hz
+ * that is not finite or not > 0; GAT_ERR_RANGE for K above GAT_MAX_FIX_CHANNELS and E above GAT_MAX_FIX_EPOCHS. */
+#define GAT_VEL_FEW_SATS 1
+#define GAT_VEL_SINGULAR 2
+#define GAT_VEL_NONFINITE 4
+#define GAT_VEL_NO_FIX 8
+#define GAT_VEL_NO_GEODETIC 16
+typedef struct gat_vel_config {
+    uint32_t struct_size; /* sizeof(gat_vel_config) */
+    uint32_t flags;       /* 0 */
+    double carrier_hz;    /* > 0, finite (1575.42e6) */
+} gat_vel_config;
+typedef struct gat_velocity {
+    int32_t status;       /* GAT_VEL_* bits; 0: a velocity with its frame */
+    int32_t num_valid;    /* channels that count in this epoch */
+    int32_t num_used;     /* channels in the equations */
+    int32_t reserved;
+    double vx, vy, vz;    /* ECEF, m/s */
+    double clock_drift;   /* s/s */
+    double rms_residual_mps;
+    double ve, vn, vu;    /* east, north, up, m/s */
+    double sin_lat, cos_lat, sin_lon, cos_lon, height_m; /* geodetic, WGS-84 */
+} gat_velocity;
+GAT_API int32_t gat_velocity_fix(gat_ctx *ctx, const gat_ephemeris *eph_dev, const int32_t *tx_ms_dev, const double *tx_frac_dev,
+                                 const double *doppler_hz_dev, const gat_fix *fixes_dev, const uint8_t *used_dev,
+                                 const double *weights_dev, int32_t num_epochs, int32_t num_channels, const gat_vel_config *config,
+                                 gat_velocity *velocities_dev, double *sat_vel_dev, double *resid_dev);
+/* The same rule in plain loops on the HOST: every pointer is host memory; the bit-exact reference of the device call. */
+GAT_API int32_t gat_velocity_fix_host(const gat_ephemeris *eph_host, const int32_t *tx_ms_host, const double *tx_frac_host,
+                                      const double *doppler_hz_host, const gat_fix *fixes_host, const uint8_t *used_host,
+                                      const double *weights_host, int32_t num_epochs, int32_t num_channels,
+                                      const gat_vel_config *config, gat_velocity *velocities, double *sat_vel, double *resid);
+/* What gat_velocity_fix would do with a call (csrc/gat_vel_plan.h): gat_position_fix's geometry and LDS. */
+GAT_API int32_t gat_velocity_fix_plan(int32_t num_epochs, int32_t num_channels, const gat_vel_config *config, gat_fix_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

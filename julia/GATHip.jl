@@ -1598,4 +1598,75 @@ function position_fix_raim_plan(num_epochs::Integer, num_channels::Integer, raim
     plan[]
 end
 
+# ---- velocity fix: satellite velocities, the Doppler solver and the local frame (include/gat.h) ----
+const GAT_VEL_FEW_SATS = Int32(1)
+const GAT_VEL_SINGULAR = Int32(2)
+const GAT_VEL_NONFINITE = Int32(4)
+const GAT_VEL_NO_FIX = Int32(8)
+const GAT_VEL_NO_GEODETIC = Int32(16)
+# struct gat_vel_config (16 bytes)
+struct VelConfig
+    struct_size::UInt32
+    flags::UInt32
+    carrier_hz::Float64
+end
+VelConfig(; carrier_hz::Real = 1575.42e6) = VelConfig(UInt32(sizeof(VelConfig)), UInt32(0), Float64(carrier_hz))
+# struct gat_velocity (120 bytes)
+struct Velocity
+    status::Int32                 # GAT_VEL_* bits
+    num_valid::Int32
+    num_used::Int32
+    reserved::Int32
+    vx::Float64                   # ECEF, m/s
+    vy::Float64
+    vz::Float64
+    clock_drift::Float64          # s/s
+    rms_residual_mps::Float64
+    ve::Float64                   # east, north, up, m/s
+    vn::Float64
+    vu::Float64
+    sin_lat::Float64              # geodetic, WGS-84
+    cos_lat::Float64
+    sin_lon::Float64
+    cos_lon::Float64
+    height_m::Float64
+end
+# the velocity of every epoch from its Doppler and its fix; doppler_hz [K x E], fixes and velocities [E]; used, weights, sat_vel
+# [4 x K x E] and resid [K x E] may be C_NULL.  Enqueues only.
+function velocity_fix!(ctx::Context, eph::Ptr{Ephemeris}, tx_ms::Ptr{Int32}, tx_frac::Ptr{Float64}, doppler_hz::Ptr{Float64}, fixes::Ptr{Fix},
+                       num_epochs::Integer, num_channels::Integer, velocities::Ptr{Velocity}; cfg::VelConfig = VelConfig(),
+                       used::Ptr{UInt8} = Ptr{UInt8}(C_NULL), weights::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                       sat_vel::Ptr{Float64} = Ptr{Float64}(C_NULL), resid::Ptr{Float64} = Ptr{Float64}(C_NULL))
+    check(ctx, ccall((:gat_velocity_fix, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Ephemeris}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Fix}, Ptr{UInt8}, Ptr{Float64}, Int32, Int32,
+                      Ref{VelConfig}, Ptr{Velocity}, Ptr{Float64}, Ptr{Float64}),
+                     ctx.handle, eph, tx_ms, tx_frac, doppler_hz, fixes, used, weights, Int32(num_epochs), Int32(num_channels), Ref(cfg),
+                     velocities, sat_vel, resid))
+end
+# the same rule on host memory, the bit-exact reference of the device call: tx_ms, tx_frac, doppler_hz [K, E]; returns
+# (velocities [E], sat_vel [4, K, E], resid [K, E])
+function velocity_fix_host(eph::Vector{Ephemeris}, tx_ms::Matrix{Int32}, tx_frac::Matrix{Float64}, doppler_hz::Matrix{Float64},
+                           fixes::Vector{Fix}; used::Union{Nothing,Matrix{UInt8}} = nothing,
+                           weights::Union{Nothing,Matrix{Float64}} = nothing, cfg::VelConfig = VelConfig())
+    K, E = size(tx_ms)
+    velocities = Vector{Velocity}(undef, E)
+    sat_vel = zeros(Float64, 4, K, E)
+    resid = zeros(Float64, K, E)
+    rc = ccall((:gat_velocity_fix_host, libgat), Int32,
+               (Ptr{Ephemeris}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Fix}, Ptr{UInt8}, Ptr{Float64}, Int32, Int32, Ref{VelConfig},
+                Ptr{Velocity}, Ptr{Float64}, Ptr{Float64}),
+               eph, tx_ms, tx_frac, doppler_hz, fixes, used === nothing ? Ptr{UInt8}(C_NULL) : pointer(used),
+               weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights), Int32(E), Int32(K), Ref(cfg), velocities, sat_vel, resid)
+    rc == GAT_OK || throw(GatError(rc, "gat_velocity_fix_host"))
+    velocities, sat_vel, resid
+end
+# what velocity_fix! would do with a call, without a device
+function velocity_fix_plan(num_epochs::Integer, num_channels::Integer, cfg::VelConfig = VelConfig())
+    plan = Ref(FixPlan(UInt32(sizeof(FixPlan)), 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_velocity_fix_plan, libgat), Int32, (Int32, Int32, Ref{VelConfig}, Ref{FixPlan}), Int32(num_epochs), Int32(num_channels),
+               Ref(cfg), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_velocity_fix_plan"))
+    plan[]
+end
+
 end # module
