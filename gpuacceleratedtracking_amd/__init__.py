@@ -15,6 +15,8 @@ from .algorithms import (ALGODICT, ALGODICTINV, MEMDICT, REDDICT, KernelAlgorith
                          ReplicaAlgorithm, cpu_reduce_partial_sum, cuda_reduce_partial_sum, kernel_algorithm)
 from .array import (GAT_BF_CONVENTIONAL, GAT_BF_MVDR, GAT_BF_POWER_INVERSION, beamform, beamform_samples,  # noqa: F401
                     beamformer_weights, spatial_covariance)
+from .atmosphere import (Klobuchar, Page18, RangeCorrections, atmosphere_plan, lnav_page18, lnav_page18_payload,  # noqa: F401
+                         position_fix_corrected, range_corrections, range_corrections_host, tropo_zenith, tropo_zenith_from_fix)
 from .benchmarks import (add_metadata, add_results, algorithmic_bytes, build_stream,  # noqa: F401
                          run_kernel_benchmark, run_reduction_benchmark, run_replica_benchmark, stream_scenario)
 from .context import Context, ResidentCorrelator, get_context  # noqa: F401

@@ -52,6 +52,10 @@ GAT_RAIM_NOT_CHECKED, GAT_RAIM_NO_REDUNDANCY, GAT_RAIM_DETECTED, GAT_RAIM_EXCLUD
 GAT_FIX_EXCLUDED, GAT_RAIM_MAX_EXCLUDE = 64, 4
 # velocity fix (the status bits of gat_velocity)
 GAT_VEL_FEW_SATS, GAT_VEL_SINGULAR, GAT_VEL_NONFINITE, GAT_VEL_NO_FIX, GAT_VEL_NO_GEODETIC = 1, 2, 4, 8, 16
+# atmosphere (the flags of gat_atm_config, the bits of epoch_status and of channel_status)
+GAT_ATM_IONO, GAT_ATM_TROPO = 1, 2
+GAT_ATM_NO_FIX, GAT_ATM_NO_GEODETIC = 1, 2
+GAT_ATM_CH_CORRECTED, GAT_ATM_CH_LOW, GAT_ATM_CH_NONFINITE = 1, 2, 4
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -98,6 +102,9 @@ EXPORTS = [
     "gat_position_fix_raim", "gat_position_fix_raim_host", "gat_position_fix_raim_plan",
     # velocity fix: satellite velocities, the Doppler solver and the local frame
     "gat_velocity_fix", "gat_velocity_fix_host", "gat_velocity_fix_plan",
+    # atmosphere: Klobuchar and troposphere delays, corrected transmit times, subframe 4 page 18
+    "gat_range_corrections", "gat_range_corrections_host", "gat_range_corrections_plan", "gat_atm_atan2_host",
+    "gat_lnav_page18_host", "gat_lnav_page18_words_host",
 ]
 
 
@@ -357,6 +364,19 @@ VELOCITY_DTYPE = np.dtype([("status", "<i4"), ("num_valid", "<i4"), ("num_used",
 assert C.sizeof(VelConfig) == 16 and VELOCITY_DTYPE.itemsize == 120
 
 
+class AtmConfig(C.Structure):
+    """gat_atm_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("carrier_hz", C.c_double), ("floor_sin", C.c_double),
+                ("alpha", C.c_double * 4), ("beta", C.c_double * 4), ("zenith_dry_m", C.c_double), ("zenith_wet_m", C.c_double)]
+
+
+# gat_lnav_page18 (include/gat.h)
+PAGE18_DTYPE = np.dtype([(n, "<i4") for n in ("valid", "data_id", "sv_id", "wnt", "dt_ls", "wnlsf", "dn", "dt_lsf")]
+                        + [("alpha", "<f8", (4,)), ("beta", "<f8", (4,)), ("a0", "<f8"), ("a1", "<f8"), ("tot", "<f8")])
+assert C.sizeof(AtmConfig) == 104 and PAGE18_DTYPE.itemsize == 120
+
+
 _LIB = None
 
 
@@ -492,6 +512,12 @@ def load(build_if_missing: bool = True):
         "gat_velocity_fix": (i32, [vp] * 8 + [i32, i32, C.POINTER(VelConfig), vp, vp, vp]),
         "gat_velocity_fix_host": (i32, [vp] * 7 + [i32, i32, C.POINTER(VelConfig), vp, vp, vp]),
         "gat_velocity_fix_plan": (i32, [i32, i32, C.POINTER(VelConfig), C.POINTER(FixPlan)]),
+        "gat_range_corrections": (i32, [vp] * 8 + [i32, i32, C.POINTER(AtmConfig)] + [vp] * 5),
+        "gat_range_corrections_host": (i32, [vp] * 7 + [i32, i32, C.POINTER(AtmConfig)] + [vp] * 5),
+        "gat_range_corrections_plan": (i32, [i32, i32, C.POINTER(AtmConfig), C.POINTER(FixPlan)]),
+        "gat_atm_atan2_host": (i32, [vp, vp, C.c_int64, vp]),
+        "gat_lnav_page18_host": (i32, [vp, i32, vp]),
+        "gat_lnav_page18_words_host": (i32, [vp, vp]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_update_host_weighted": (i32, [vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),
         "gat_tracking_run_weighted": (i32, [vp, C.POINTER(SignalDesc), i32, i32, i32, C.POINTER(C.c_int32), dbl,

@@ -1709,6 +1709,120 @@ GAT_API int32_t gat_velocity_fix_host(const gat_ephemeris *eph_host, const int32
 /* What gat_velocity_fix would do with a call (csrc/gat_vel_plan.h): gat_position_fix's geometry and LDS. */
 GAT_API int32_t gat_velocity_fix_plan(int32_t num_epochs, int32_t num_channels, const gat_vel_config *config, gat_fix_plan *plan);
 
+/* ---- atmosphere: Klobuchar ionosphere, mapped troposphere, corrected transmit times -----------------------------------------
+ * The fix and the velocity fix model no atmosphere.  gat_range_corrections takes a first fix (gat_position_fix or
+ * gat_position_fix_raim) and gives per (epoch, channel) the ionospheric and the tropospheric delay of the IS-GPS-200
+ * single-frequency user, the elevation and the azimuth as seen from the WGS-84 ellipsoid, and a transmit-time fraction
+ * advanced by the delay that gat_position_fix, gat_position_fix_raim and gat_velocity_fix take as it is: fix ->
+ * corrections -> fix (or RAIM) -> velocity, nothing read back.  The arithmetic is the fix's (FP64, no contraction, no libm
+ * transcendental, every expression as written: csrc/gat_atm.h on top of csrc/gat_fix.h and csrc/gat_vel.h, shared by the
+ * kernel and the host twin: the same bits).  c = 299792458 m/s, pi = 3.1415926535898 wherever semicircles are turned.
+ *   atan2    atm_atan2(y, x): |x| and |y| are swapped so that t = min / max lies in [0, 1] (0 where max is 0: x = y = 0
+ *            gives +0); k = rint(16 t), s = (t - k/16) / (1 + t k/16), |s| <= 1/32; atan t = A[k] + s + s^3 P(s^2) with A[k]
+ *            = atan(k/16) (17 doubles) and P the odd Taylor polynomial to degree 11 in Horner form with explicit fused
+ *            multiply-adds (truncation s^13 / 13 < 2^-68); swapped: pi/2 - a; x < 0: pi - a (pi in two parts); the sign
+ *            bit of y is the result's.  |error| <= 1e-15 rad.  A quotient that is not a number (inf / inf, NaN) gives NaN.
+ *   epoch    the state (x, y, z, c clock_bias_s) of the gat_fix record, accepted exactly as gat_velocity_fix accepts it
+ *            (else GAT_ATM_NO_FIX); R = |xyz| not >= 1e6 m: GAT_ATM_NO_GEODETIC.  Else the velocity fix's frame (8 steps):
+ *            sin / cos of the geodetic latitude phi and of the longitude lambda.  An epoch with either bit passes every
+ *            tx_frac through and writes zeros to every other output of its channels.
+ *   counts   a channel counts when the position fix's rule takes it: usable ephemeris, transmit and receive time given,
+ *            X, Y, Z, dts and the pseudorange finite.  One that does not count: tx_frac passed through, zeros, status 0.
+ *   geometry the fix's row at the state evaluated three times (tau = 0.075 s, r / c, r / c) as the velocity fix does; los
+ *            its unit vector; e = -sin lambda lx + cos lambda ly, n = -sin phi cos lambda lx - sin phi sin lambda ly + cos
+ *            phi lz, u = cos phi cos lambda lx + cos phi sin lambda ly + sin phi lz; e, n or u not finite:
+ *            GAT_ATM_CH_NONFINITE.  sin el = u clipped to [-1, 1] -- against the ellipsoid's normal, not the fix's
+ *            spherical up --; h = sqrt(e^2 + n^2), cos A = n / h, sin A = e / h, (1, 0) where h is not > 0.  A channel
+ *            with sin el >= floor_sin is corrected (GAT_ATM_CH_CORRECTED), else GAT_ATM_CH_LOW: zero delays, tx_frac
+ *            passed through; geom is written for both.
+ *   iono     (GAT_ATM_IONO) in semicircles E = atm_atan2(u, h) / pi, phi_u = atm_atan2(sin phi, cos phi) / pi, lambda_u =
+ *            atm_atan2(sin lambda, cos lambda) / pi; psi = 0.0137 / (E + 0.11) - 0.022; phi_i = phi_u + psi cos A clipped to
+ *            +-0.416; lambda_i = lambda_u + psi sin A / cos(pi phi_i); phi_m = phi_i + 0.064 cos(pi (lambda_i - 1.617));
+ *            t_gps = (rx_ms mod 86400000) 1e-3 + rx_frac - clock_bias_s, t = 43200 lambda_i + t_gps, less 86400 where t >=
+ *            86400, then plus 86400 where t < 0; F = 1 + 16 (0.53 - E)^3; PER = beta0 + phi_m (beta1 + phi_m (beta2 + phi_m
+ *            beta3)) raised to 72000, AMP the same polynomial in alpha raised to 0; xx = 2 pi (t - 50400) / PER; T = F (5e-9
+ *            + AMP (1 - xx^2 / 2 + xx^4 / 24)) where |xx| < 1.57, else F 5e-9; delay = c T (1575.42e6 / carrier_hz)^2.  The
+ *            two cosines are the fix's.  An AMP or PER that is not finite before it is raised, or a delay that is not
+ *            finite: GAT_ATM_CH_NONFINITE for that channel alone (zero delays, tx_frac passed through).
+ *   tropo    (GAT_ATM_TROPO) the zenith delays z_d (hydrostatic) and z_w (wet), metres at the receiver, are the caller's:
+ *            zenith [E][2], or the config's two scalars where it is null.  Chao's mapping with s = sin el, tan = s / sqrt(1
+ *            - s^2): m_d = 1 / (s + 0.00143 / (tan + 0.0445)), m_w = 1 / (s + 0.00035 / (tan + 0.017)), delay = z_d m_d +
+ *            z_w m_w (s = 1: tan infinite, m = 1).  Not finite: GAT_ATM_CH_NONFINITE.
+ *   output   d = iono + tropo (a switched-off term is 0); tx_frac_out = tx_frac + d / c, tx_frac itself where d = 0.  No
+ *            carry into tx_ms: the fix takes any finite fraction.  Advancing the transmit time by d / c also moves the
+ *            satellite by v d / c: along the line of sight at most 930 m/s d / c, 0.3 mm for d = 100 m.  The exact
+ *            alternative, a range-correction input to the fix and RAIM kernels, would need new variants of both.
+ * tx_frac_out double [E][K] is required.  Optional (null: not written): delay double [E][K][2] (iono, tropo, m), geom double
+ * [E][K][3] (sin el, cos A, sin A), channel_status uint8 [E][K], epoch_status int32 [E].
+ * gat_range_corrections enqueues one kernel on the context's stream: one thread an (epoch, channel), t = e K + k, 256
+ * threads a workgroup, every thread forming its epoch's frame itself; no LDS, no barrier, no atomics, no scratch, no
+ * allocation, no synchronisation.
+ * Refusals, all before any launch (the host twin: before any write): GAT_ERR_ARG for a null required pointer (ephemerides,
+ * the four times, fixes, config, tx_frac_out), a wrong struct_size, E or K < 1, a flag other than GAT_ATM_IONO and
+ * GAT_ATM_TROPO, a floor_sin that is not finite and a carrier_hz that is not finite or not > 0; GAT_ERR_RANGE for K above
+ * GAT_MAX_FIX_CHANNELS and E above GAT_MAX_FIX_EPOCHS. */
+#define GAT_ATM_IONO 1
+#define GAT_ATM_TROPO 2
+#define GAT_ATM_NO_FIX 1          /* epoch_status */
+#define GAT_ATM_NO_GEODETIC 2
+#define GAT_ATM_CH_CORRECTED 1    /* channel_status; 0: the channel does not count, or its epoch has no frame */
+#define GAT_ATM_CH_LOW 2
+#define GAT_ATM_CH_NONFINITE 4
+typedef struct gat_atm_config {
+    uint32_t struct_size; /* sizeof(gat_atm_config) */
+    uint32_t flags;       /* GAT_ATM_IONO | GAT_ATM_TROPO */
+    double carrier_hz;    /* > 0, finite (1575.42e6) */
+    double floor_sin;     /* finite (0): a channel below it is not corrected */
+    double alpha[4];      /* Klobuchar: s, s/sc, s/sc^2, s/sc^3 */
+    double beta[4];       /* s, s/sc, s/sc^2, s/sc^3 */
+    double zenith_dry_m;  /* where zenith is null */
+    double zenith_wet_m;
+} gat_atm_config;
+GAT_API int32_t gat_range_corrections(gat_ctx *ctx, const gat_ephemeris *eph_dev, const int32_t *tx_ms_dev, const double *tx_frac_dev,
+                                      const int32_t *rx_ms_dev, const double *rx_frac_dev, const gat_fix *fixes_dev,
+                                      const double *zenith_dev, int32_t num_epochs, int32_t num_channels,
+                                      const gat_atm_config *config, double *tx_frac_out_dev, double *delay_dev, double *geom_dev,
+                                      uint8_t *channel_status_dev, int32_t *epoch_status_dev);
+/* The same rule in plain loops on the HOST: every pointer is host memory; the bit-exact reference of the device call. */
+GAT_API int32_t gat_range_corrections_host(const gat_ephemeris *eph_host, const int32_t *tx_ms_host, const double *tx_frac_host,
+                                           const int32_t *rx_ms_host, const double *rx_frac_host, const gat_fix *fixes_host,
+                                           const double *zenith_host, int32_t num_epochs, int32_t num_channels,
+                                           const gat_atm_config *config, double *tx_frac_out, double *delay, double *geom,
+                                           uint8_t *channel_status, int32_t *epoch_status);
+/* What gat_range_corrections would do with a call (csrc/gat_atm_plan.h): workgroups of `threads`, waves_per_workgroup waves
+ * each, no LDS and no scratch. */
+GAT_API int32_t gat_range_corrections_plan(int32_t num_epochs, int32_t num_channels, const gat_atm_config *config, gat_fix_plan *plan);
+/* atm_atan2 (above) of count pairs, on the host: what the rule's angles are made of.  GAT_ERR_ARG for a null pointer or
+ * count < 0. */
+GAT_API int32_t gat_atm_atan2_host(const double *y, const double *x, int64_t count, double *angle);
+/* Subframe 4, page 18 (ionospheric and UTC data) from one channel's gat_nav_frame records, on the host: the newest frame
+ * with every status bit set, id 4 and SV ID 56.  Found: *page filled, valid = 1; else *page zero.  Returns GAT_ERR_ARG for a
+ * null pointer or num_frames < 0, else GAT_OK.  Data bits d1 .. d24 of words 3 .. 10, the MSB first, signed fields in two's
+ * complement:
+ *   word 3: data ID(2) SV ID(6) alpha0(8 s, 2^-30) alpha1(8 s, 2^-27); word 4: alpha2(8 s, 2^-24) alpha3(8 s, 2^-24) beta0(8 s,
+ *   2^11); word 5: beta1(8 s, 2^14) beta2(8 s, 2^16) beta3(8 s, 2^16); word 6: A1(24 s, 2^-50); word 7: A0 31..8; word 8: A0
+ *   7..0 (32 s, 2^-30) tot(8, 2^12) WNt(8); word 9: dtLS(8 s) WNLSF(8) DN(8); word 10: dtLSF(8 s).
+ * The UTC fields are extracted because they share the page; nothing converts times with them. */
+typedef struct gat_lnav_page18 {
+    int32_t valid;
+    int32_t data_id;
+    int32_t sv_id;    /* 56 */
+    int32_t wnt;
+    int32_t dt_ls;    /* s */
+    int32_t wnlsf;
+    int32_t dn;
+    int32_t dt_lsf;   /* s */
+    double alpha[4];  /* as gat_atm_config */
+    double beta[4];
+    double a0;        /* s */
+    double a1;        /* s/s */
+    double tot;       /* s */
+} gat_lnav_page18;
+GAT_API int32_t gat_lnav_page18_host(const gat_nav_frame *frames, int32_t num_frames, gat_lnav_page18 *page);
+/* The inverse: the 190 payload bits of the page (one bit a byte), every field rint(value / scale) kept to its width; the
+ * reserved bits of word 10 are 0.  valid is not read. */
+GAT_API int32_t gat_lnav_page18_words_host(const gat_lnav_page18 *page, uint8_t *payload_bits);
+
 #ifdef __cplusplus
 }
 #endif

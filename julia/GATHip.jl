@@ -1669,4 +1669,105 @@ function velocity_fix_plan(num_epochs::Integer, num_channels::Integer, cfg::VelC
     plan[]
 end
 
+# ---- atmosphere: Klobuchar and troposphere delays, corrected transmit times, subframe 4 page 18 (include/gat.h) ----
+const GAT_ATM_IONO = UInt32(1)
+const GAT_ATM_TROPO = UInt32(2)
+const GAT_ATM_NO_FIX = Int32(1)
+const GAT_ATM_NO_GEODETIC = Int32(2)
+const GAT_ATM_CH_CORRECTED = UInt8(1)
+const GAT_ATM_CH_LOW = UInt8(2)
+const GAT_ATM_CH_NONFINITE = UInt8(4)
+# struct gat_atm_config (104 bytes)
+struct AtmConfig
+    struct_size::UInt32
+    flags::UInt32                 # GAT_ATM_IONO | GAT_ATM_TROPO
+    carrier_hz::Float64
+    floor_sin::Float64
+    alpha::NTuple{4,Float64}      # Klobuchar: s, s/sc, s/sc^2, s/sc^3
+    beta::NTuple{4,Float64}
+    zenith_dry_m::Float64         # where zenith is C_NULL / nothing
+    zenith_wet_m::Float64
+end
+AtmConfig(; flags::Integer = GAT_ATM_IONO | GAT_ATM_TROPO, carrier_hz::Real = 1575.42e6, floor_sin::Real = 0.0, alpha = (0.0, 0.0, 0.0, 0.0),
+          beta = (0.0, 0.0, 0.0, 0.0), zenith_dry_m::Real = 0.0, zenith_wet_m::Real = 0.0) =
+    AtmConfig(UInt32(sizeof(AtmConfig)), UInt32(flags), Float64(carrier_hz), Float64(floor_sin), NTuple{4,Float64}(Float64.(alpha)),
+              NTuple{4,Float64}(Float64.(beta)), Float64(zenith_dry_m), Float64(zenith_wet_m))
+# struct gat_lnav_page18 (120 bytes)
+struct Page18
+    valid::Int32
+    data_id::Int32
+    sv_id::Int32
+    wnt::Int32
+    dt_ls::Int32
+    wnlsf::Int32
+    dn::Int32
+    dt_lsf::Int32
+    alpha::NTuple{4,Float64}
+    beta::NTuple{4,Float64}
+    a0::Float64
+    a1::Float64
+    tot::Float64
+end
+# the delays of every (epoch, channel) at the fixes and the corrected transmit-time fractions; tx_frac_out [K x E]; zenith [2 x E],
+# delay [2 x K x E], geom [3 x K x E], channel_status [K x E] and epoch_status [E] may be C_NULL.  Enqueues only.
+function range_corrections!(ctx::Context, eph::Ptr{Ephemeris}, tx_ms::Ptr{Int32}, tx_frac::Ptr{Float64}, rx_ms::Ptr{Int32}, rx_frac::Ptr{Float64},
+                            fixes::Ptr{Fix}, num_epochs::Integer, num_channels::Integer, tx_frac_out::Ptr{Float64}; cfg::AtmConfig = AtmConfig(),
+                            zenith::Ptr{Float64} = Ptr{Float64}(C_NULL), delay::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                            geom::Ptr{Float64} = Ptr{Float64}(C_NULL), channel_status::Ptr{UInt8} = Ptr{UInt8}(C_NULL),
+                            epoch_status::Ptr{Int32} = Ptr{Int32}(C_NULL))
+    check(ctx, ccall((:gat_range_corrections, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Ephemeris}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Fix}, Ptr{Float64}, Int32, Int32,
+                      Ref{AtmConfig}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Int32}),
+                     ctx.handle, eph, tx_ms, tx_frac, rx_ms, rx_frac, fixes, zenith, Int32(num_epochs), Int32(num_channels), Ref(cfg),
+                     tx_frac_out, delay, geom, channel_status, epoch_status))
+end
+# the same rule on host memory, the bit-exact reference of the device call: tx_ms, tx_frac [K, E]; returns (tx_frac_out [K, E],
+# delay [2, K, E], geom [3, K, E], channel_status [K, E], epoch_status [E])
+function range_corrections_host(eph::Vector{Ephemeris}, tx_ms::Matrix{Int32}, tx_frac::Matrix{Float64}, rx_ms::Vector{Int32},
+                                rx_frac::Vector{Float64}, fixes::Vector{Fix}; zenith::Union{Nothing,Matrix{Float64}} = nothing,
+                                cfg::AtmConfig = AtmConfig())
+    K, E = size(tx_ms)
+    tx_frac_out = zeros(Float64, K, E)
+    delay = zeros(Float64, 2, K, E)
+    geom = zeros(Float64, 3, K, E)
+    channel_status = zeros(UInt8, K, E)
+    epoch_status = zeros(Int32, E)
+    rc = ccall((:gat_range_corrections_host, libgat), Int32,
+               (Ptr{Ephemeris}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Fix}, Ptr{Float64}, Int32, Int32, Ref{AtmConfig},
+                Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Int32}),
+               eph, tx_ms, tx_frac, rx_ms, rx_frac, fixes, zenith === nothing ? Ptr{Float64}(C_NULL) : pointer(zenith), Int32(E), Int32(K),
+               Ref(cfg), tx_frac_out, delay, geom, channel_status, epoch_status)
+    rc == GAT_OK || throw(GatError(rc, "gat_range_corrections_host"))
+    tx_frac_out, delay, geom, channel_status, epoch_status
+end
+# what range_corrections! would do with a call, without a device
+function range_corrections_plan(num_epochs::Integer, num_channels::Integer, cfg::AtmConfig = AtmConfig())
+    plan = Ref(FixPlan(UInt32(sizeof(FixPlan)), 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_range_corrections_plan, libgat), Int32, (Int32, Int32, Ref{AtmConfig}, Ref{FixPlan}), Int32(num_epochs),
+               Int32(num_channels), Ref(cfg), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_range_corrections_plan"))
+    plan[]
+end
+# the rule's arctangent of every pair
+function atm_atan2(y::Vector{Float64}, x::Vector{Float64})
+    angle = zeros(Float64, length(y))
+    rc = ccall((:gat_atm_atan2_host, libgat), Int32, (Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}), y, x, Int64(length(y)), angle)
+    rc == GAT_OK || throw(GatError(rc, "gat_atm_atan2_host"))
+    angle
+end
+# subframe 4, page 18 from one channel's frame records (nav_decode_host's frames[:, k]); valid = 0 where there is none
+function lnav_page18(frames::Vector{NavFrame})
+    page = Ref{Page18}()
+    rc = ccall((:gat_lnav_page18_host, libgat), Int32, (Ptr{NavFrame}, Int32, Ref{Page18}), frames, Int32(length(frames)), page)
+    rc == GAT_OK || throw(GatError(rc, "gat_lnav_page18_host"))
+    page[]
+end
+# the inverse: the page's 190 payload bits
+function lnav_page18_words(page::Page18)
+    bits = zeros(UInt8, 190)
+    rc = ccall((:gat_lnav_page18_words_host, libgat), Int32, (Ref{Page18}, Ptr{UInt8}), Ref(page), bits)
+    rc == GAT_OK || throw(GatError(rc, "gat_lnav_page18_words_host"))
+    bits
+end
+
 end # module
