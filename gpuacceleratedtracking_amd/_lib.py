@@ -56,6 +56,10 @@ GAT_VEL_FEW_SATS, GAT_VEL_SINGULAR, GAT_VEL_NONFINITE, GAT_VEL_NO_FIX, GAT_VEL_N
 GAT_ATM_IONO, GAT_ATM_TROPO = 1, 2
 GAT_ATM_NO_FIX, GAT_ATM_NO_GEODETIC = 1, 2
 GAT_ATM_CH_CORRECTED, GAT_ATM_CH_LOW, GAT_ATM_CH_NONFINITE = 1, 2, 4
+# carrier smoothing (the flag of gat_smooth_config, the bits of status, the limit on the epochs)
+GAT_SMOOTH_RATE_TEST = 1
+GAT_SMOOTH_MEASURED, GAT_SMOOTH_GAP, GAT_SMOOTH_CMC, GAT_SMOOTH_RATE = 1, 2, 4, 8
+GAT_MAX_SMOOTH_EPOCHS = 1048576
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -105,6 +109,8 @@ EXPORTS = [
     # atmosphere: Klobuchar and troposphere delays, corrected transmit times, subframe 4 page 18
     "gat_range_corrections", "gat_range_corrections_host", "gat_range_corrections_plan", "gat_atm_atan2_host",
     "gat_lnav_page18_host", "gat_lnav_page18_words_host",
+    # carrier smoothing: cycle-slip arcs and Hatch-filtered transmit times
+    "gat_smooth_observables", "gat_smooth_observables_host", "gat_smooth_observables_plan",
 ]
 
 
@@ -377,6 +383,26 @@ PAGE18_DTYPE = np.dtype([(n, "<i4") for n in ("valid", "data_id", "sv_id", "wnt"
 assert C.sizeof(AtmConfig) == 104 and PAGE18_DTYPE.itemsize == 120
 
 
+class SmoothConfig(C.Structure):
+    """gat_smooth_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("window", C.c_int32), ("reserved", C.c_int32), ("carrier_hz", C.c_double),
+                ("if_hz", C.c_double), ("epoch_seconds", C.c_double), ("cmc_gate_s", C.c_double), ("rate_gate_cycles", C.c_double)]
+
+
+class SmoothPlan(C.Structure):
+    """gat_smooth_plan (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("chunk_epochs", C.c_int32), ("num_chunks", C.c_int32), ("lanes", C.c_int32), ("rows", C.c_int32),
+                ("run_epochs", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32), ("chunk_workgroups", C.c_int32),
+                ("channel_workgroups", C.c_int32), ("output_workgroups", C.c_int32), ("reserved", C.c_int32), ("scratch_bytes", C.c_int64)]
+
+
+# gat_smooth_channel (include/gat.h)
+SMOOTH_CHANNEL_DTYPE = np.dtype([(n, "<i4") for n in ("measured", "arcs", "cmc_resets", "rate_resets")])
+assert C.sizeof(SmoothConfig) == 56 and C.sizeof(SmoothPlan) == 56 and SMOOTH_CHANNEL_DTYPE.itemsize == 16
+
+
 _LIB = None
 
 
@@ -516,6 +542,9 @@ def load(build_if_missing: bool = True):
         "gat_range_corrections_host": (i32, [vp] * 7 + [i32, i32, C.POINTER(AtmConfig)] + [vp] * 5),
         "gat_range_corrections_plan": (i32, [i32, i32, C.POINTER(AtmConfig), C.POINTER(FixPlan)]),
         "gat_atm_atan2_host": (i32, [vp, vp, C.c_int64, vp]),
+        "gat_smooth_observables": (i32, [vp] * 9 + [i32, i32, C.POINTER(SmoothConfig)] + [vp] * 5),
+        "gat_smooth_observables_host": (i32, [vp] * 8 + [i32, i32, C.POINTER(SmoothConfig)] + [vp] * 5),
+        "gat_smooth_observables_plan": (i32, [i32, i32, C.POINTER(SmoothConfig), C.POINTER(SmoothPlan)]),
         "gat_lnav_page18_host": (i32, [vp, i32, vp]),
         "gat_lnav_page18_words_host": (i32, [vp, vp]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),

@@ -79,6 +79,12 @@ class Observables(PlannedResult):
         return (self.channels["status"] & ~EDGE_AMBIGUOUS) == 0
 
 
+def _with_epochs(obs: Observables, cfg) -> Observables:
+    """what the carrier smoothing reads of the call besides its arrays: ``if_hz`` and ``epoch_seconds`` = epoch_stride * block_seconds"""
+    obs.if_hz, obs.epoch_seconds = float(cfg.if_hz), int(cfg.epoch_stride) * float(cfg.block_seconds)
+    return obs
+
+
 def _loop_config(loop, mon, config: dict) -> dict:
     """the loop's and the monitor's values under the caller's"""
     if loop is not None:
@@ -142,7 +148,7 @@ def observables(history: torch.Tensor, mon, nav, *, loop=None, epoch_first: int 
     rc = ctx.lib.gat_observables(ctx._h, vp(history), vp(mon_recs), vp(nav_chan), vp(nav_frames), B, K, E, C.byref(cfg),
                                  *[vp(raw.get(n)) for n in OUTPUTS])
     ctx.check(rc, "gat_observables")
-    return keep_alive(Observables(raw, ctx), history, mon_recs, nav_chan, nav_frames)
+    return keep_alive(_with_epochs(Observables(raw, ctx), cfg), history, mon_recs, nav_chan, nav_frames)
 
 
 def observables_host(history, mon, nav, *, loop=None, epoch_first: int = 0, epoch_stride: int = 1, num_epochs: int | None = None,
@@ -179,7 +185,7 @@ def observables_host(history, mon, nav, *, loop=None, epoch_first: int = 0, epoc
     rc = _lib.load().gat_observables_host(addr(history), addr(mon_recs), addr(nav_chan), addr(nav_frames), B, K, E, C.byref(cfg),
                                           *[addr(raw.get(n)) for n in OUTPUTS])
     host_check(rc, "gat_observables_host")
-    return Observables(raw)
+    return _with_epochs(Observables(raw), cfg)
 
 
 def observables_plan(num_blocks: int, num_channels: int, num_epochs: int | None = None, *, loop=None, epoch_first: int = 0, epoch_stride: int = 1,

@@ -1823,6 +1823,111 @@ GAT_API int32_t gat_lnav_page18_host(const gat_nav_frame *frames, int32_t num_fr
  * reserved bits of word 10 are 0.  valid is not read. */
 GAT_API int32_t gat_lnav_page18_words_host(const gat_lnav_page18 *page, uint8_t *payload_bits);
 
+/* ---- carrier smoothing: cycle-slip arcs and Hatch-filtered transmit times ---------------------------------------------------
+ * Raw code phase carries metres of noise; the carrier phase of the same channel is good to millimetres but ambiguous by whole
+ * cycles and broken at a slip.  gat_smooth_observables reads what gat_observables wrote (tx_ms int32 and tx_frac double [E][K],
+ * the fraction raw or corrected by gat_range_corrections; rx_ms int32 and rx_frac double [E]; carrier_cycles int64 and
+ * carrier_frac double [E][K]; optionally doppler_hz double [E][K] and a lock mask valid uint8 [E][K], 0 = not measured, the
+ * hook for a lock detector of the caller's), cuts every channel into arcs at gaps and cycle slips and writes a transmit-time
+ * fraction smoothed by the carrier over the last W epochs of the arc, which gat_position_fix, gat_position_fix_raim,
+ * gat_range_corrections and gat_velocity_fix take as it is.  FP64, no contraction, every expression as written, no libm
+ * beyond rint and fabs (csrc/gat_smooth.h, shared by the kernels and the host twin: the same bits).  u = 2^-48 s (c u = 1.07
+ * um); W = window, g = cmc_gate_s, fL = carrier_hz, Te = epoch_seconds.
+ *   measured  epoch e of channel k is measured when tx_ms >= 0 and rx_ms[e] >= 0; tx_frac, rx_frac[e] and carrier_frac are
+ *             finite; doppler_hz is finite (with GAT_SMOOTH_RATE_TEST; not read without); valid is null or nonzero.  Not
+ *             measured: tx_frac passed through, count 0, cmc_s 0, status 0.
+ *   increment for e > 0 with e - 1 and e measured: dms = wrap(rx_ms[e] - rx_ms[e-1]) - wrap(tx_ms[e] - tx_ms[e-1]), each
+ *             difference in int64 and wrapped once (one week's 604800000 added or taken) into [-302400000, 302400000);
+ *             dPhi = (double)(cycles[e] - cycles[e-1]) + (frac[e] - frac[e-1]), the integer difference in int64 (modulo
+ *             2^64); dPhin = dPhi - if_hz * Te; delta = (double) dms * 1e-3 + ((rx_frac[e] - rx_frac[e-1]) - (tx_frac[e] -
+ *             tx_frac[e-1])) + dPhin / fL: the growth of pseudorange minus carrier range between the two epochs in seconds
+ *             (the replica's phase grows by IF plus Doppler, and a falling range is a positive Doppler).
+ *   resets    epoch e begins an arc for any of: GAT_SMOOTH_GAP, e = 0 or e - 1 not measured; GAT_SMOOTH_CMC, |dms| > 1000 or
+ *             !(fabs(delta) <= g), which catches NaN; GAT_SMOOTH_RATE (with GAT_SMOOTH_RATE_TEST), !(fabs(dPhin - 0.5 *
+ *             (doppler[e] + doppler[e-1]) * Te) <= rate_gate_cycles).  status = GAT_SMOOTH_MEASURED | the reasons.  At an arc
+ *             start q_e = 0, else q_e = (int64) rint(delta / u): |q| <= 2^30 by the bound on g.
+ *   scans     per channel over all epochs: C_e = sum_{i<=e} q_i and SS_e = sum_{i<=e} C_i, uint64 modulo 2^64; a(e) the
+ *             latest arc start at or before e (a max-scan).  An epoch that is not measured adds q = 0, starts no arc and
+ *             gets no smoothed output.
+ *   output    for a measured e: n = min(e - a(e) + 1, W); S = (int64)(SS_e - SS_{e-n} - n C_e), SS_{-1} = 0; m = ((double) S *
+ *             0x1p-48) / (double) n; tx_frac_out = tx_frac - m (n = 1: tx_frac itself); count = n; cmc_s = (double)(int64)(C_e -
+ *             C_{a(e)}) * 0x1p-48, code minus carrier since the arc began (the multipath and divergence monitor).  S is the
+ *             sum over the window of (P_j - L_j) - (P_e - L_e): tx_frac_out is the transmit time of the pseudorange L_e +
+ *             mean(P_j - L_j) over the last n epochs of the arc, the Hatch filter in sliding-window form, identical to the
+ *             recursive form while n < W; white code noise of sigma leaves sigma / sqrt(n).  |S| <= 2^30 W (W - 1) / 2 <
+ *             2^62, so the modular differences are exact whatever the global sums wrapped to.  The ionosphere delays the
+ *             code and advances the carrier: code minus carrier diverges at twice the ionosphere's rate of change, and the
+ *             mean over the window lags by half the window's share of it -- W bounds that bias.  No carry into tx_ms: the
+ *             fix takes any finite fraction.
+ * tx_frac_out double [E][K] is required.  Optional (null: not written): count int32 [E][K], cmc_s double [E][K], status
+ * uint8 [E][K], channels [K].
+ * The call enqueues four kernels on the context's stream, does not synchronise and allocates nothing but the context's
+ * scratch (gat_smooth_observables_plan, csrc/gat_smooth_plan.h).  The epochs are cut into chunks of consecutive epochs, one
+ * contiguous [chunk][K] span each; a workgroup a chunk reduces every thread's run to (len, Q, S, last reset, counts) --
+ * segments combine as Q = Q_A + Q_B, S = S_A + S_B + len_B Q_A, the later reset -- and the chunk through LDS; a wave a
+ * channel scans the chunks' segments and writes the channel's record; a workgroup a chunk walks its span again and writes C,
+ * SS and a(e) to the scratch, and the status; one thread an (epoch, channel) gathers SS_{e-n} and C_{a(e)} and writes the
+ * rest.  No atomics, no floating-point sum, plain vector stores: the same bits every call and from the twin.
+ * Refusals, all before any launch (the host twin: before any write): GAT_ERR_ARG for a null required pointer (the four
+ * times, carrier_cycles, carrier_frac, config, tx_frac_out), a wrong struct_size, E or K < 1, a flag other than
+ * GAT_SMOOTH_RATE_TEST, reserved != 0, the rate test without doppler_hz, a carrier_hz or epoch_seconds that is not finite
+ * or not > 0 and an if_hz that is not finite; GAT_ERR_RANGE for a window outside 1 .. 65536, a cmc_gate_s outside (0,
+ * 2^-18], a rate_gate_cycles that is not finite and > 0 with the rate test, K above GAT_MAX_FIX_CHANNELS, E above
+ * GAT_MAX_SMOOTH_EPOCHS and a call whose scratch would exceed 1 GiB. */
+#define GAT_MAX_SMOOTH_EPOCHS 1048576
+#define GAT_SMOOTH_RATE_TEST 1  /* flags */
+#define GAT_SMOOTH_MEASURED 1   /* status */
+#define GAT_SMOOTH_GAP 2
+#define GAT_SMOOTH_CMC 4
+#define GAT_SMOOTH_RATE 8
+typedef struct gat_smooth_config {
+    uint32_t struct_size;    /* sizeof(gat_smooth_config) */
+    uint32_t flags;          /* GAT_SMOOTH_RATE_TEST */
+    int32_t window;          /* W, 1 .. 65536 epochs */
+    int32_t reserved;        /* 0 */
+    double carrier_hz;       /* > 0, finite (1575.42e6) */
+    double if_hz;            /* finite: the observables' */
+    double epoch_seconds;    /* > 0, finite: epoch_stride * block_seconds */
+    double cmc_gate_s;       /* 0 < g <= 2^-18 s */
+    double rate_gate_cycles; /* > 0 with GAT_SMOOTH_RATE_TEST */
+} gat_smooth_config;
+typedef struct gat_smooth_channel {
+    int32_t measured;    /* measured epochs */
+    int32_t arcs;        /* arc starts */
+    int32_t cmc_resets;  /* epochs with GAT_SMOOTH_CMC */
+    int32_t rate_resets; /* epochs with GAT_SMOOTH_RATE */
+} gat_smooth_channel;
+GAT_API int32_t gat_smooth_observables(gat_ctx *ctx, const int32_t *tx_ms_dev, const double *tx_frac_dev, const int32_t *rx_ms_dev,
+                                       const double *rx_frac_dev, const int64_t *carrier_cycles_dev, const double *carrier_frac_dev,
+                                       const double *doppler_hz_dev, const uint8_t *valid_dev, int32_t num_epochs, int32_t num_channels,
+                                       const gat_smooth_config *config, double *tx_frac_out_dev, int32_t *count_dev, double *cmc_s_dev,
+                                       uint8_t *status_dev, gat_smooth_channel *channels_dev);
+/* The same rule in plain loops on the HOST: every pointer is host memory; the bit-exact reference of the device call. */
+GAT_API int32_t gat_smooth_observables_host(const int32_t *tx_ms_host, const double *tx_frac_host, const int32_t *rx_ms_host,
+                                            const double *rx_frac_host, const int64_t *carrier_cycles_host,
+                                            const double *carrier_frac_host, const double *doppler_hz_host, const uint8_t *valid_host,
+                                            int32_t num_epochs, int32_t num_channels, const gat_smooth_config *config,
+                                            double *tx_frac_out, int32_t *count, double *cmc_s, uint8_t *status,
+                                            gat_smooth_channel *channels);
+/* What gat_smooth_observables would do with a call (csrc/gat_smooth_plan.h; no context, no device, nothing is read but
+ * config).  A chunk is chunk_epochs consecutive epochs (the last one takes what is left); a workgroup of `threads` is rows x
+ * lanes, lane l < num_channels holds channel l and row r walks run_epochs consecutive epochs of the chunk.  The emit and the
+ * output stage are separate kernels for every call: a look-back of up to W epochs leaves the workgroup's chunk.  The refusals
+ * are the call's, but for the pointers. */
+typedef struct gat_smooth_plan {
+    uint32_t struct_size; /* sizeof(gat_smooth_plan), set by the caller */
+    int32_t chunk_epochs, num_chunks;
+    int32_t lanes, rows, run_epochs;
+    int32_t threads, lds_bytes;
+    int32_t chunk_workgroups;   /* num_chunks: the sum kernel and the emit kernel each */
+    int32_t channel_workgroups; /* four channels (waves) a workgroup */
+    int32_t output_workgroups;  /* `threads` (epoch, channel) pairs a workgroup */
+    int32_t reserved;
+    int64_t scratch_bytes;
+} gat_smooth_plan;
+GAT_API int32_t gat_smooth_observables_plan(int32_t num_epochs, int32_t num_channels, const gat_smooth_config *config,
+                                            gat_smooth_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

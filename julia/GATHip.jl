@@ -1770,4 +1770,92 @@ function lnav_page18_words(page::Page18)
     bits
 end
 
+# ---- carrier smoothing: cycle-slip arcs and Hatch-filtered transmit times (include/gat.h) ----
+const GAT_MAX_SMOOTH_EPOCHS = 1048576
+const GAT_SMOOTH_RATE_TEST = UInt32(1)
+const GAT_SMOOTH_MEASURED = UInt8(1)
+const GAT_SMOOTH_GAP = UInt8(2)
+const GAT_SMOOTH_CMC = UInt8(4)
+const GAT_SMOOTH_RATE = UInt8(8)
+# struct gat_smooth_config (56 bytes)
+struct SmoothConfig
+    struct_size::UInt32
+    flags::UInt32                 # GAT_SMOOTH_RATE_TEST
+    window::Int32                 # W, 1 .. 65536 epochs
+    reserved::Int32
+    carrier_hz::Float64
+    if_hz::Float64                # the observables'
+    epoch_seconds::Float64        # epoch_stride * block_seconds
+    cmc_gate_s::Float64           # 0 < g <= 2^-18 s
+    rate_gate_cycles::Float64     # > 0 with GAT_SMOOTH_RATE_TEST
+end
+SmoothConfig(; window::Integer, epoch_seconds::Real, if_hz::Real = 0.0, cmc_gate_s::Real = 15.0 / 299792458.0,
+             rate_gate_cycles::Union{Nothing,Real} = nothing, carrier_hz::Real = 1575.42e6,
+             flags::Integer = rate_gate_cycles === nothing ? 0 : GAT_SMOOTH_RATE_TEST) =
+    SmoothConfig(UInt32(sizeof(SmoothConfig)), UInt32(flags), Int32(window), Int32(0), Float64(carrier_hz), Float64(if_hz), Float64(epoch_seconds),
+                 Float64(cmc_gate_s), rate_gate_cycles === nothing ? 0.0 : Float64(rate_gate_cycles))
+# struct gat_smooth_channel (16 bytes)
+struct SmoothChannel
+    measured::Int32
+    arcs::Int32
+    cmc_resets::Int32
+    rate_resets::Int32
+end
+# struct gat_smooth_plan (56 bytes)
+struct SmoothPlan
+    struct_size::UInt32
+    chunk_epochs::Int32
+    num_chunks::Int32
+    lanes::Int32
+    rows::Int32
+    run_epochs::Int32
+    threads::Int32
+    lds_bytes::Int32
+    chunk_workgroups::Int32
+    channel_workgroups::Int32
+    output_workgroups::Int32
+    reserved::Int32
+    scratch_bytes::Int64
+end
+# the observables' transmit-time fractions smoothed by their carrier phase; tx_ms, tx_frac, carrier_cycles, carrier_frac, tx_frac_out
+# [K x E], rx_ms, rx_frac [E]; doppler_hz and valid [K x E], count, cmc_s, status [K x E] and channels [K] may be C_NULL.  Enqueues only.
+function smooth_observables!(ctx::Context, tx_ms::Ptr{Int32}, tx_frac::Ptr{Float64}, rx_ms::Ptr{Int32}, rx_frac::Ptr{Float64},
+                             carrier_cycles::Ptr{Int64}, carrier_frac::Ptr{Float64}, num_epochs::Integer, num_channels::Integer,
+                             cfg::SmoothConfig, tx_frac_out::Ptr{Float64}; doppler_hz::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                             valid::Ptr{UInt8} = Ptr{UInt8}(C_NULL), count::Ptr{Int32} = Ptr{Int32}(C_NULL),
+                             cmc_s::Ptr{Float64} = Ptr{Float64}(C_NULL), status::Ptr{UInt8} = Ptr{UInt8}(C_NULL),
+                             channels::Ptr{SmoothChannel} = Ptr{SmoothChannel}(C_NULL))
+    check(ctx, ccall((:gat_smooth_observables, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32, Int32,
+                      Ref{SmoothConfig}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{UInt8}, Ptr{SmoothChannel}),
+                     ctx.handle, tx_ms, tx_frac, rx_ms, rx_frac, carrier_cycles, carrier_frac, doppler_hz, valid, Int32(num_epochs),
+                     Int32(num_channels), Ref(cfg), tx_frac_out, count, cmc_s, status, channels))
+end
+# the same rule on host memory, the bit-exact reference of the device call: returns (tx_frac_out, count, cmc_s, status [K, E], channels [K])
+function smooth_observables_host(tx_ms::Matrix{Int32}, tx_frac::Matrix{Float64}, rx_ms::Vector{Int32}, rx_frac::Vector{Float64},
+                                 carrier_cycles::Matrix{Int64}, carrier_frac::Matrix{Float64}, cfg::SmoothConfig;
+                                 doppler_hz::Union{Nothing,Matrix{Float64}} = nothing, valid::Union{Nothing,Matrix{UInt8}} = nothing)
+    K, E = size(tx_ms)
+    tx_frac_out = zeros(Float64, K, E)
+    count = zeros(Int32, K, E)
+    cmc_s = zeros(Float64, K, E)
+    status = zeros(UInt8, K, E)
+    channels = Vector{SmoothChannel}(undef, K)
+    rc = ccall((:gat_smooth_observables_host, libgat), Int32,
+               (Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32, Int32,
+                Ref{SmoothConfig}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{UInt8}, Ptr{SmoothChannel}),
+               tx_ms, tx_frac, rx_ms, rx_frac, carrier_cycles, carrier_frac, doppler_hz === nothing ? Ptr{Float64}(C_NULL) : pointer(doppler_hz),
+               valid === nothing ? Ptr{UInt8}(C_NULL) : pointer(valid), Int32(E), Int32(K), Ref(cfg), tx_frac_out, count, cmc_s, status, channels)
+    rc == GAT_OK || throw(GatError(rc, "gat_smooth_observables_host"))
+    tx_frac_out, count, cmc_s, status, channels
+end
+# what smooth_observables! would do with a call, without a device
+function smooth_observables_plan(num_epochs::Integer, num_channels::Integer, cfg::SmoothConfig)
+    plan = Ref(SmoothPlan(UInt32(sizeof(SmoothPlan)), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_smooth_observables_plan, libgat), Int32, (Int32, Int32, Ref{SmoothConfig}, Ref{SmoothPlan}), Int32(num_epochs),
+               Int32(num_channels), Ref(cfg), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_smooth_observables_plan"))
+    plan[]
+end
+
 end # module
