@@ -40,6 +40,7 @@ from .spectrum import (auto_notch, find_tones, sample_spectrum, sample_spectrum_
 from .spacetime import (spacetime_covariance, spacetime_delay, spacetime_filter, spacetime_filter_host, spacetime_steering,  # noqa: F401
                         spacetime_stream, spacetime_weights)
 from .smoothing import SmoothedObservables, smooth_observables, smooth_observables_host, smoothing_plan  # noqa: F401
+from .snapshot import SnapshotFix, code_fractions, snapshot_fix, snapshot_fix_host, snapshot_plan  # noqa: F401
 from .signals import GNSSDICT, GPSL1, GPSL5, generate_codes, get_code_frequency, get_code_length  # noqa: F401
 from .subspace import (accumulator_covariance, accumulator_covariance_host, hermitian_eig, hermitian_eig_host, source_count,  # noqa: F401
                        steering_from_accumulators, subspace_plan)

@@ -60,6 +60,9 @@ GAT_ATM_CH_CORRECTED, GAT_ATM_CH_LOW, GAT_ATM_CH_NONFINITE = 1, 2, 4
 GAT_SMOOTH_RATE_TEST = 1
 GAT_SMOOTH_MEASURED, GAT_SMOOTH_GAP, GAT_SMOOTH_CMC, GAT_SMOOTH_RATE = 1, 2, 4, 8
 GAT_MAX_SMOOTH_EPOCHS = 1048576
+# snapshot fix (the status bits of gat_snap_fix)
+(GAT_SNAP_FEW_SATS, GAT_SNAP_SINGULAR, GAT_SNAP_NONFINITE, GAT_SNAP_NOT_CONVERGED, GAT_SNAP_MASK_STARVED, GAT_SNAP_MASKED, GAT_SNAP_AMBIGUOUS,
+ GAT_SNAP_RERESOLVED) = 1, 2, 4, 8, 16, 32, 64, 128
 
 EXPORTS = [
     "gat_create", "gat_destroy", "gat_set_stream", "gat_sync", "gat_last_error", "gat_version",
@@ -111,6 +114,8 @@ EXPORTS = [
     "gat_lnav_page18_host", "gat_lnav_page18_words_host",
     # carrier smoothing: cycle-slip arcs and Hatch-filtered transmit times
     "gat_smooth_observables", "gat_smooth_observables_host", "gat_smooth_observables_plan",
+    # snapshot fix: a coarse-time position from code phases alone
+    "gat_snapshot_fix", "gat_snapshot_fix_host", "gat_snapshot_fix_plan",
 ]
 
 
@@ -370,6 +375,20 @@ VELOCITY_DTYPE = np.dtype([("status", "<i4"), ("num_valid", "<i4"), ("num_used",
 assert C.sizeof(VelConfig) == 16 and VELOCITY_DTYPE.itemsize == 120
 
 
+class SnapConfig(C.Structure):
+    """gat_snap_config (include/gat.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("max_iter", C.c_int32), ("tol_m", C.c_double), ("mask_sin", C.c_double),
+                ("init_xyz", C.c_double * 3), ("ambiguity_margin", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# gat_snap_fix (include/gat.h)
+SNAP_FIX_DTYPE = np.dtype([("status", "<i4"), ("num_valid", "<i4"), ("num_used", "<i4"), ("iterations", "<i4")]
+                          + [(n, "<f8") for n in ("x", "y", "z", "clock_bias_s", "coarse_time_s", "rms_residual_m", "last_step_m", "gdop", "pdop",
+                                                  "tdop")])
+assert C.sizeof(SnapConfig) == 64 and SNAP_FIX_DTYPE.itemsize == 96
+
+
 class AtmConfig(C.Structure):
     """gat_atm_config (include/gat.h)."""
 
@@ -545,6 +564,9 @@ def load(build_if_missing: bool = True):
         "gat_smooth_observables": (i32, [vp] * 9 + [i32, i32, C.POINTER(SmoothConfig)] + [vp] * 5),
         "gat_smooth_observables_host": (i32, [vp] * 8 + [i32, i32, C.POINTER(SmoothConfig)] + [vp] * 5),
         "gat_smooth_observables_plan": (i32, [i32, i32, C.POINTER(SmoothConfig), C.POINTER(SmoothPlan)]),
+        "gat_snapshot_fix": (i32, [vp] * 7 + [i32, i32, C.POINTER(SnapConfig)] + [vp] * 7),
+        "gat_snapshot_fix_host": (i32, [vp] * 6 + [i32, i32, C.POINTER(SnapConfig)] + [vp] * 7),
+        "gat_snapshot_fix_plan": (i32, [i32, i32, C.POINTER(SnapConfig), C.POINTER(FixPlan)]),
         "gat_lnav_page18_host": (i32, [vp, i32, vp]),
         "gat_lnav_page18_words_host": (i32, [vp, vp]),
         "gat_tracking_update_weighted": (i32, [vp, vp, vp, i32, i32, C.POINTER(LoopConfig), vp, vp, vp, vp, vp]),

@@ -24,7 +24,7 @@ SOURCES = ["gat_dc_f0.hip", "gat_dc_f1.hip", "gat_dc_f2.hip", "gat_dc_f3.hip", "
            "gat_nav.hip", "gat_nav_api.cpp", "gat_fix.hip", "gat_fix_api.cpp",
            "gat_obs.hip", "gat_obs_api.cpp", "gat_raim.hip", "gat_raim_api.cpp",
            "gat_vel.hip", "gat_vel_api.cpp", "gat_atm.hip", "gat_atm_api.cpp",
-           "gat_smooth.hip", "gat_smooth_api.cpp"]
+           "gat_smooth.hip", "gat_smooth_api.cpp", "gat_snap.hip", "gat_snap_api.cpp"]
 # gat_version.cpp is not in SOURCES: it is compiled at every link with the build's identity (git commit, flags)
 # every header a source may include (csrc/*.h, csrc/*.inc, the public header): a newer one rebuilds every object
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc"))) + [os.path.join(ROOT, "include", "gat.h")]

@@ -1928,6 +1928,99 @@ typedef struct gat_smooth_plan {
 GAT_API int32_t gat_smooth_observables_plan(int32_t num_epochs, int32_t num_channels, const gat_smooth_config *config,
                                             gat_smooth_plan *plan);
 
+/* ---- snapshot fix: a coarse-time position from code phases alone -------------------------------------------------------------
+ * Every stage behind the loop takes transmit times as whole milliseconds and a fraction, and only gat_observables makes the
+ * whole milliseconds: it needs bit sync, frame sync and a decoded TOW.  gat_snapshot_fix needs the fraction alone -- what
+ * gat_observables writes as tx_frac, or an acquisition's code phase over the chipping rate --, the ephemerides, a position
+ * known to tens of kilometres and a clock known to tens of seconds: the whole milliseconds are resolved against the
+ * predicted ranges, and a solve of five unknowns finds position, clock bias and the error of the coarse time together
+ * (coarse-time navigation).  The rule is csrc/gat_snap.h on top of gat_fix.h and gat_vel.h: FP64, no contraction, no libm
+ * transcendental, every sum in channel order from +0, the same text in the kernel and in the host twin, the same bits.
+ * Per epoch (K <= 64 channels; Lambda = c 1e-3):
+ *   fraction code_frac [E][K], the transmit time modulo 1 ms in seconds; not finite or outside [0, 1e-3): no measurement.
+ *            phi = rx_frac - code_frac, plus 1e-3 with the borrow beta = 1 where it is negative; z = c phi.
+ *   predict  at a state (x, y, z, b, t_c) -- first (prior, 0, 0), the prior prior_xyz [E][3] or config.init_xyz -- the
+ *            transmit time is R - t_c - tau, R = rx_ms 1e-3 + rx_frac, tau = 0.075 s, then r / c of the last range, three
+ *            evaluations as the velocity fix does; clock, orbit and their rates by the fix's and the velocity fix's
+ *            expressions; p = r + b - c dts with the fix's Earth-rotation turn; sin el as the fix's.
+ *   usable   a channel counts (num_valid) when its ephemeris is usable as in gat_position_fix, its fraction and the
+ *            reception are given and its first predicted state is finite; it is used when besides its weight is finite and
+ *            > 0.  Fewer than 5 used channels: GAT_SNAP_FEW_SATS.
+ *   integers the reference k0 is the used channel with the largest predicted sin el, the lowest index on a tie (within 1e6 m
+ *            of the centre every sin el is 0: the lowest used channel).  n_k0 = rint((p_k0 - z_k0) / Lambda); n_k = rint(q_k),
+ *            q_k = (p_k - p_k0 + n_k0 Lambda + z_k0 - z_k) / Lambda, for every usable channel.  GAT_SNAP_AMBIGUOUS: a used
+ *            channel has |q_k - n_k| > 0.5 - ambiguity_margin; the fix stands.  A |q| above 1e6: GAT_SNAP_NONFINITE.  A wrong
+ *            n_k0 shifts every n_k alike and is absorbed by b and one millisecond of t_c: no error.  The margin guards a prior
+ *            within (0.5 - margin) Lambda / 2 of the truth in every relative range (30 km and 20 s with the default); far
+ *            beyond it a relative error near a whole Lambda clears the margin with a wrong integer: with more than five
+ *            used channels rms_residual_m then shows hundreds of metres, and gat_position_fix_raim finds it in the times.
+ *   solver   rho_k = n_k Lambda + z_k stays fixed.  An iteration: per usable channel the satellite at its own time (rx_ms -
+ *            n_k - beta_k) 1e-3 + code_frac_k - t_c, the fix's row with v = rho - (r + b - c dts), the row a = (-los, 1,
+ *            -(los . v_sat - c ddts)), the satellite's velocity turned as its position; the 20 sums of w a_i a_j (i <= j)
+ *            and w a_i v over the used channels; a 5 x 5 Cholesky with the fix's pivot rule; the state moves by the step.
+ *            A pass ends when |d_xyz| < tol_m or after max_iter iterations (GAT_SNAP_NOT_CONVERGED, the outputs stand).
+ *            GAT_SNAP_SINGULAR and GAT_SNAP_NONFINITE as the fix's; FEW_SATS, SINGULAR and NONFINITE end the epoch with every
+ *            output zero (tx_ms and rx_ms_out -1) but status, num_valid, num_used and iterations.
+ *   again    after a converged pass the integers are resolved once more at the solved state; if a used channel's changed, one
+ *            more pass runs from that state (GAT_SNAP_RERESOLVED).
+ *   mask     then the fix's mask at the solved state, with at least 5 channels kept (GAT_SNAP_MASKED, GAT_SNAP_MASK_STARVED).
+ *   record   the rows once more at the final state: rms_residual_m over the used channels; pdop, gdop (x, y, z, b) and tdop
+ *            (t_c, s / m) from the diagonal of the unweighted 5 x 5 (A^T A)^-1; clock_bias_s = b / c; coarse_time_s = t_c.
+ * Optional outputs (null: not written): tx_ms int32 [E][K] = (rx_ms - n_k - beta_k - m) mod 604800000 with m = rint(1000 t_c),
+ * -1 for a channel that does not count; rx_ms_out int32 [E] = (rx_ms - m) mod 604800000; n_ms int32 [E][K]; resid, sin_el
+ * double [E][K] and used uint8 [E][K] with the fix's conventions.  tx_ms, the caller's code_frac, rx_ms_out and rx_frac go
+ * into gat_position_fix, gat_position_fix_raim, gat_range_corrections and gat_velocity_fix as they are.  The true t_c is a
+ * whole number of milliseconds (the fraction of the clock's error is b); an m off by one moves every satellite by a
+ * millisecond of its flight, every range by less than 1 m, and is not flagged.  One epoch never touches another.
+ * gat_snapshot_fix enqueues one kernel of the fix's geometry on the context's stream (a wave an epoch, a lane a channel, four
+ * epochs a workgroup; the satellite is evaluated again every iteration), does not synchronise, allocates nothing and uses no
+ * atomics.  Refusals, all before any launch or write: GAT_ERR_ARG for a null required pointer (ephemerides, code_frac, rx_ms,
+ * rx_frac, config, fixes), a wrong struct_size, E or K < 1, max_iter < 1, tol_m not > 0, a mask_sin or init_xyz that is not
+ * finite, an ambiguity_margin outside [0, 0.5] and non-zero flags; GAT_ERR_RANGE for K above GAT_MAX_FIX_CHANNELS and E above
+ * GAT_MAX_FIX_EPOCHS. */
+#define GAT_SNAP_FEW_SATS 1
+#define GAT_SNAP_SINGULAR 2
+#define GAT_SNAP_NONFINITE 4
+#define GAT_SNAP_NOT_CONVERGED 8
+#define GAT_SNAP_MASK_STARVED 16
+#define GAT_SNAP_MASKED 32
+#define GAT_SNAP_AMBIGUOUS 64
+#define GAT_SNAP_RERESOLVED 128
+typedef struct gat_snap_config {
+    uint32_t struct_size;    /* sizeof(gat_snap_config) */
+    int32_t max_iter;        /* iterations a pass, >= 1 (10) */
+    double tol_m;            /* > 0 (1e-4) */
+    double mask_sin;         /* sin of the elevation mask; -1: off */
+    double init_xyz[3];      /* the prior of every epoch without prior_xyz, m */
+    double ambiguity_margin; /* 0 .. 0.5 (0.1) */
+    uint32_t flags;          /* 0 */
+    uint32_t reserved;
+} gat_snap_config;
+typedef struct gat_snap_fix {
+    int32_t status;       /* GAT_SNAP_* bits; 0: a converged fix with every integer clear of the margin */
+    int32_t num_valid;    /* channels that count in this epoch */
+    int32_t num_used;     /* channels in the last pass's equations */
+    int32_t iterations;
+    double x, y, z;       /* ECEF at reception, m */
+    double clock_bias_s;  /* b / c */
+    double coarse_time_s; /* t_c: the receiver's coarse clock minus the time the satellites were evaluated at */
+    double rms_residual_m;
+    double last_step_m;
+    double gdop, pdop;
+    double tdop;          /* s / m */
+} gat_snap_fix;
+GAT_API int32_t gat_snapshot_fix(gat_ctx *ctx, const gat_ephemeris *eph_dev, const double *code_frac_dev, const int32_t *rx_ms_dev,
+                                 const double *rx_frac_dev, const double *prior_xyz_dev, const double *weights_dev, int32_t num_epochs,
+                                 int32_t num_channels, const gat_snap_config *config, gat_snap_fix *fixes_dev, int32_t *tx_ms_dev,
+                                 int32_t *rx_ms_out_dev, int32_t *n_ms_dev, double *resid_dev, double *sin_el_dev, uint8_t *used_dev);
+/* The same rule in plain loops on the HOST: every pointer is host memory; the bit-exact reference of the device call. */
+GAT_API int32_t gat_snapshot_fix_host(const gat_ephemeris *eph_host, const double *code_frac_host, const int32_t *rx_ms_host,
+                                      const double *rx_frac_host, const double *prior_xyz_host, const double *weights_host,
+                                      int32_t num_epochs, int32_t num_channels, const gat_snap_config *config, gat_snap_fix *fixes,
+                                      int32_t *tx_ms, int32_t *rx_ms_out, int32_t *n_ms, double *resid, double *sin_el, uint8_t *used);
+/* What gat_snapshot_fix would do with a call (csrc/gat_snap_plan.h): gat_position_fix's geometry, its own LDS (20 terms). */
+GAT_API int32_t gat_snapshot_fix_plan(int32_t num_epochs, int32_t num_channels, const gat_snap_config *config, gat_fix_plan *plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1858,4 +1858,89 @@ function smooth_observables_plan(num_epochs::Integer, num_channels::Integer, cfg
     plan[]
 end
 
+# ---- snapshot fix: a coarse-time position from code phases alone (include/gat.h) ----
+const GAT_SNAP_FEW_SATS = Int32(1)
+const GAT_SNAP_SINGULAR = Int32(2)
+const GAT_SNAP_NONFINITE = Int32(4)
+const GAT_SNAP_NOT_CONVERGED = Int32(8)
+const GAT_SNAP_MASK_STARVED = Int32(16)
+const GAT_SNAP_MASKED = Int32(32)
+const GAT_SNAP_AMBIGUOUS = Int32(64)
+const GAT_SNAP_RERESOLVED = Int32(128)
+# struct gat_snap_config (64 bytes)
+struct SnapConfig
+    struct_size::UInt32
+    max_iter::Int32
+    tol_m::Float64
+    mask_sin::Float64
+    init_xyz::NTuple{3,Float64}
+    ambiguity_margin::Float64
+    flags::UInt32
+    reserved::UInt32
+end
+SnapConfig(; max_iter::Integer = 10, tol_m::Real = 1e-4, mask_sin::Real = -1.0, init_xyz = (0.0, 0.0, 0.0), ambiguity_margin::Real = 0.1) =
+    SnapConfig(UInt32(sizeof(SnapConfig)), Int32(max_iter), Float64(tol_m), Float64(mask_sin), Float64.(Tuple(init_xyz)), Float64(ambiguity_margin),
+               UInt32(0), UInt32(0))
+# struct gat_snap_fix (96 bytes)
+struct SnapFix
+    status::Int32                 # GAT_SNAP_* bits
+    num_valid::Int32
+    num_used::Int32
+    iterations::Int32
+    x::Float64                    # ECEF at reception, m
+    y::Float64
+    z::Float64
+    clock_bias_s::Float64
+    coarse_time_s::Float64
+    rms_residual_m::Float64
+    last_step_m::Float64
+    gdop::Float64
+    pdop::Float64
+    tdop::Float64                 # s / m
+end
+# the position, clock bias and coarse-time error of every epoch from the fractions of its transmit times; code_frac [K x E], rx_ms,
+# rx_frac, fixes [E]; prior_xyz [3 x E], weights, tx_ms, n_ms, resid, sin_el, used [K x E] and rx_ms_out [E] may be C_NULL.  Enqueues only.
+function snapshot_fix!(ctx::Context, eph::Ptr{Ephemeris}, code_frac::Ptr{Float64}, rx_ms::Ptr{Int32}, rx_frac::Ptr{Float64},
+                       num_epochs::Integer, num_channels::Integer, cfg::SnapConfig, fixes::Ptr{SnapFix};
+                       prior_xyz::Ptr{Float64} = Ptr{Float64}(C_NULL), weights::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                       tx_ms::Ptr{Int32} = Ptr{Int32}(C_NULL), rx_ms_out::Ptr{Int32} = Ptr{Int32}(C_NULL), n_ms::Ptr{Int32} = Ptr{Int32}(C_NULL),
+                       resid::Ptr{Float64} = Ptr{Float64}(C_NULL), sin_el::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                       used::Ptr{UInt8} = Ptr{UInt8}(C_NULL))
+    check(ctx, ccall((:gat_snapshot_fix, libgat), Int32,
+                     (Ptr{Cvoid}, Ptr{Ephemeris}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ref{SnapConfig},
+                      Ptr{SnapFix}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+                     ctx.handle, eph, code_frac, rx_ms, rx_frac, prior_xyz, weights, Int32(num_epochs), Int32(num_channels), Ref(cfg), fixes, tx_ms,
+                     rx_ms_out, n_ms, resid, sin_el, used))
+end
+# the same rule on host memory, the bit-exact reference of the device call: code_frac [K, E]; returns
+# (fixes [E], tx_ms [K, E], rx_ms_out [E], n_ms [K, E], resid [K, E], sin_el [K, E], used [K, E])
+function snapshot_fix_host(eph::Vector{Ephemeris}, code_frac::Matrix{Float64}, rx_ms::Vector{Int32}, rx_frac::Vector{Float64};
+                           prior_xyz::Union{Nothing,Matrix{Float64}} = nothing, weights::Union{Nothing,Matrix{Float64}} = nothing,
+                           cfg::SnapConfig = SnapConfig())
+    K, E = size(code_frac)
+    fixes = Vector{SnapFix}(undef, E)
+    tx_ms = zeros(Int32, K, E)
+    rx_ms_out = zeros(Int32, E)
+    n_ms = zeros(Int32, K, E)
+    resid = zeros(Float64, K, E)
+    sin_el = zeros(Float64, K, E)
+    used = zeros(UInt8, K, E)
+    rc = ccall((:gat_snapshot_fix_host, libgat), Int32,
+               (Ptr{Ephemeris}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ref{SnapConfig}, Ptr{SnapFix},
+                Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+               eph, code_frac, rx_ms, rx_frac, prior_xyz === nothing ? Ptr{Float64}(C_NULL) : pointer(prior_xyz),
+               weights === nothing ? Ptr{Float64}(C_NULL) : pointer(weights), Int32(E), Int32(K), Ref(cfg), fixes, tx_ms, rx_ms_out, n_ms, resid,
+               sin_el, used)
+    rc == GAT_OK || throw(GatError(rc, "gat_snapshot_fix_host"))
+    fixes, tx_ms, rx_ms_out, n_ms, resid, sin_el, used
+end
+# what snapshot_fix! would do with a call, without a device
+function snapshot_fix_plan(num_epochs::Integer, num_channels::Integer, cfg::SnapConfig = SnapConfig())
+    plan = Ref(FixPlan(UInt32(sizeof(FixPlan)), 0, 0, 0, 0, 0, 0))
+    rc = ccall((:gat_snapshot_fix_plan, libgat), Int32, (Int32, Int32, Ref{SnapConfig}, Ref{FixPlan}), Int32(num_epochs), Int32(num_channels),
+               Ref(cfg), plan)
+    rc == GAT_OK || throw(GatError(rc, "gat_snapshot_fix_plan"))
+    plan[]
+end
+
 end # module
