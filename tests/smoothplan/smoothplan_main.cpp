@@ -4,10 +4,11 @@
 // segment combine must be associative on random triples and agree with pushing the epochs one by one.  The twin then runs on heap
 // buffers of exactly the extents the call describes -- every subset of the optional outputs, with and without Doppler and mask -- so
 // that AddressSanitizer sees any access outside them, and the four stages of the device split, walked here in plain loops over the
-// same plan (runs, chunk segments, the channels' scan, emit, output), must give the twin's bytes.  Last, hostile entries: NaN, the
-// infinities, the largest finite values and the integer extremes in every input; everything must stay defined (the sanitizers'
-// business, float-cast-overflow among them) and no channel may touch another.  Built with
+// same plan (runs, chunk segments, the channels' scan with one, two and three chunks a lane, emit, output), must give the twin's
+// bytes.  Last, hostile entries: NaN, the infinities, the largest finite values and the integer extremes in every input; everything
+// must stay defined (the sanitizers' business, float-cast-overflow among them) and no channel may touch another.  Built with
 // -fsanitize=address,undefined,float-cast-overflow by tests/test_smoothing_plan_host.py.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -388,8 +389,10 @@ void staged(const SmPlan &p, const SmIn &in, const SmOut &out)
 
 void twin(std::mt19937_64 &rng)
 {
-    const int shapes[][3] = {{1, 1, 1}, {2, 3, 1}, {255, 5, 7}, {256, 1, 256}, {257, 64, 2}, {3 * 256 + 7, 5, 259}, {3 * 256 + 7, 12, 65536}, {700, 33, 40}};
-    int runs = 0;
+    // the last two: 66 and 129 chunks, where a lane of the channel scan holds two and three chunks and the lanes past the last idle
+    const int shapes[][3] = {{1, 1, 1}, {2, 3, 1}, {255, 5, 7}, {256, 1, 256}, {257, 64, 2}, {3 * 256 + 7, 5, 259}, {3 * 256 + 7, 12, 65536}, {700, 33, 40},
+                             {66 * 256 - 255, 5, 257}, {129 * 256 - 255, 5, 65536}};
+    int runs = 0, deepest = 0;
     for (const auto &s : shapes) {
         const int E = s[0], K = s[1], W = s[2];
         for (int variant = 0; variant < 4; ++variant) { // bit 0: rate test and Doppler, bit 1: mask
@@ -402,6 +405,7 @@ void twin(std::mt19937_64 &rng)
             a.out = all.out;
             SmPlan p{};
             CHECK(sm_plan(a, &p).code == GAT_OK, "E %d K %d refused", E, K);
+            deepest = std::max(deepest, (p.chunks + kSmWave - 1) / kSmWave);
             sm_host_run(p, a.in, all.out);
             int measured = 0, arcs = 0, smoothed = 0;
             for (size_t i = 0; i < (size_t)E * K; ++i) measured += all.status[i] & 1, smoothed += all.count[i] > 1;
@@ -418,7 +422,8 @@ void twin(std::mt19937_64 &rng)
             CHECK(outputs_equal(all, dev, E, K), "E %d K %d W %d variant %d: the staged split differs from the twin", E, K, W, variant);
         }
     }
-    std::printf("twin ran %d times on exact buffers\n", runs);
+    CHECK(deepest == 3, "no plan gives a lane of the channel scan three chunks (%d)", deepest);
+    std::printf("twin ran %d times on exact buffers, up to %d chunks a lane of the channel scan\n", runs, deepest);
 }
 
 // every input hostile in turn: everything stays defined, the staged split agrees, other channels keep their bytes
